@@ -6,7 +6,15 @@ Workload (BASELINE.json configs[1], the configuration the metric is quoted on):
     twice shifted (xk ~ N(0,1), sj ~ U(-1/2, 1/2)), q ~ N(0,1), lambda = sigma = 1.  Synthetic data.
 A "step" is one prox! call over the whole n-vector.  Inputs are resident in HBM before the timed region.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--elements N] [--no-cpu] [--no-extra]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--elements N] [--dump-outputs DIR] [--full [--no-cpu] [--no-extra]]
+
+A plain run sets up, warms up, times the K steps and prints the result line (metric, value, unit, ms_per_step, roofline, ...).
+--dump-outputs DIR  after the timed steps, writes what the last timed step computed: DIR/y.npy (float64), the prox! result y --
+                    all of it up to DUMP_SAMPLE elements, above that the elements at a fixed, seeded set of indices, which go to
+                    DIR/y_index.npy (float64).  The inputs are the same from run to run (fixed seed), so two builds can be
+                    compared output for output.  Rank 0's shard only.
+--full              also the secondary legs below (their own runs: other operators, the captured-graph iteration, the CPU
+                    baselines); --no-extra / --no-cpu leave out the operator / CPU legs of a --full run.
 
 Multi-GPU (launched by torch.distributed.run, one rank per GPU): the operators are separable, so every rank
 owns its own contiguous n-element shard and there is NO data-path collective ("replicas / weak scaling",
@@ -15,10 +23,12 @@ SURVEY.md 8e); the only collectives are the barrier and a MAX over ranks of the 
 One JSON line on rank 0: metric/value/... plus
   roofline      -- dominant kernel (k_sep_lds<OpL1Box>): algorithmic bytes (32 B/element) / average launch
                    duration measured with HIP events on the launching stream over the timed region
+and, with --full only:
   cpu_baseline  -- the CPU oracle (literal single-thread C restatement of the reference's Julia loop; the
                    reference itself cannot run here: no Julia) timed on rank 0's host core
   other_operators         -- the other BASELINE configs and the adjacent calls (iprox!, psi(y), prox! + psi in one pass,
                              ShiftedNormL1B2, vector bounds, the PCIe-inclusive host-pointer form) at full size
+  solver_iteration_in_a_graph -- one solver-style iteration at solver sizes, call by call and as one captured graph
   cpu_port_other_configs  -- the single-thread CPU port on bounded samples of the other configs
 """
 import argparse
@@ -34,6 +44,8 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak, /opt/skills/guides/MI355X_MICROARCH.md "Chip-level parameters"
 BYTES_PER_ELEM = 32    # read q, xk, sj + write y (scalar bounds, no mask)
 SYNTH_SEED = 20250613  # spx_synth_fill seed (+ rank); streams: 0 = xk, 1 = sj, 2 = q
+DUMP_SAMPLE = 3_000_000  # --dump-outputs: at most this many values of y (+ as many indices): 48 MB in all
+DUMP_SEED = 20251015     # --dump-outputs: the seed of the sampled indices
 
 
 def main():
@@ -42,9 +54,15 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--elements", dest="n", type=int, default=100_000_000, help="elements per GPU")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary operators")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write y of the last timed step (a fixed, seeded sample above %d elements) as DIR/*.npy" % DUMP_SAMPLE)
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary legs: other operators, the captured-graph iteration, the CPU baselines")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the secondary operators")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` outside a launcher: start the N ranks ourselves (one per GPU, RCCL) as a child
@@ -82,8 +100,7 @@ def main():
         else:
             dist.init_process_group(backend)
 
-    import __graft_entry__ as ge
-    s = ge.build()
+    s = _load(with_oracle=args.full)  # the CPU oracle serves the --full legs only
     L = s._lib.load()
 
     n = args.n
@@ -160,13 +177,16 @@ def main():
                      **_pmc_traffic(n)},
     }
 
-    if rank == 0 and not args.no_extra:
+    if rank == 0 and args.dump_outputs:
+        _dump_outputs(args.dump_outputs, y, torch)
+
+    if rank == 0 and args.full and not args.no_extra:
         out["other_operators"] = _extra(s, L, ctx, dev, n, torch)
         try:
             out["solver_iteration_in_a_graph"] = _graph_iteration(s, dev, torch)
         except Exception as e:  # reported, never fatal for the headline line
             out["solver_iteration_in_a_graph"] = {"error": "%s: %s" % (type(e).__name__, e)}
-    if rank == 0 and not args.no_cpu:
+    if rank == 0 and args.full and not args.no_cpu:
         out["cpu_baseline"] = _cpu_baseline(s, psi, q, xk, sj, y, n, torch)
         if not args.no_extra:
             out["cpu_port_other_configs"] = _cpu_other_configs()
@@ -175,6 +195,41 @@ def main():
         print(json.dumps(out))
     if dist_on:
         dist.destroy_process_group()
+
+
+def _load(with_oracle):
+    """The package with libspx loaded, as build() left it.  build() takes a lock file next to the library even when there is
+    nothing to rebuild, and a built checkout may be read-only to whoever benchmarks it: so when the library is there and no
+    source of it is newer (the set build() compares with), it is loaded without build(); otherwise build() rebuilds it, or
+    fails loudly where it cannot.  With the oracle: oracle.build() runs make only when its library is missing or stale."""
+    import __graft_entry__ as ge
+    csrc = os.path.join(ge.PKG, "csrc")
+    srcs = [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".hpp", ".sh"))]
+    srcs.append(os.path.join(ROOT, "include", "spx.h"))
+    lib = os.path.join(ge.PKG, "lib", os.environ.get("SPX_LIB_NAME", "libspx.so"))
+    if ge._stale(lib, srcs):
+        return ge.build(with_oracle=with_oracle)
+    if with_oracle:
+        from oracle import oracle
+        oracle.build()
+    import spx_amd
+    spx_amd._lib.load()
+    return spx_amd
+
+
+def _dump_outputs(d, y, torch):
+    """y of the last timed step as DIR/y.npy (float64): the whole vector up to DUMP_SAMPLE elements, above that the elements at
+    DUMP_SAMPLE indices drawn with DUMP_SEED (sorted, duplicates dropped), which go to DIR/y_index.npy (float64, exact below 2^53)."""
+    import numpy as np
+    n = y.numel()
+    if n <= DUMP_SAMPLE:
+        idx = np.arange(n, dtype=np.int64)
+    else:
+        idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, size=DUMP_SAMPLE, dtype=np.int64))
+    vals = y[torch.from_numpy(idx).to(y.device)].cpu().numpy()
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "y.npy"), vals.astype(np.float64, copy=False))
+    np.save(os.path.join(d, "y_index.npy"), idx.astype(np.float64))
 
 
 def _pmc_traffic(n):

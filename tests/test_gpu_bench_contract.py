@@ -1,6 +1,7 @@
 """bench.py's output contract on a small workload: one JSON line with the keys the driver reads, at N = 1 and in a
 two-rank rehearsal (both ranks on the one GPU of the test box, barrier / MAX over gloo -- the driver's own multi-GPU
-runs use nccl, one rank per GPU; the code path around the timed region is the same)."""
+runs use nccl, one rank per GPU; the code path around the timed region is the same); a plain run carries none of the
+--full legs, and --dump-outputs writes the same y from run to run -- the oracle's, on host-regenerated inputs."""
 import json
 import os
 import subprocess
@@ -29,7 +30,8 @@ def _line(out):
 def test_single_gpu_line():
     _gpu()
     env = dict(os.environ, SPX_NO_BUILD="1")
-    p = subprocess.run([sys.executable, "bench.py", "--steps", "5", "--warmup", "2", "--elements", "4000000", "--no-extra"],
+    p = subprocess.run([sys.executable, "bench.py", "--steps", "5", "--warmup", "2", "--elements", "4000000", "--no-extra",
+                        "--full"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-2000:]
     d = _line(p.stdout)
@@ -41,6 +43,35 @@ def test_single_gpu_line():
     c = d["cpu_baseline"]
     assert c["kind"] == "port" and c["cores"] == 1 and c["value"] > 0
     assert "workload" in d["config"]
+
+
+def test_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    _gpu()
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    from oracle import oracle
+    n, env = 4000000, dict(os.environ, SPX_NO_BUILD="1")
+    ys = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        p = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--elements", str(n), "--dump-outputs", str(d)],
+                           cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+        assert p.returncode == 0, p.stderr[-2000:]
+        line = _line(p.stdout)
+        assert KEYS <= set(line) and line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0
+        assert not {"cpu_baseline", "other_operators", "solver_iteration_in_a_graph", "cpu_port_other_configs"} & set(line)
+        assert sorted(os.listdir(d)) == ["y.npy", "y_index.npy"]
+        assert sum(os.path.getsize(d / f) for f in os.listdir(d)) <= 64 * 2**20
+        y, idx = np.load(d / "y.npy"), np.load(d / "y_index.npy")
+        assert y.dtype == np.float64 and idx.dtype == np.float64 and y.shape == idx.shape
+        assert 0 < y.size <= bench.DUMP_SAMPLE < n and np.all(np.diff(idx) > 0) and 0 <= idx[0] and idx[-1] < n
+        ys.append((y, idx))
+    (ya, ia), (yb, ib) = ys
+    assert np.array_equal(ia, ib) and np.array_equal(ya.view(np.int64), yb.view(np.int64))
+    xh, sh, qh = (oracle.synth_fill(n, bench.SYNTH_SEED, stream, kind, 1.0, 4) for stream, kind in ((0, 1), (1, 0), (2, 1)))
+    ref = oracle.prox_l1_box(qh, xh, sh, 1.0, 1.0, -1.0, 1.0)
+    assert np.array_equal(ya.view(np.int64), ref[ia.astype(np.int64)].view(np.int64))
 
 
 def _free_port():

@@ -138,3 +138,31 @@ def test_bench_refuses_a_world_size_that_disagrees_with_gpus():
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1"], env=env,
                        capture_output=True, text=True, timeout=120)
     assert p.returncode != 0 and "WORLD_SIZE=3" in (p.stderr + p.stdout)
+
+
+def test_bench_loads_a_built_library_without_build(s, monkeypatch):
+    """A built checkout may be read-only to whoever benchmarks it, and build() opens a lock file next to the library even
+    when there is nothing to rebuild: bench.py loads a library that no source is newer than without going through build()."""
+    import os
+    import sys
+    import __graft_entry__ as ge
+    sys.path.insert(0, ge.ROOT)
+    import bench
+
+    def no_build(*a, **k):
+        raise AssertionError("build() called for an up-to-date library")
+
+    monkeypatch.delenv("SPX_LIB_NAME", raising=False)
+    monkeypatch.setattr(ge, "build", no_build)
+    assert os.path.exists(os.path.join(ge.PKG, "lib", "libspx.so"))
+    assert bench._load(with_oracle=False) is s and s._lib.load() is not None
+    assert bench._load(with_oracle=True) is s
+    import time
+    src = os.path.join(ge.PKG, "csrc", "spx_common.hpp")
+    st = os.stat(src)
+    try:
+        os.utime(src, (time.time() + 5, time.time() + 5))               # a source newer than the library: build() it is
+        with pytest.raises(AssertionError, match="build"):
+            bench._load(with_oracle=False)
+    finally:
+        os.utime(src, (st.st_atime, st.st_mtime))

@@ -19,7 +19,8 @@ def test_oracle_golden_suite_under_asan_ubsan():
         pytest.skip("libasan not installed")
     subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "-s", "asan"])
     env = dict(os.environ)
-    env.update(SPX_ORACLE_SO=os.path.join(ROOT, "oracle", "_asan", "libspx_oracle_asan.so"), LD_PRELOAD=libasan,
+    preload = " ".join(p for p in (libasan, env.get("LD_PRELOAD", "")) if p)  # the runtime first; keep what was preloaded already
+    env.update(SPX_ORACLE_SO=os.path.join(ROOT, "oracle", "_asan", "libspx_oracle_asan.so"), LD_PRELOAD=preload,
                ASAN_OPTIONS="detect_leaks=0:abort_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_oracle_golden.py"), "-q", "-x",
                         "-p", "no:cacheprovider"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
