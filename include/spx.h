@@ -371,6 +371,9 @@ int spx_obj_l1_b2(spx_ctx* ctx, const double* y, const double* xk, const double*
 /* Groups are contiguous index ranges (the reference's `idx` entries as UnitRanges / [:]):
  *   group_offsets != NULL : CSR offsets (device, int64, length ngroups+1, 0-based, non-decreasing,
  *                           offsets[0] >= 0, offsets[ngroups] <= n); group g = [off[g], off[g+1]).
+ *                           psi(y) (spx_obj_group_l2*) checks this on the device: a violation is SPX_ERR_INVALID_ARG
+ *                           (NaN in a device value target).  The prox! entries do not check: what they compute or
+ *                           write on offsets that break it is undefined.
  *                           group_size is then a HINT: 0 = unknown, > 0 = an upper bound on the group sizes; a bound
  *                           <= 512 selects the register-tile kernels (a group that exceeds it is still computed
  *                           correctly, by the general kernel).

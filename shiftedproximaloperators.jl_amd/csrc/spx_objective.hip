@@ -229,7 +229,11 @@ __global__ __launch_bounds__(256) void k_obj_group(const T* __restrict__ y, cons
     const bool live = g < ngroups;
     int64_t lo = 0, hi = 0;
     if (live) {
-      if (offsets) { lo = offsets[g]; hi = offsets[g + 1]; }
+      if (offsets) {
+        lo = offsets[g]; hi = offsets[g + 1];
+        // contiguous CSR layouts: the offsets contract (include/spx.h), checked as k_obj_chunk_prefix does (bit 2)
+        if (!index) bad_index |= lo > hi || (g == 0 && lo < 0) || (g == ngroups - 1 && hi > n);
+      }
       else { lo = g * gsize; hi = lo + gsize; }
     }
     if (lo < 0) lo = 0;
@@ -287,9 +291,11 @@ __global__ __launch_bounds__(256) void k_obj_group(const T* __restrict__ y, cons
 constexpr int kObjChunk = 4096;
 constexpr int kObjFuseGroups = 256;   // the one-launch form of the chunked psi(y): at most this many (uniform) groups ...
 constexpr int kObjFuseChunks = 4096;  // ... and chunks (16 Mi elements): the last workgroup adds them, 16 loads per lane
-// chunks before group g (CSR layouts; uniform groups need no table)
+// chunks before group g (CSR layouts; uniform groups need no table).  Offsets that break the contract of include/spx.h
+// (decreasing, offsets[0] < 0, offsets[ngroups] > n) raise bit 2 of ws->infeasible: psi(y) is then an error (NaN in a device
+// value target).  Such layouts can total more chunks than the workspace holds: k_obj_chunks / k_obj_chunk_groups stop at kmax.
 __global__ __launch_bounds__(1024) void k_obj_chunk_prefix(const int64_t* __restrict__ offsets, int64_t ngroups, int64_t n,
-                                                            int64_t* __restrict__ prefix /* ngroups + 1 */) {
+                                                            int64_t* __restrict__ prefix /* ngroups + 1 */, ObjWs* ws) {
   __shared__ long long part[1024];
   const int t = threadIdx.x;
   const int64_t per = (ngroups + 1023) / 1024;
@@ -301,7 +307,12 @@ __global__ __launch_bounds__(1024) void k_obj_chunk_prefix(const int64_t* __rest
     return hi > lo ? (hi - lo + kObjChunk - 1) / kObjChunk : 0;
   };
   long long mine = 0;
-  for (int64_t g = g0; g < g1; ++g) mine += chunks_of(g);
+  bool bad = false;
+  for (int64_t g = g0; g < g1; ++g) {
+    mine += chunks_of(g);
+    bad |= offsets[g] > offsets[g + 1] || (g == 0 && offsets[0] < 0) || (g == ngroups - 1 && offsets[ngroups] > n);
+  }
+  if (bad) atomicOr(&ws->infeasible, 2);
   part[t] = mine;
   __syncthreads();
   if (t == 0) {
@@ -319,14 +330,15 @@ template <int MODE>
 __global__ __launch_bounds__(256) void k_obj_chunks(const double* __restrict__ y, const double* __restrict__ xk,
                                                      const double* __restrict__ sj, int64_t n,
                                                      const int64_t* __restrict__ offsets, int64_t gsize, int64_t ngroups,
-                                                     const int64_t* __restrict__ prefix, int64_t nchunks_uniform, int par,
-                                                     double rad, double* __restrict__ chunk_ss, ObjWs* ws,
+                                                     const int64_t* __restrict__ prefix, int64_t nchunks_uniform, int64_t kmax,
+                                                     int par, double rad, double* __restrict__ chunk_ss, ObjWs* ws,
                                                      ObjFin fin /* hdr != NULL (uniform groups, <= kObjFuseGroups of them, <= kObjFuseChunks
                                                                    chunks): the last workgroup also does k_obj_chunk_groups' and k_obj_final's work */,
                                                      const double* __restrict__ lambda) {
   __shared__ double lds4[4];
   const int t = threadIdx.x;
-  const int64_t K = prefix ? prefix[ngroups] : nchunks_uniform;
+  int64_t K = prefix ? prefix[ngroups] : nchunks_uniform;
+  if (K > kmax) K = kmax;  // (offsets that break the contract: chunk_ss holds kmax sums; k_obj_chunk_prefix has raised bit 2)
   const int64_t cpg = (gsize + kObjChunk - 1) / kObjChunk;  // (uniform groups)
   bool bad = false;
   for (int64_t k = blockIdx.x; k < K; k += gridDim.x) {
@@ -432,12 +444,13 @@ __global__ __launch_bounds__(256) void k_obj_chunks(const double* __restrict__ y
 }
 // ws->partial[b] = sum over the groups b, b + grid, ... of lambda_g sqrt(sum of the group's chunk sums, in index order)
 __global__ __launch_bounds__(256) void k_obj_chunk_groups(const double* __restrict__ chunk_ss, const int64_t* __restrict__ prefix,
-                                                           int64_t cpg, int64_t ngroups, const double* __restrict__ lambda,
-                                                           ObjWs* ws) {
+                                                           int64_t cpg, int64_t ngroups, int64_t kmax,
+                                                           const double* __restrict__ lambda, ObjWs* ws) {
   __shared__ double lds4[4];
   double acc = 0.0;
   for (int64_t g = blockIdx.x; g < ngroups; g += gridDim.x) {
-    const int64_t c0 = prefix ? prefix[g] : g * cpg, c1 = prefix ? prefix[g + 1] : (g + 1) * cpg;
+    const int64_t c0 = prefix ? prefix[g] : g * cpg, c1e = prefix ? prefix[g + 1] : (g + 1) * cpg;
+    const int64_t c1 = c1e < kmax ? c1e : kmax;  // (as k_obj_chunks)
     double ss = 0.0;
     for (int64_t c = c0 + threadIdx.x; c < c1; c += 256) ss += chunk_ss[c];
     ss = block_sum(ss, lds4);
@@ -595,13 +608,13 @@ int run_obj_group(spx_ctx* ctx, const T* y, const T* xk, const T* sj, int64_t n,
       if (!cfin.hdr) { const int rz = spx_zero_async(ctx, &ws->infeasible, sizeof(int)); if (rz) return rz; }
       double* chunk_ss = reinterpret_cast<double*>(static_cast<char*>(ctx->ws) + ss_off);
       int64_t* prefix = offsets ? reinterpret_cast<int64_t*>(static_cast<char*>(ctx->ws) + pre_off) : nullptr;
-      if (offsets) hipLaunchKernelGGL(k_obj_chunk_prefix, dim3(1), dim3(1024), 0, ctx->stream, offsets, ngroups, n, prefix);
+      if (offsets) hipLaunchKernelGGL(k_obj_chunk_prefix, dim3(1), dim3(1024), 0, ctx->stream, offsets, ngroups, n, prefix, ws);
       const auto bit3 = [](const void* p) { return (int)((reinterpret_cast<uintptr_t>(p) >> 3) & 1u); };
       const int par = (bit3(y) == bit3(xk) && bit3(y) == bit3(sj)) ? bit3(y) : -1;
       int64_t cb = kmax < (int64_t)ctx->num_cu * 64 ? kmax : (int64_t)ctx->num_cu * 64;
       if (cb < 1) cb = 1;
       hipLaunchKernelGGL((k_obj_chunks<MODE>), dim3((unsigned)cb), dim3(256), 0, ctx->stream, (const double*)y, (const double*)xk,
-                         (const double*)sj, n, offsets, gsize, ngroups, (const int64_t*)prefix, cpg * ngroups, par, rad, chunk_ss, ws,
+                         (const double*)sj, n, offsets, gsize, ngroups, (const int64_t*)prefix, cpg * ngroups, kmax, par, rad, chunk_ss, ws,
                          cfin, (const double*)lambda);
       if (cfin.hdr) {
         SPX_LAUNCH_CHECK();
@@ -610,13 +623,19 @@ int run_obj_group(spx_ctx* ctx, const T* y, const T* xk, const T* sj, int64_t n,
       }
       int64_t gb = ngroups < kObjBlocks ? ngroups : kObjBlocks;
       hipLaunchKernelGGL(k_obj_chunk_groups, dim3((unsigned)gb), dim3(256), 0, ctx->stream, (const double*)chunk_ss,
-                         (const int64_t*)prefix, cpg, ngroups, (const double*)lambda, ws);
+                         (const int64_t*)prefix, cpg, ngroups, kmax, (const double*)lambda, ws);
       if (MODE == 2 && offsets)  // the groups need not tile 0:n: the trust-region indicator covers every index
         hipLaunchKernelGGL(k_obj_linf_uncovered, dim3(256), dim3(256), 0, ctx->stream, (const double*)y, (const double*)sj, n, offsets,
                            ngroups, rad, ws);
       SPX_LAUNCH_CHECK();
       int bad_;
-      return obj_finish(ctx, ws, (int)gb, kRuleGroup, 1.0, 0.0, value, &bad_);
+      rc = obj_finish(ctx, ws, (int)gb, kRuleGroup, 1.0, 0.0, value, &bad_);
+      if (rc) return rc;
+      if (bad_ & 2) {  // (with a device value target the value is NaN instead: nothing is read back)
+        spx_set_error("invalid argument: group offsets decreasing or outside [0, n]");
+        return SPX_ERR_INVALID_ARG;
+      }
+      return SPX_OK;
     }
   }
   // lanes per group: about four elements per lane of a typical group (uniform size, the caller's size bound, or the average)
@@ -669,7 +688,8 @@ int run_obj_group(spx_ctx* ctx, const T* y, const T* xk, const T* sj, int64_t n,
   rc = obj_finish(ctx, ws, (int)blocks, kRuleGroup, 1.0, 0.0, value, &bad, fin.hdr != nullptr);
   if (rc) return rc;
   if (bad & 2) {  // (with a device value target the value is NaN instead: nothing is read back)
-    spx_set_error("invalid argument: group index outside [0, n) (BoundsError)");
+    spx_set_error(index ? "invalid argument: group index outside [0, n) (BoundsError)"
+                        : "invalid argument: group offsets decreasing or outside [0, n]");
     return SPX_ERR_INVALID_ARG;
   }
   return SPX_OK;

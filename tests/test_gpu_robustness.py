@@ -164,7 +164,8 @@ for n, binf, fast in ((120_000, 0, 1), (120_000, 1, 1), (3_000_000, 0, 1), (3_00
         return L.spx_prox_group_l2(ctx, y.data_ptr(), q.data_ptr(), x.data_ptr(), sj.data_ptr(), n, None, n, 1, lam.data_ptr(), ctypes.c_double(0.9))
     assert call() == 0
     torch.cuda.synchronize()
-    good = y.clone()
+    good = y.clone()                                   # no later call writes this copy
+    scratch = torch.empty_like(q)
     assert not bool(torch.isnan(good).any())
     assert L.spx_ctx_set_tuning(ctx, 102, 1) == 0      # the last workgroup of the team arrives late
     y.fill_(7.0)
@@ -172,11 +173,11 @@ for n, binf, fast in ((120_000, 0, 1), (120_000, 1, 1), (3_000_000, 0, 1), (3_00
     torch.cuda.synchronize()
     L.spx_ctx_set_tuning(ctx, 102, 0)
     nan = int(torch.isnan(y).sum())
-    rc_next = L.spx_prox_l1(ctx, good.data_ptr(), q.data_ptr(), x.data_ptr(), sj.data_ptr(), n, ctypes.c_double(1.0), ctypes.c_double(1.0))
+    rc_next = L.spx_prox_l1(ctx, scratch.data_ptr(), q.data_ptr(), x.data_ptr(), sj.data_ptr(), n, ctypes.c_double(1.0), ctypes.c_double(1.0))
     rc_sync = L.spx_sync(ctx)
     rc_after = call()
     torch.cuda.synchronize()
-    same = bool(torch.equal(y.view(torch.int64), (good if True else y).view(torch.int64))) if False else int(torch.isnan(y).sum()) == 0
+    same = bool(torch.equal(y.view(torch.int64), good.view(torch.int64)))   # the result after spx_sync: bit for bit the good one
     res.append((n, binf, fast, rc_launch, nan, rc_next, rc_sync, rc_after, int(same)))
 L.spx_ctx_set_tuning(ctx, 14, 1)
 print("RESULT", res)
@@ -186,8 +187,8 @@ print("RESULT", res)
 def test_a_team_of_workgroups_poisons_its_result_too(s):
     """Round 4: the team form (csrc/spx_group_team.hip) synchronises inside its launches like top-r and B2.  Hooks build, tuning key
     102: the last workgroup of the team takes part in no reduction and only runs once the others have given up -- on chip and
-    streamed, plain and Binf (fast path and generic body): NaN over the whole group, SPX_ERR_INTERNAL on the next call, a clean
-    result after spx_sync."""
+    streamed, plain and Binf (fast path and generic body): NaN over the whole group, SPX_ERR_INTERNAL on the next call, after
+    spx_sync the result of the call before the planted one, bit for bit."""
     lib = os.path.join(ROOT, "shiftedproximaloperators.jl_amd", "lib", "libspx_hooks.so")
     if not os.path.exists(lib):
         pytest.skip("libspx_hooks.so not built")
@@ -202,7 +203,7 @@ def test_a_team_of_workgroups_poisons_its_result_too(s):
         assert rc_launch == 0, what
         assert nan == n, "%r: the abandoned launch must poison the whole group (%d of %d NaN)" % (what, nan, n)
         assert rc_next == 7 and rc_sync == 7, what
-        assert rc_after == 0 and clean == 1, what
+        assert rc_after == 0 and clean == 1, "%r: after spx_sync the call returns the good result bit for bit" % (what,)
 
 
 def test_residency_cap_takes_the_smaller_grid_forms(s, orc):
