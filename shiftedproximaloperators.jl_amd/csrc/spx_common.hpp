@@ -233,7 +233,26 @@ __device__ __forceinline__ float jl_max(float x, float y) {
 // Base.sign: +-1.0, or x itself for +-0.0 / NaN
 __device__ __forceinline__ double jl_sign(double x) { return (x > 0.0) ? 1.0 : (x < 0.0) ? -1.0 : x; }
 // prox_zero(q, l, u) = min(max(q, l), u)   src/ShiftedProximalOperators.jl:203
-__device__ __forceinline__ double prox_zero(double q, double l, double u) { return jl_min(jl_max(q, l), u); }
+template <class T>
+__device__ __forceinline__ T prox_zero(T q, T l, T u) { return jl_min(jl_max(q, l), u); }
+
+namespace {
+// element terms of h (the objectives, spx_objective.hip, and the prox! fused with its value, spx_separable.hip)
+// (float overloads: the Float32 forms.  The reference forms xsy and every term in Float32 -- which entries are exactly zero,
+//  the rounding of each square root -- and adds them up in Float32; here the terms are Float32 values, the SUM is Float64.)
+struct TermL1 {  // NormL1 [ext]
+  __device__ __forceinline__ double operator()(double v) const { return fabs(v); }
+  __device__ __forceinline__ double operator()(float v) const { return (double)fabsf(v); }
+};
+struct TermL0 {  // NormL0, IndBallL0 [ext]
+  __device__ __forceinline__ double operator()(double v) const { return (v != 0.0) ? 1.0 : 0.0; }
+  __device__ __forceinline__ double operator()(float v) const { return (v != 0.0f) ? 1.0 : 0.0; }
+};
+struct TermLhalf {  // src/rootNormLhalf.jl:27-29
+  __device__ __forceinline__ double operator()(double v) const { return sqrt(fabs(v)); }
+  __device__ __forceinline__ double operator()(float v) const { return (double)__builtin_sqrtf(fabsf(v)); }
+};
+}  // namespace
 
 // sum over the 64 lanes of a wavefront, result in every lane (xor butterfly; DPP/permute lowered by hipcc)
 __device__ __forceinline__ double wave_sum(double v) {

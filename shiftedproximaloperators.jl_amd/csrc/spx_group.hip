@@ -446,23 +446,6 @@ __global__ __launch_bounds__(256) void k_group_lds(double* y, const double* q, c
   }
 }
 
-// ShiftedGroupNormL2 with CSR offsets that do not span 0:n: indices before offsets[0] / from offsets[ngroups] on keep
-// the caller's y minus the shift (src/shiftedGroupNormL2.jl:77 runs over every index)
-__global__ __launch_bounds__(256) void k_csr_uncovered(double* y, const double* xk, const double* sj,
-                                                        const int64_t* __restrict__ offsets, int64_t ngroups, int64_t n) {
-  int64_t head = offsets[0], tail0 = offsets[ngroups];
-  if (head < 0) head = 0;
-  if (head > n) head = n;
-  if (tail0 < head) tail0 = head;
-  if (tail0 > n) tail0 = n;
-  const int64_t total = head + (n - tail0);
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += stride) {
-    const int64_t i = (t < head) ? t : tail0 + (t - head);
-    y[i] = y[i] - (xk[i] + sj[i]);
-  }
-}
-
 // sol = (q + xk) + sj (:65 / :80), owner = -1
 __global__ __launch_bounds__(256) void k_gather_prepare(double* __restrict__ sol, int* __restrict__ owner,
                                                          const double* q, const double* xk, const double* sj, int64_t n) {
@@ -531,7 +514,7 @@ static int run_group(spx_ctx* ctx, double* y, const double* q, const double* xk,
   if (ngroups == 0) {  // no group at all: ShiftedGroupNormL2 still subtracts the shift everywhere (:77)
     if (!BINF && offsets) {
       SPX_ON_DEVICE(ctx);
-      hipLaunchKernelGGL(k_csr_uncovered, dim3(256), dim3(256), 0, ctx->stream, y, xk, sj, offsets, ngroups, n);
+      hipLaunchKernelGGL(k_csr_uncovered<double>, dim3(256), dim3(256), 0, ctx->stream, y, xk, sj, offsets, ngroups, n);
       SPX_LAUNCH_CHECK();
     }
     return SPX_OK;
@@ -607,7 +590,7 @@ static int run_group(spx_ctx* ctx, double* y, const double* q, const double* xk,
     }
     const bool pairs = !ragged_reg && (gsize & 1) == 0 && aligned;  // otherwise 8-byte loads
     if (!BINF && ragged_reg)  // offsets need not span 0:n (src/shiftedGroupNormL2.jl:77 runs over every index)
-      hipLaunchKernelGGL(k_csr_uncovered, dim3(256), dim3(256), 0, ctx->stream, y, xk, sj, offsets, ngroups, n);
+      hipLaunchKernelGGL(k_csr_uncovered<double>, dim3(256), dim3(256), 0, ctx->stream, y, xk, sj, offsets, ngroups, n);
 #define SPX_LAUNCH_REG(LPG, EPL)                                                                                    \
   do {                                                                                                              \
     if (pairs && gsize == (LPG) * (EPL)) {                                                                          \
@@ -676,7 +659,7 @@ static int run_group(spx_ctx* ctx, double* y, const double* q, const double* xk,
   if (gsize > 512 && gsize <= (BINF ? kLdsGroupMax : kLdsGroupMaxPlain)) {
     // 512 < group size (uniform) or size bound (ragged, CSR offsets): LDS-resident group per workgroup
     if (!BINF && offsets)
-      hipLaunchKernelGGL(k_csr_uncovered, dim3(256), dim3(256), 0, ctx->stream, y, xk, sj, offsets, ngroups, n);
+      hipLaunchKernelGGL(k_csr_uncovered<double>, dim3(256), dim3(256), 0, ctx->stream, y, xk, sj, offsets, ngroups, n);
     const size_t dyn = (size_t)gsize * 2 * sizeof(double);
     // per device (the attribute belongs to the function ON the current device) and cheap: set on every call that needs it,
     // no process-wide cache that a second GPU or a second thread would find in the wrong state
@@ -710,7 +693,7 @@ static int run_group(spx_ctx* ctx, double* y, const double* q, const double* xk,
     }
   }
   if (!BINF && offsets)
-    hipLaunchKernelGGL(k_csr_uncovered, dim3(256), dim3(256), 0, ctx->stream, y, xk, sj, offsets, ngroups, n);
+    hipLaunchKernelGGL(k_csr_uncovered<double>, dim3(256), dim3(256), 0, ctx->stream, y, xk, sj, offsets, ngroups, n);
   const double avg = (double)n / (double)ngroups;
   if (avg <= 2048.0) {
     // lanes per group by the average size (ragged groups without a size bound from the caller, or with one above 512): a

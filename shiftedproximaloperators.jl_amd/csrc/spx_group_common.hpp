@@ -1,6 +1,7 @@
 // spx_group_common.hpp -- device code shared by the group kernels (spx_group.hip: register tiles, wavefront / workgroup per
 // group; spx_group_team.hip: a TEAM OF WORKGROUPS per group): team reductions, element providers, the Binf root find
 // (src/shiftedGroupNormL2Binf.jl:85-108) and the per-group body (src/shiftedGroupNormL2.jl:67-76, shiftedGroupNormL2Binf.jl:84-117).
+// k_csr_uncovered, at the end, serves both precisions (spx_group.hip, spx_group_f32.hip).
 #pragma once
 #include <cmath>
 
@@ -986,5 +987,23 @@ __device__ __forceinline__ void group_body(const GRP& grp, double* y, double lam
       const double tau = ru / (sl + ru);  // = alpha at the root
       grp.store(y, [&](double S, double X) { return binf_y(S, X, tau, delta); });
     }
+  }
+}
+
+// ShiftedGroupNormL2 with CSR offsets that do not span 0:n: indices before offsets[0] / from offsets[ngroups] on keep
+// the caller's y minus the shift (src/shiftedGroupNormL2.jl:77 runs over every index)
+template <class T>
+__global__ __launch_bounds__(256) void k_csr_uncovered(T* y, const T* xk, const T* sj, const int64_t* __restrict__ offsets,
+                                                        int64_t ngroups, int64_t n) {
+  int64_t head = offsets[0], tail0 = offsets[ngroups];
+  if (head < 0) head = 0;
+  if (head > n) head = n;
+  if (tail0 < head) tail0 = head;
+  if (tail0 > n) tail0 = n;
+  const int64_t total = head + (n - tail0);
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += stride) {
+    const int64_t i = (t < head) ? t : tail0 + (t - head);
+    y[i] = y[i] - (xk[i] + sj[i]);
   }
 }

@@ -10,7 +10,7 @@
 // the second pass: a generality path, not the tuned register-tile kernels of the Float64 form (spx_group.hip).
 // ShiftedGroupNormL2Binf has NO Float32 form: its root find would run `fzero` in Float32, whose result next to the pole of
 // step(n) is rounding noise in the reference itself.
-#include "spx_common.hpp"
+#include "spx_group_common.hpp"
 
 namespace {
 
@@ -54,22 +54,6 @@ __global__ __launch_bounds__(256) void k_group_l2_f32(float* y, const float* q, 
   }
 }
 
-// indices before offsets[0] / from offsets[ngroups] on: y - (xk + sj)   (:77 runs over every index)
-__global__ __launch_bounds__(256) void k_csr_uncovered_f32(float* y, const float* xk, const float* sj,
-                                                            const int64_t* __restrict__ offsets, int64_t ngroups, int64_t n) {
-  int64_t head = offsets[0], tail0 = offsets[ngroups];
-  if (head < 0) head = 0;
-  if (head > n) head = n;
-  if (tail0 < head) tail0 = head;
-  if (tail0 > n) tail0 = n;
-  const int64_t total = head + (n - tail0);
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += stride) {
-    const int64_t i = (t < head) ? t : tail0 + (t - head);
-    y[i] = y[i] - (xk[i] + sj[i]);
-  }
-}
-
 }  // namespace
 
 SPX_EXPORT int spx_prox_group_l2_f32(spx_ctx* ctx, float* y, const float* q, const float* xk, const float* sj, int64_t n,
@@ -81,7 +65,7 @@ SPX_EXPORT int spx_prox_group_l2_f32(spx_ctx* ctx, float* y, const float* q, con
   if (n == 0) return SPX_OK;
   SPX_ON_DEVICE(ctx);
   if (group_offsets) {
-    hipLaunchKernelGGL(k_csr_uncovered_f32, dim3(256), dim3(256), 0, ctx->stream, y, xk, sj, group_offsets, ngroups, n);
+    hipLaunchKernelGGL(k_csr_uncovered<float>, dim3(256), dim3(256), 0, ctx->stream, y, xk, sj, group_offsets, ngroups, n);
     SPX_LAUNCH_CHECK();
   }
   if (ngroups == 0) return SPX_OK;

@@ -28,22 +28,6 @@ struct ObjWs {
   int pad;
 };
 
-// element terms of h
-// (float overloads: the Float32 forms.  The reference forms xsy and every term in Float32 -- which entries are exactly zero,
-//  the rounding of each square root -- and adds them up in Float32; here the terms are Float32 values, the SUM is Float64.)
-struct TermL1 {  // NormL1 [ext]
-  __device__ __forceinline__ double operator()(double v) const { return fabs(v); }
-  __device__ __forceinline__ double operator()(float v) const { return (double)fabsf(v); }
-};
-struct TermL0 {  // NormL0, IndBallL0 [ext]
-  __device__ __forceinline__ double operator()(double v) const { return (v != 0.0) ? 1.0 : 0.0; }
-  __device__ __forceinline__ double operator()(float v) const { return (v != 0.0f) ? 1.0 : 0.0; }
-};
-struct TermLhalf {  // src/rootNormLhalf.jl:27-29
-  __device__ __forceinline__ double operator()(double v) const { return sqrt(fabs(v)); }
-  __device__ __forceinline__ double operator()(float v) const { return (double)__builtin_sqrtf(fabsf(v)); }
-};
-
 __device__ __forceinline__ double block_sum(double v, double* lds4) {
   v = wave_sum(v);
   const int w = threadIdx.x >> 6;
@@ -700,28 +684,27 @@ const double kInf = std::numeric_limits<double>::infinity();
 }  // namespace
 
 // ---- generic forms: h(xk + sj + y) ---------------------------------------------------------------
-#define SPX_OBJ_PLAIN(NAME, TERM)                                                                                  \
-  SPX_EXPORT int NAME(spx_ctx* ctx, const double* y, const double* xk, const double* sj, int64_t n, double lambda, \
-                      double* value) {                                                                             \
+#define SPX_OBJ_PLAIN(NAME, T, TERM)                                                                               \
+  SPX_EXPORT int NAME(spx_ctx* ctx, const T* y, const T* xk, const T* sj, int64_t n, T lambda, double* value) {   \
     SPX_REQUIRE(value != nullptr, "value is NULL");                                                                \
-    return run_obj<double, TERM, 0>(ctx, y, xk, sj, n, nullptr, nullptr, 0.0, 0.0, nullptr, 0.0, kRuleScaled, lambda, 0.0, value); \
+    return run_obj<T, TERM, 0>(ctx, y, xk, sj, n, nullptr, nullptr, (T)0, (T)0, nullptr, 0.0, kRuleScaled,         \
+                               (double)lambda, 0.0, value);                                                        \
   }
-SPX_OBJ_PLAIN(spx_obj_l1, TermL1)
-SPX_OBJ_PLAIN(spx_obj_l0, TermL0)
-SPX_OBJ_PLAIN(spx_obj_lhalf, TermLhalf)
+SPX_OBJ_PLAIN(spx_obj_l1, double, TermL1)
+SPX_OBJ_PLAIN(spx_obj_l0, double, TermL0)
+SPX_OBJ_PLAIN(spx_obj_lhalf, double, TermLhalf)
 
 // ---- Box forms -----------------------------------------------------------------------------------------
-#define SPX_OBJ_BOX(NAME, TERM)                                                                                    \
-  SPX_EXPORT int NAME(spx_ctx* ctx, const double* y, const double* xk, const double* sj, int64_t n, double lambda, \
-                      const double* l_vec, const double* u_vec, double l_scalar, double u_scalar,                  \
-                      const uint8_t* sel_mask, double* value) {                                                    \
+#define SPX_OBJ_BOX(NAME, T, TERM)                                                                                 \
+  SPX_EXPORT int NAME(spx_ctx* ctx, const T* y, const T* xk, const T* sj, int64_t n, T lambda, const T* l_vec,    \
+                      const T* u_vec, T l_scalar, T u_scalar, const uint8_t* sel_mask, double* value) {            \
     SPX_REQUIRE(value != nullptr, "value is NULL");                                                                \
-    return run_obj<double, TERM, 1>(ctx, y, xk, sj, n, l_vec, u_vec, l_scalar, u_scalar, sel_mask, 0.0, kRuleBox, lambda, 0.0,    \
-                            value);                                                                                \
+    return run_obj<T, TERM, 1>(ctx, y, xk, sj, n, l_vec, u_vec, l_scalar, u_scalar, sel_mask, 0.0, kRuleBox,       \
+                               (double)lambda, 0.0, value);                                                        \
   }
-SPX_OBJ_BOX(spx_obj_l1_box, TermL1)
-SPX_OBJ_BOX(spx_obj_l0_box, TermL0)
-SPX_OBJ_BOX(spx_obj_lhalf_box, TermLhalf)
+SPX_OBJ_BOX(spx_obj_l1_box, double, TermL1)
+SPX_OBJ_BOX(spx_obj_l0_box, double, TermL0)
+SPX_OBJ_BOX(spx_obj_lhalf_box, double, TermLhalf)
 
 // ---- IndBallL0: 0 if at most r nonzeros, else +Inf  [ext: ProximalOperators.IndBallL0] ---------------------
 SPX_EXPORT int spx_obj_indball_l0(spx_ctx* ctx, const double* y, const double* xk, const double* sj, int64_t n,
@@ -767,27 +750,12 @@ SPX_EXPORT int spx_obj_group_l2_binf_gather(spx_ctx* ctx, const double* y, const
 // test/runtests.jl:196-209, 268-282, 346-360, 397-412, 524-550).  Element arithmetic in Float32 as in the reference
 // ((xk + sj) + y, sj + y, the box ends -+ sqrt(eps(Float32)), each sqrt), `1.1 * Delta` and the comparison against it in
 // Float64 (Julia promotes the literal), sums in Float64; the value comes back as a double (round it to Float32 to compare).
-#define SPX_OBJ_PLAIN_F32(NAME, TERM)                                                                              \
-  SPX_EXPORT int NAME(spx_ctx* ctx, const float* y, const float* xk, const float* sj, int64_t n, float lambda,     \
-                      double* value) {                                                                             \
-    SPX_REQUIRE(value != nullptr, "value is NULL");                                                                \
-    return run_obj<float, TERM, 0>(ctx, y, xk, sj, n, nullptr, nullptr, 0.0f, 0.0f, nullptr, 0.0, kRuleScaled,     \
-                                   (double)lambda, 0.0, value);                                                    \
-  }
-SPX_OBJ_PLAIN_F32(spx_obj_l1_f32, TermL1)
-SPX_OBJ_PLAIN_F32(spx_obj_l0_f32, TermL0)
-SPX_OBJ_PLAIN_F32(spx_obj_lhalf_f32, TermLhalf)
-#define SPX_OBJ_BOX_F32(NAME, TERM)                                                                                \
-  SPX_EXPORT int NAME(spx_ctx* ctx, const float* y, const float* xk, const float* sj, int64_t n, float lambda,     \
-                      const float* l_vec, const float* u_vec, float l_scalar, float u_scalar,                      \
-                      const uint8_t* sel_mask, double* value) {                                                    \
-    SPX_REQUIRE(value != nullptr, "value is NULL");                                                                \
-    return run_obj<float, TERM, 1>(ctx, y, xk, sj, n, l_vec, u_vec, l_scalar, u_scalar, sel_mask, 0.0, kRuleBox,   \
-                                   (double)lambda, 0.0, value);                                                    \
-  }
-SPX_OBJ_BOX_F32(spx_obj_l1_box_f32, TermL1)
-SPX_OBJ_BOX_F32(spx_obj_l0_box_f32, TermL0)
-SPX_OBJ_BOX_F32(spx_obj_lhalf_box_f32, TermLhalf)
+SPX_OBJ_PLAIN(spx_obj_l1_f32, float, TermL1)
+SPX_OBJ_PLAIN(spx_obj_l0_f32, float, TermL0)
+SPX_OBJ_PLAIN(spx_obj_lhalf_f32, float, TermLhalf)
+SPX_OBJ_BOX(spx_obj_l1_box_f32, float, TermL1)
+SPX_OBJ_BOX(spx_obj_l0_box_f32, float, TermL0)
+SPX_OBJ_BOX(spx_obj_lhalf_box_f32, float, TermLhalf)
 SPX_EXPORT int spx_obj_indball_l0_f32(spx_ctx* ctx, const float* y, const float* xk, const float* sj, int64_t n, int64_t r,
                                       double* value) {
   SPX_REQUIRE(value != nullptr, "value is NULL");

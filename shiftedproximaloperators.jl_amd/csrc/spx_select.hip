@@ -2381,70 +2381,60 @@ __global__ __launch_bounds__(1024) void k_s2_front(const double* q, const double
 #define SPX_SEL_REG_MAX_LOG2 21  // largest n (log2) on the register-resident one-launch select = what 256 CUs hold at 8 elements per lane (n = 2e6: 37 us vs 57 us for the sample-predicted pipeline; beyond it the one-launch form parks v in y and is no faster: tools/r2/topr_midn.py)
 #endif
 
-template <bool BINF>
-int run_select(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n, int64_t r,
-               double delta) {
-  int rc = spx_check_common(ctx, y, q, xk, sj, n);
-  if (rc) return rc;
-  if (n == 0) return SPX_OK;
-  SPX_ON_DEVICE(ctx);
-  // one workgroup, one launch, no scratch -- up to 8192 elements (n = 16 384: 32 us in one workgroup, 21 us on two;
-  // n = 65 536: 84 vs 19 us -- tools/r2/topr_small.py)
-  if (n <= kSmallNCoop && ctx->tune_sel_small) {
-    hipLaunchKernelGGL((k_sel_small<BINF>), dim3(1), dim3(1024), 0, ctx->stream, y, q, xk, sj, n, r, delta);
-    SPX_LAUNCH_CHECK();
-    return SPX_OK;
-  }
-  const int vec = (spx_aligned16(y) && spx_aligned16(q) && spx_aligned16(xk) && spx_aligned16(sj)) ? 1 : 0;
-  // all four vectors 8 bytes off a 16-byte boundary (a view that starts at an odd element): the sample-predicted path
-  // runs on the aligned rest and its wave 0 takes element 0 along (ioff = 1)
-  auto off8 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 8u; };
-  const int ioff = (!vec && off8(y) && off8(q) && off8(xk) && off8(sj)) ? 1 : 0;
-  // Residency of the kernels that synchronise inside one launch: a grid never exceeds what the occupancy query says can be
-  // resident at once (spx_resident_cap); a form whose grid does not fit hands over to the one that works with any grid.
-  const int64_t cap_reg = spx_resident_cap(ctx, reinterpret_cast<const void*>(&k_sel_coop<BINF, true>), 1024, 0);
-  const int64_t cap_mem = spx_resident_cap(ctx, reinterpret_cast<const void*>(&k_sel_coop<BINF, false>), 1024, 0);
-  if (cap_mem < 1) return SPX_ERR_INTERNAL;  // (message set by spx_resident_cap)
-  // samples per lane of the front kernel: 1 / 2 / 4 by n (see k_s2_front); 16 for a cut in the bulk of a large vector -- the band
-  // is +-6 sigma of the SAMPLE rank, sigma^2 = M p (1 - p): its share of the vector shrinks with sqrt(M), and at r = n/2 the band
-  // of the 4-sample form holds 1.2 % of the vector as candidates (main pass +40 us, compaction +20 us; tuning key 10 overrides)
-  const double pcut = (double)r / (double)n;
-  int spl = n >= ((int64_t)1 << 25) ? 4 : (n >= ((int64_t)1 << 23) ? 2 : 1);
-  if (n >= ((int64_t)1 << 26) && pcut * (1.0 - pcut) > 0.04) spl = 16;
-  if (ctx->tune_front_spl == 1 || ctx->tune_front_spl == 2 || ctx->tune_front_spl == 4 || ctx->tune_front_spl == 16) spl = ctx->tune_front_spl;
-  const void* front_fn = spl == 16 ? reinterpret_cast<const void*>(&k_s2_front<16>)
-                       : spl == 4 ? reinterpret_cast<const void*>(&k_s2_front<4>)
-                       : spl == 2 ? reinterpret_cast<const void*>(&k_s2_front<2>)
-                                  : reinterpret_cast<const void*>(&k_s2_front<1>);
-  const int64_t cap_front = spx_resident_cap(ctx, front_fn, 1024, 0);
-  const int64_t reg_cap = (int64_t)kCoopEpl * 1024 * (cap_reg < ctx->num_cu ? cap_reg : ctx->num_cu);  // (2 Mi elements on 256 CUs)
-  // ... and 4 Mi with v parked in LDS (k_sel_lds): the sample-predicted pipeline (six launches, ~50 us of them fixed cost) takes
-  // over above what the resident grid holds on chip.  y must not overlap the inputs elsewhere than element for element (a lane
-  // reads all its inputs before it writes: aliasing q, xk or sj exactly is fine, as in the other one-launch forms).
-  int64_t lds_cap = 0;
-  if (ctx->tune_sel_reg16) {
-    const int64_t capl = vec ? spx_resident_cap(ctx, reinterpret_cast<const void*>(&k_sel_lds<BINF, true>), 1024, 0)
-                             : spx_resident_cap(ctx, reinterpret_cast<const void*>(&k_sel_lds<BINF, false>), 1024, 0);
-    lds_cap = (int64_t)kLdsEpl * 1024 * (capl < ctx->num_cu ? capl : ctx->num_cu);
-  }
-  // ... and 6 Mi with 8 more elements per lane in registers (k_sel_lds<.., REGX>: 16-byte aligned vectors only; tuning key 11 = 2
-  // keeps the pipeline from 4 Mi on)
-  int64_t hyb_cap = 0;
-  if (ctx->tune_sel_reg16 == 1 && vec && lds_cap > 0) {
-    const int64_t caph = spx_resident_cap(ctx, reinterpret_cast<const void*>(&k_sel_lds<BINF, true, double, kLdsRegX>), 1024, 0);
-    hyb_cap = (int64_t)(kLdsEpl + kLdsRegX) * 1024 * (caph < ctx->num_cu ? caph : ctx->num_cu);
-    if (hyb_cap > 0x7fffffff) hyb_cap = 0;  // (the form indexes with 32-bit integers)
-  }
-  int64_t fast_min = ((int64_t)1 << SPX_SEL_REG_MAX_LOG2) + 1;
-  if (lds_cap >= fast_min) fast_min = lds_cap + 1;
-  if (hyb_cap >= fast_min) fast_min = hyb_cap + 1;
-  const bool try_fast = ctx->tune_sel_fast && (vec || ioff) && (n - ioff) >= fast_min && r > 0 && r < n &&
-                        cap_front >= kFrontBlocks;  // (the front kernel's sample layout is tied to its grid)
-  rc = spx_sync_reserve(ctx, sizeof(SelSync));
+// The exact select in ONE launch, for both precisions: k_sel_coop (v in registers: kCoopReg; v parked in y: kCoopMem) or
+// k_sel_lds (v parked in LDS; kLdsRegX: and 8 more elements per lane in registers, Float64 and 16-byte aligned vectors only)
+// on the grid the caller's precision chose (run_select), with the histogram-set / parity state around it.
+enum class SelForm { kCoopReg, kCoopMem, kLds, kLdsRegX };
+template <bool BINF, class T>
+int launch_sel_exact(spx_ctx* ctx, SelForm form, bool vec, int64_t g, T* y, const T* q, const T* xk, const T* sj, int64_t n,
+                     int64_t r, T delta) {
+  int rc = spx_sync_reserve(ctx, sizeof(SelSync));
   if (rc) return rc;
   SelSync* ss = reinterpret_cast<SelSync*>(ctx->sync);
   const bool graph_safe = spx_capture_check(ctx) || ctx->graph_safe;  // (see spx_ctx::graph_safe)
-  const int64_t g_mem = cap_mem < ctx->num_cu ? cap_mem : ctx->num_cu;  // grid of the form that parks v in y: any size >= 1 works
+  int use_set = ctx->sel_hist_next, other = use_set ^ 1;
+  int clear_set = ctx->sel_hist_dirty[other] ? other : -1;
+  int parity = ctx->coop_parity;
+  if (graph_safe) {  // the counters and histogram set 0, zeroed by a node in front of the launch; nothing alternates
+    rc = spx_zero_async(ctx, &ss->hdr, sizeof(ss->hdr.bar));
+    if (rc) return rc;
+    rc = spx_zero_async(ctx, &ss->chist[0][0][0], sizeof(ss->chist[0]));
+    if (rc) return rc;
+    use_set = 0; other = 1; clear_set = -1; parity = 0;
+  }
+  void (*kernel)(T*, const T*, const T*, const T*, int64_t, int64_t, T, SelSync*, int, int, int) =
+      form == SelForm::kCoopReg ? k_sel_coop<BINF, true, T>
+      : form == SelForm::kCoopMem ? k_sel_coop<BINF, false, T>
+      : vec ? k_sel_lds<BINF, true, T> : k_sel_lds<BINF, false, T>;
+  if constexpr (std::is_same<T, double>::value) {
+    if (form == SelForm::kLdsRegX) kernel = k_sel_lds<BINF, true, double, kLdsRegX>;
+  }
+  {
+    SpxCoopLaunchGuard guard(ctx);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)g), dim3(1024), 0, ctx->stream, y, q, xk, sj, n, r, delta, ss, parity, use_set,
+                       clear_set);
+  }
+  if (graph_safe) {  // whatever the host believed about the sets no longer holds: both count as used
+    ctx->sel_hist_dirty[0] = ctx->sel_hist_dirty[1] = 1;
+  } else {
+    ctx->coop_parity ^= 1;
+    ctx->sel_hist_dirty[use_set] = 1;
+    ctx->sel_hist_dirty[other] = 0;
+    ctx->sel_hist_next = other;
+  }
+  SPX_LAUNCH_CHECK();
+  return SPX_OK;
+}
+
+// Float64 above the one-launch forms: the sample-predicted single streaming pass (front -> main -> verdict / candidates),
+// with the exact select queued behind it as the fallback (k_s2_tail)
+template <bool BINF>
+int run_select_fast(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n, int64_t r,
+                    double delta, int ioff, int spl) {
+  int rc = spx_sync_reserve(ctx, sizeof(SelSync));
+  if (rc) return rc;
+  SelSync* ss = reinterpret_cast<SelSync*>(ctx->sync);
+  const bool graph_safe = spx_capture_check(ctx) || ctx->graph_safe;  // (see spx_ctx::graph_safe)
   const int64_t cap_tail = spx_resident_cap(ctx, reinterpret_cast<const void*>(&k_s2_tail<BINF>), 1024, 0);
   if (cap_tail < 1) return SPX_ERR_INTERNAL;
   const int64_t g_tail = cap_tail < 256 ? (cap_tail < ctx->num_cu ? cap_tail : ctx->num_cu) : (ctx->num_cu < 256 ? ctx->num_cu : 256);  // (<= 256: SelSync::tie_part)
@@ -2452,70 +2442,6 @@ int run_select(spx_ctx* ctx, double* y, const double* q, const double* xk, const
 #ifdef SPX_TEST_HOOKS  // the planted fault of tests/test_gpu_robustness.py (key 101): the last workgroup of the tail kernel leaves
   tail_hook = ctx->tune_force_tail > 0 ? 2 : 0;  // without arriving anywhere, as if it had never been placed -- the others give up waiting
 #endif
-  if (!try_fast) {
-    // exact select in ONE launch: register-resident up to 8 Ki elements per resident workgroup, v parked in y beyond that
-    // k_sel_lds from 1 Mi elements on (n = 2e6: 34 / 42 us at r = n/100 / n/2 against 39 / 45 with v in registers; n = 1e6:
-    // 36 / 30 against 35 / 29 -- tools/r3/topr_small_grid.py), and wherever the register form's grid does not fit
-    const bool lds = n <= lds_cap && (n > kLdsMinN || n > reg_cap);
-    const bool hyb = !lds && n > lds_cap && n <= hyb_cap;  // (vec: hyb_cap is 0 otherwise)
-    const bool reg = !lds && !hyb && n <= reg_cap;
-    // Register form: 1 / 2 / 4 / 8 elements per lane by n -- the fewer elements a lane walks per pass the better, until the
-    // workgroups are so many that their histogram flushes and arrivals cost more (us per call at r = n/100, 1 / 2 / 4 / 8 per
-    // lane: n = 3e4 17.4 / 18.4 / 20.7 / 24.1; n = 1e5 19.8 / 19.3 / 20.8 / 24.4; n = 3e5 26.8 / 22.8 / 22.1 / 24.9; n = 1e6
-    // 35.6 / 35.7 / 36.6 / 34.7 -- tools/r3/topr_small_grid.py)
-    const int64_t epl = n <= 65536 ? 1 : n <= 196608 ? 2 : n <= 655360 ? 4 : kCoopEpl;
-    int64_t g = g_mem;
-    if (reg) {
-      const int64_t gmax = cap_reg < ctx->num_cu ? cap_reg : ctx->num_cu;
-      g = (n + epl * 1024 - 1) / (epl * 1024);
-      if (g > gmax) g = gmax;  // (n <= reg_cap: 8 elements per lane always fit)
-    }
-    // (k_sel_lds: every CU the grid may have -- the load phase is most of the kernel and wants all of them pulling; a rendezvous
-    //  costs 1.4 us with 256 workgroups since the arrivals are spread over eight counters)
-    if (lds) g = lds_cap / ((int64_t)kLdsEpl * 1024);
-    if (hyb) g = hyb_cap / ((int64_t)(kLdsEpl + kLdsRegX) * 1024);
-#ifdef SPX_TEST_HOOKS  // the planted fault of tests/test_gpu_robustness.py: a grid that cannot be resident
-    if (!reg && !lds && !hyb && ctx->tune_force_grid > 0) g = ctx->tune_force_grid;
-#endif
-    int use_set = ctx->sel_hist_next, other = use_set ^ 1;
-    int clear_set = ctx->sel_hist_dirty[other] ? other : -1;
-    int parity = ctx->coop_parity;
-    if (graph_safe) {  // the counters and histogram set 0, zeroed by a node in front of the launch; nothing alternates
-      rc = spx_zero_async(ctx, &ss->hdr, sizeof(ss->hdr.bar));
-      if (rc) return rc;
-      rc = spx_zero_async(ctx, &ss->chist[0][0][0], sizeof(ss->chist[0]));
-      if (rc) return rc;
-      use_set = 0; other = 1; clear_set = -1; parity = 0;
-    }
-    {
-      SpxCoopLaunchGuard guard(ctx);
-      if (reg)
-        hipLaunchKernelGGL((k_sel_coop<BINF, true>), dim3((unsigned)g), dim3(1024), 0, ctx->stream, y, q, xk, sj, n, r,
-                           delta, ss, parity, use_set, clear_set);
-      else if (lds && vec)
-        hipLaunchKernelGGL((k_sel_lds<BINF, true>), dim3((unsigned)g), dim3(1024), 0, ctx->stream, y, q, xk, sj, n, r, delta, ss,
-                           parity, use_set, clear_set);
-      else if (lds)
-        hipLaunchKernelGGL((k_sel_lds<BINF, false>), dim3((unsigned)g), dim3(1024), 0, ctx->stream, y, q, xk, sj, n, r, delta, ss,
-                           parity, use_set, clear_set);
-      else if (hyb)
-        hipLaunchKernelGGL((k_sel_lds<BINF, true, double, kLdsRegX>), dim3((unsigned)g), dim3(1024), 0, ctx->stream, y, q, xk, sj,
-                           n, r, delta, ss, parity, use_set, clear_set);
-      else
-        hipLaunchKernelGGL((k_sel_coop<BINF, false>), dim3((unsigned)g), dim3(1024), 0, ctx->stream, y, q, xk, sj, n, r,
-                           delta, ss, parity, use_set, clear_set);
-    }
-    if (graph_safe) {  // whatever the host believed about the sets no longer holds: both count as used
-      ctx->sel_hist_dirty[0] = ctx->sel_hist_dirty[1] = 1;
-    } else {
-      ctx->coop_parity ^= 1;
-      ctx->sel_hist_dirty[use_set] = 1;
-      ctx->sel_hist_dirty[other] = 0;
-      ctx->sel_hist_next = other;
-    }
-    SPX_LAUNCH_CHECK();
-    return SPX_OK;
-  }
   // fast path scratch: one candidate region + count word per wavefront of the main pass
   const int64_t n2 = (n - ioff) >> 1;
   const int64_t mblocks = (n2 + kMainTilePairs - 1) / kMainTilePairs;
@@ -2603,90 +2529,121 @@ int run_select(spx_ctx* ctx, double* y, const double* q, const double* xk, const
   return SPX_OK;
 }
 
-// Float32 vectors (round 3): the exact select in one launch, on the same kernels -- one workgroup up to 8192 elements,
-// register-resident up to 8 Ki elements per resident workgroup, v parked in y beyond.  (The sample-predicted single pass is
-// Float64 only: ~44 B/element here instead of 16, 0.7 ms at n = 1e8.)  Bit-exact: v = (xk + sj) + q, the comparisons and the
-// final subtraction are Float32 operations, as in the reference with R = Float32.
-template <bool BINF>
-int run_select_f32(spx_ctx* ctx, float* y, const float* q, const float* xk, const float* sj, int64_t n, int64_t r, float delta) {
+template <bool BINF, class T>
+int run_select(spx_ctx* ctx, T* y, const T* q, const T* xk, const T* sj, int64_t n, int64_t r, T delta) {
   int rc = spx_check_common(ctx, y, q, xk, sj, n);
   if (rc) return rc;
   if (n == 0) return SPX_OK;
   SPX_ON_DEVICE(ctx);
+  // one workgroup, one launch, no scratch -- up to 8192 elements (n = 16 384: 32 us in one workgroup, 21 us on two;
+  // n = 65 536: 84 vs 19 us -- tools/r2/topr_small.py)
   if (n <= kSmallNCoop && ctx->tune_sel_small) {
-    hipLaunchKernelGGL((k_sel_small<BINF, float>), dim3(1), dim3(1024), 0, ctx->stream, y, q, xk, sj, n, r, delta);
+    hipLaunchKernelGGL((k_sel_small<BINF, T>), dim3(1), dim3(1024), 0, ctx->stream, y, q, xk, sj, n, r, delta);
     SPX_LAUNCH_CHECK();
     return SPX_OK;
   }
-  const int64_t cap_reg = spx_resident_cap(ctx, reinterpret_cast<const void*>(&k_sel_coop<BINF, true, float>), 1024, 0);
-  const int64_t cap_mem = spx_resident_cap(ctx, reinterpret_cast<const void*>(&k_sel_coop<BINF, false, float>), 1024, 0);
-  if (cap_mem < 1) return SPX_ERR_INTERNAL;
-  rc = spx_sync_reserve(ctx, sizeof(SelSync));
-  if (rc) return rc;
-  SelSync* ss = reinterpret_cast<SelSync*>(ctx->sync);
-  const bool graph_safe = spx_capture_check(ctx) || ctx->graph_safe;
-  const int64_t reg_cap = (int64_t)kCoopEpl * 1024 * (cap_reg < ctx->num_cu ? cap_reg : ctx->num_cu);
-  // v parked in LDS (k_sel_lds<.., float>: 32 Ki elements per resident workgroup, 8 Mi on 256 CUs) above what the register form
-  // holds (2 Mi; below, registers win: n = 2e6 39 / 41 us against 43 / 45 -- the Float32 first digit is not folded and the LDS
-  // form's third pass costs more); beyond what the grid holds: the form that parks v in y (n = 8e6: 97 -> 64 us,
-  // tools/r3/topr_f32_midn.py)
   const bool vec = spx_aligned16(y) && spx_aligned16(q) && spx_aligned16(xk) && spx_aligned16(sj);
+  // Residency of the kernels that synchronise inside one launch: a grid never exceeds what the occupancy query says can be
+  // resident at once (spx_resident_cap); a form whose grid does not fit hands over to the one that works with any grid.
+  const int64_t cap_reg = spx_resident_cap(ctx, reinterpret_cast<const void*>(&k_sel_coop<BINF, true, T>), 1024, 0);
+  const int64_t cap_mem = spx_resident_cap(ctx, reinterpret_cast<const void*>(&k_sel_coop<BINF, false, T>), 1024, 0);
+  if (cap_mem < 1) return SPX_ERR_INTERNAL;  // (message set by spx_resident_cap)
+  const int64_t reg_cap = (int64_t)kCoopEpl * 1024 * (cap_reg < ctx->num_cu ? cap_reg : ctx->num_cu);  // (2 Mi elements on 256 CUs)
+  // ... and with v parked in LDS (k_sel_lds: 16 Ki Float64 / 32 Ki Float32 elements per resident workgroup, 4 Mi / 8 Mi on 256
+  // CUs).  y must not overlap the inputs elsewhere than element for element (a lane reads all its inputs before it writes:
+  // aliasing q, xk or sj exactly is fine, as in the other one-launch forms).
+  constexpr int kLdsSlots = std::is_same<T, double>::value ? kLdsEpl : kLdsEpl32;
   int64_t lds_cap = 0;
   if (ctx->tune_sel_reg16) {
-    const int64_t capl = vec ? spx_resident_cap(ctx, reinterpret_cast<const void*>(&k_sel_lds<BINF, true, float>), 1024, 0)
-                             : spx_resident_cap(ctx, reinterpret_cast<const void*>(&k_sel_lds<BINF, false, float>), 1024, 0);
-    lds_cap = (int64_t)kLdsEpl32 * 1024 * (capl < ctx->num_cu ? capl : ctx->num_cu);
+    const int64_t capl = vec ? spx_resident_cap(ctx, reinterpret_cast<const void*>(&k_sel_lds<BINF, true, T>), 1024, 0)
+                             : spx_resident_cap(ctx, reinterpret_cast<const void*>(&k_sel_lds<BINF, false, T>), 1024, 0);
+    lds_cap = (int64_t)kLdsSlots * 1024 * (capl < ctx->num_cu ? capl : ctx->num_cu);
   }
-  const bool lds = n <= lds_cap && n > reg_cap;
-  const bool reg = !lds && n <= reg_cap;
-  int64_t g = reg ? (n + (int64_t)kCoopEpl * 1024 - 1) / ((int64_t)kCoopEpl * 1024) : (cap_mem < ctx->num_cu ? cap_mem : ctx->num_cu);
-  if (lds) g = lds_cap / ((int64_t)kLdsEpl32 * 1024);
-  int use_set = ctx->sel_hist_next, other = use_set ^ 1;
-  int clear_set = ctx->sel_hist_dirty[other] ? other : -1;
-  int parity = ctx->coop_parity;
-  if (graph_safe) {
-    rc = spx_zero_async(ctx, &ss->hdr, sizeof(ss->hdr.bar));
-    if (rc) return rc;
-    rc = spx_zero_async(ctx, &ss->chist[0][0][0], sizeof(ss->chist[0]));
-    if (rc) return rc;
-    use_set = 0; other = 1; clear_set = -1; parity = 0;
-  }
-  {
-    SpxCoopLaunchGuard guard(ctx);
-    if (reg)
-      hipLaunchKernelGGL((k_sel_coop<BINF, true, float>), dim3((unsigned)g), dim3(1024), 0, ctx->stream, y, q, xk, sj, n, r, delta, ss,
-                         parity, use_set, clear_set);
-    else if (lds && vec)
-      hipLaunchKernelGGL((k_sel_lds<BINF, true, float>), dim3((unsigned)g), dim3(1024), 0, ctx->stream, y, q, xk, sj, n, r, delta, ss,
-                         parity, use_set, clear_set);
-    else if (lds)
-      hipLaunchKernelGGL((k_sel_lds<BINF, false, float>), dim3((unsigned)g), dim3(1024), 0, ctx->stream, y, q, xk, sj, n, r, delta, ss,
-                         parity, use_set, clear_set);
-    else
-      hipLaunchKernelGGL((k_sel_coop<BINF, false, float>), dim3((unsigned)g), dim3(1024), 0, ctx->stream, y, q, xk, sj, n, r, delta, ss,
-                         parity, use_set, clear_set);
-  }
-  if (graph_safe) {
-    ctx->sel_hist_dirty[0] = ctx->sel_hist_dirty[1] = 1;
+  const int64_t g_mem = cap_mem < ctx->num_cu ? cap_mem : ctx->num_cu;  // grid of the form that parks v in y: any size >= 1 works
+  // (k_sel_lds: every CU the grid may have -- the load phase is most of the kernel and wants all of them pulling; a rendezvous
+  //  costs 1.4 us with 256 workgroups since the arrivals are spread over eight counters)
+  const int64_t g_lds = lds_cap / ((int64_t)kLdsSlots * 1024);
+  SelForm form;
+  int64_t g;
+  if constexpr (std::is_same<T, float>::value) {
+    // Float32: k_sel_lds above what the register form holds (2 Mi; below, registers win: n = 2e6 39 / 41 us against 43 / 45 --
+    // the Float32 first digit is not folded and the LDS form's third pass costs more), 8 elements per lane in registers;
+    // beyond what the grid holds: the form that parks v in y (n = 8e6: 97 -> 64 us, tools/r3/topr_f32_midn.py).  The
+    // sample-predicted single pass is Float64 only (~44 B/element here instead of 16, 0.7 ms at n = 1e8).
+    const bool lds = n <= lds_cap && n > reg_cap;
+    const bool reg = !lds && n <= reg_cap;
+    form = lds ? SelForm::kLds : reg ? SelForm::kCoopReg : SelForm::kCoopMem;
+    g = lds ? g_lds : reg ? (n + (int64_t)kCoopEpl * 1024 - 1) / ((int64_t)kCoopEpl * 1024) : g_mem;
   } else {
-    ctx->coop_parity ^= 1;
-    ctx->sel_hist_dirty[use_set] = 1;
-    ctx->sel_hist_dirty[other] = 0;
-    ctx->sel_hist_next = other;
+    // Float64: the sample-predicted pipeline above what the one-launch forms hold, k_sel_lds from 1 Mi elements on, the
+    // hybrid LDS + register form up to 6 Mi, elements per lane graded by n on the register form.
+    // all four vectors 8 bytes off a 16-byte boundary (a view that starts at an odd element): the sample-predicted path
+    // runs on the aligned rest and its wave 0 takes element 0 along (ioff = 1)
+    auto off8 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 8u; };
+    const int ioff = (!vec && off8(y) && off8(q) && off8(xk) && off8(sj)) ? 1 : 0;
+    // samples per lane of the front kernel: 1 / 2 / 4 by n (see k_s2_front); 16 for a cut in the bulk of a large vector -- the band
+    // is +-6 sigma of the SAMPLE rank, sigma^2 = M p (1 - p): its share of the vector shrinks with sqrt(M), and at r = n/2 the band
+    // of the 4-sample form holds 1.2 % of the vector as candidates (main pass +40 us, compaction +20 us; tuning key 10 overrides)
+    const double pcut = (double)r / (double)n;
+    int spl = n >= ((int64_t)1 << 25) ? 4 : (n >= ((int64_t)1 << 23) ? 2 : 1);
+    if (n >= ((int64_t)1 << 26) && pcut * (1.0 - pcut) > 0.04) spl = 16;
+    if (ctx->tune_front_spl == 1 || ctx->tune_front_spl == 2 || ctx->tune_front_spl == 4 || ctx->tune_front_spl == 16) spl = ctx->tune_front_spl;
+    const void* front_fn = spl == 16 ? reinterpret_cast<const void*>(&k_s2_front<16>)
+                         : spl == 4 ? reinterpret_cast<const void*>(&k_s2_front<4>)
+                         : spl == 2 ? reinterpret_cast<const void*>(&k_s2_front<2>)
+                                    : reinterpret_cast<const void*>(&k_s2_front<1>);
+    const int64_t cap_front = spx_resident_cap(ctx, front_fn, 1024, 0);
+    // ... and 6 Mi with 8 more elements per lane in registers (k_sel_lds<.., REGX>: 16-byte aligned vectors only; tuning key 11 = 2
+    // keeps the pipeline from 4 Mi on).  The sample-predicted pipeline (six launches, ~50 us of them fixed cost) takes over above
+    // what the resident grid holds on chip.
+    int64_t hyb_cap = 0;
+    if (ctx->tune_sel_reg16 == 1 && vec && lds_cap > 0) {
+      const int64_t caph = spx_resident_cap(ctx, reinterpret_cast<const void*>(&k_sel_lds<BINF, true, double, kLdsRegX>), 1024, 0);
+      hyb_cap = (int64_t)(kLdsEpl + kLdsRegX) * 1024 * (caph < ctx->num_cu ? caph : ctx->num_cu);
+      if (hyb_cap > 0x7fffffff) hyb_cap = 0;  // (the form indexes with 32-bit integers)
+    }
+    int64_t fast_min = ((int64_t)1 << SPX_SEL_REG_MAX_LOG2) + 1;
+    if (lds_cap >= fast_min) fast_min = lds_cap + 1;
+    if (hyb_cap >= fast_min) fast_min = hyb_cap + 1;
+    const bool try_fast = ctx->tune_sel_fast && (vec || ioff) && (n - ioff) >= fast_min && r > 0 && r < n &&
+                          cap_front >= kFrontBlocks;  // (the front kernel's sample layout is tied to its grid)
+    if (try_fast) return run_select_fast<BINF>(ctx, y, q, xk, sj, n, r, delta, ioff, spl);
+    // exact select in ONE launch: register-resident up to 8 Ki elements per resident workgroup, v parked in y beyond that
+    // k_sel_lds from 1 Mi elements on (n = 2e6: 34 / 42 us at r = n/100 / n/2 against 39 / 45 with v in registers; n = 1e6:
+    // 36 / 30 against 35 / 29 -- tools/r3/topr_small_grid.py), and wherever the register form's grid does not fit
+    const bool lds = n <= lds_cap && (n > kLdsMinN || n > reg_cap);
+    const bool hyb = !lds && n > lds_cap && n <= hyb_cap;  // (vec: hyb_cap is 0 otherwise)
+    const bool reg = !lds && !hyb && n <= reg_cap;
+    // Register form: 1 / 2 / 4 / 8 elements per lane by n -- the fewer elements a lane walks per pass the better, until the
+    // workgroups are so many that their histogram flushes and arrivals cost more (us per call at r = n/100, 1 / 2 / 4 / 8 per
+    // lane: n = 3e4 17.4 / 18.4 / 20.7 / 24.1; n = 1e5 19.8 / 19.3 / 20.8 / 24.4; n = 3e5 26.8 / 22.8 / 22.1 / 24.9; n = 1e6
+    // 35.6 / 35.7 / 36.6 / 34.7 -- tools/r3/topr_small_grid.py)
+    const int64_t epl = n <= 65536 ? 1 : n <= 196608 ? 2 : n <= 655360 ? 4 : kCoopEpl;
+    form = lds ? SelForm::kLds : hyb ? SelForm::kLdsRegX : reg ? SelForm::kCoopReg : SelForm::kCoopMem;
+    g = g_mem;
+    if (reg) {
+      const int64_t gmax = cap_reg < ctx->num_cu ? cap_reg : ctx->num_cu;
+      g = (n + epl * 1024 - 1) / (epl * 1024);
+      if (g > gmax) g = gmax;  // (n <= reg_cap: 8 elements per lane always fit)
+    }
+    if (lds) g = g_lds;
+    if (hyb) g = hyb_cap / ((int64_t)(kLdsEpl + kLdsRegX) * 1024);
+#ifdef SPX_TEST_HOOKS  // the planted fault of tests/test_gpu_robustness.py: a grid that cannot be resident
+    if (!reg && !lds && !hyb && ctx->tune_force_grid > 0) g = ctx->tune_force_grid;
+#endif
   }
-  SPX_LAUNCH_CHECK();
-  return SPX_OK;
+  return launch_sel_exact<BINF>(ctx, form, vec, g, y, q, xk, sj, n, r, delta);
 }
 
 }  // namespace
 
 SPX_EXPORT int spx_prox_indball_l0_f32(spx_ctx* ctx, float* y, const float* q, const float* xk, const float* sj, int64_t n,
                                        int64_t r) {
-  return run_select_f32<false>(ctx, y, q, xk, sj, n, r, 0.0f);
+  return run_select<false>(ctx, y, q, xk, sj, n, r, 0.0f);
 }
 SPX_EXPORT int spx_prox_indball_l0_binf_f32(spx_ctx* ctx, float* y, const float* q, const float* xk, const float* sj, int64_t n,
                                             int64_t r, float delta) {
-  return run_select_f32<true>(ctx, y, q, xk, sj, n, r, delta);
+  return run_select<true>(ctx, y, q, xk, sj, n, r, delta);
 }
 
 SPX_EXPORT int spx_prox_indball_l0(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj,

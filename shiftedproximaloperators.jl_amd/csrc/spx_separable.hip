@@ -1,5 +1,6 @@
 // spx_separable.hip -- the six separable prox! kernels (ShiftedNormL1/L0/RootNormLhalf and their Box
-// forms).  One streaming skeleton, one functor per operator.
+// forms) and iprox!, on Float64 and (L1 / L0 forms) Float32 vectors.  One streaming skeleton per precision, one functor
+// per operator.
 //
 // HBM layout: q, xk, sj, y (and l, u when they are vectors) are plain contiguous fp64 vectors.
 // Algorithmic traffic: 3 reads + 1 write = 32 B/element (48 B with vector bounds, +1 B with a mask).
@@ -17,83 +18,87 @@
 #include "spx_common.hpp"
 
 // ---------------------------------------------------------------------------------------------
-// per-element operators.  Signature: (q, x, s, l, u, selected) -> y.  Unboxed ones ignore l, u, selected.
+// per-element operators, one body per operator for both precisions (T = double: the kernels below; T = float: k_sep_f32).
+// Signature: (q, x, s, l, u, selected) -> y.  Unboxed ones ignore l, u, selected.
 // Every expression keeps the reference's association (cited); the library is built with
-// -ffp-contract=off so a*b+c never becomes an FMA.
+// -ffp-contract=off so a*b+c never becomes an FMA.  Every literal is a T: with R = Float32 the reference's Int literals
+// promote to Float32 (`2 * psi.lambda * sigma`, `0`), so the Float32 results are reproduced BIT FOR BIT in fp32 as well.
 // ---------------------------------------------------------------------------------------------
-struct OpL1 {  // src/shiftedNormL1.jl:46-51
-  double ls;   // lambda * sigma
+template <class T>
+struct ProxL1 {  // src/shiftedNormL1.jl:46-51
+  T ls;          // lambda * sigma
   static constexpr bool kBox = false;
-  static constexpr int kLdsKiB = 6;  // KiB per wave and input vector in the LDS-staged skeleton
-  static constexpr int kNIn = 3;
-  static constexpr bool kObj = false;     // input vectors besides bounds: q, xk, sj
-  __device__ __forceinline__ double operator()(double q, double x, double s, double, double, bool) const {
-    double t = (-x) - s;                          // :47  @. y = -xk - sj
+  static constexpr int kNIn = 3;  // input vectors besides bounds: q, xk, sj
+  __device__ __forceinline__ T operator()(T q, T x, T s, T, T, bool) const {
+    T t = (-x) - s;                               // :47  @. y = -xk - sj
     return jl_min(jl_max(t, q - ls), q + ls);     // :50
   }
 };
-struct OpL1Aliased {  // y === q in the reference: the broadcast at :47 overwrites q before :50 reads it
+template <class T>
+struct ProxL1Aliased {  // y === q in the reference: the broadcast at :47 overwrites q before :50 reads it
   static constexpr bool kBox = false;
-  static constexpr int kLdsKiB = 6;  // KiB per wave and input vector in the LDS-staged skeleton
   static constexpr int kNIn = 3;
-  static constexpr bool kObj = false;     // input vectors besides bounds: q, xk, sj
-  __device__ __forceinline__ double operator()(double, double x, double s, double, double, bool) const {
+  __device__ __forceinline__ T operator()(T, T x, T s, T, T, bool) const {
     return (-x) - s;  // min(max(t, t - ls), t + ls) == t bit for bit whenever ls >= 0
   }
 };
-struct OpL0 {  // src/shiftedNormL0.jl:45-52
-  double c;    // sqrt(2 * lambda * sigma)
+template <class T>
+struct ProxL0 {  // src/shiftedNormL0.jl:45-52
+  T c;           // sqrt(2 * lambda * sigma)
   static constexpr bool kBox = false;
-  static constexpr int kLdsKiB = 6;  // KiB per wave and input vector in the LDS-staged skeleton
   static constexpr int kNIn = 3;
-  static constexpr bool kObj = false;     // input vectors besides bounds: q, xk, sj
-  __device__ __forceinline__ double operator()(double q, double x, double s, double, double, bool) const {
-    double xps = x + s;
+  __device__ __forceinline__ T operator()(T q, T x, T s, T, T, bool) const {
+    T xps = x + s;
     return (fabs(xps + q) <= c) ? -xps : q;
   }
 };
-struct OpL1Box {  // src/shiftedNormL1Box.jl:96-122
-  double sl;      // sigma * lambda
+template <class T>
+struct ProxL1Box {  // src/shiftedNormL1Box.jl:96-122
+  T sl;             // sigma * lambda
   static constexpr bool kBox = true;
-  static constexpr int kLdsKiB = 6;  // KiB per wave and input vector in the LDS-staged skeleton
   static constexpr int kNIn = 3;
-  static constexpr bool kObj = false;     // input vectors besides bounds: q, xk, sj
-  __device__ __forceinline__ double operator()(double q, double x, double s, double l, double u, bool sel) const {
-    double xs = x + s;
-    double xsq = xs + q;
-    double t = (xsq <= -sl) ? (q + sl) : ((xsq >= sl) ? (q - sl) : -xs);  // :111-117
-    t = sel ? t : q;                                                       // :121 prox_zero(qi, ...)
-    return jl_min(jl_max(t, l - s), u - s);                                // :118
+  __device__ __forceinline__ T operator()(T q, T x, T s, T l, T u, bool sel) const {
+    T xs = x + s;
+    T xsq = xs + q;
+    T t = (xsq <= -sl) ? (q + sl) : ((xsq >= sl) ? (q - sl) : -xs);  // :111-117
+    t = sel ? t : q;                                                  // :121 prox_zero(qi, ...)
+    return jl_min(jl_max(t, l - s), u - s);                           // :118
   }
 };
-struct OpL0Box {  // src/shiftedNormL0Box.jl:96-128
-  double c;       // 2 * lambda * sigma
+template <class T>
+struct ProxL0Box {  // src/shiftedNormL0Box.jl:96-128
+  T c;              // 2 * lambda * sigma
   static constexpr bool kBox = true;
-  static constexpr int kLdsKiB = 6;  // KiB per wave and input vector in the LDS-staged skeleton
   static constexpr int kNIn = 3;
-  static constexpr bool kObj = false;     // input vectors besides bounds: q, xk, sj
-  __device__ __forceinline__ double operator()(double q, double x, double s, double l, double u, bool sel) const {
-    double sq = s + q;
-    double xs = x + s;
-    double xsq = xs + q;
-    double dl = l - sq, du = u - sq;
-    double val_left = dl * dl + ((x == -l) ? 0.0 : c);   // :110
-    double val_right = du * du + ((x == -u) ? 0.0 : c);  // :111
-    double yi = (val_left < val_right) ? (l - s) : (u - s);  // :114
-    double val_min = jl_min(val_left, val_right);
-    double mx = -x;
+  __device__ __forceinline__ T operator()(T q, T x, T s, T l, T u, bool sel) const {
+    T sq = s + q;
+    T xs = x + s;
+    T xsq = xs + q;
+    T dl = l - sq, du = u - sq;
+    T val_left = dl * dl + ((x == -l) ? T(0) : c);   // :110
+    T val_right = du * du + ((x == -u) ? T(0) : c);  // :111
+    T yi = (val_left < val_right) ? (l - s) : (u - s);  // :114
+    T val_min = jl_min(val_left, val_right);
+    T mx = -x;
     if (l <= mx && mx <= u) {  // :116
-      double val_0 = xsq * xsq;
+      T val_0 = xsq * xsq;
       yi = (val_0 < val_min) ? -xs : yi;
       val_min = jl_min(val_0, val_min);
     }
     if (l <= sq && sq <= u) {  // :121
-      double val_xsq = (xsq == 0.0) ? 0.0 : c;
+      T val_xsq = (xsq == T(0)) ? T(0) : c;
       yi = (val_xsq < val_min) ? q : yi;
     }
     return sel ? yi : prox_zero(q, l - s, u - s);  // :127
   }
 };
+// The Float64 operators of the kernels below; kLdsKiB: KiB per wave and input vector in the LDS-staged skeleton (0: the
+// register-staged one), kObj: WithValue adds the value of h
+struct OpL1 : ProxL1<double> { static constexpr int kLdsKiB = 6; static constexpr bool kObj = false; };
+struct OpL1Aliased : ProxL1Aliased<double> { static constexpr int kLdsKiB = 6; static constexpr bool kObj = false; };
+struct OpL0 : ProxL0<double> { static constexpr int kLdsKiB = 6; static constexpr bool kObj = false; };
+struct OpL1Box : ProxL1Box<double> { static constexpr int kLdsKiB = 6; static constexpr bool kObj = false; };
+struct OpL0Box : ProxL0Box<double> { static constexpr int kLdsKiB = 6; static constexpr bool kObj = false; };
 
 // ---------------------------------------------------------------------------------------------
 // RootNormLhalf closed form.  Reference (src/shiftedRootNormLhalf.jl:48,57; shiftedRootNormLhalfBox.jl:92,106):
@@ -240,162 +245,166 @@ struct OpLhalfBox {  // src/shiftedRootNormLhalfBox.jl:92-117
 
 // ---------------------------------------------------------------------------------------------
 // iprox!  (SURVEY.md 8f rank 1): argmin 1/2 y'Dy + g'y + psi(y), D = diag(d).  Four input vectors (g, d, xk, sj):
-// 40 B/element.  Only +, -, *, /, sqrt and comparisons: bit-exact against the reference formulas.
+// 40 B/element (20 in Float32).  Only +, -, *, /, sqrt and comparisons: bit-exact against the reference formulas, in
+// either precision (the reference's iprox! methods are generic in R; the thresholds are eps(R)).
 // ---------------------------------------------------------------------------------------------
 // iprox_zero(d, g, l, u)   src/ShiftedProximalOperators.jl:217-236
-__device__ __forceinline__ double iprox_zero(double d, double g, double l, double u) {
-  const double eps = 2.220446049250313e-16;
-  const double a = jl_min(jl_max(-g / d, l), u);                       // d > eps
-  const double d_2 = d / 2;
-  const double b = ((d_2 * (l * l) + g * l) < (d_2 * (u * u) + g * u)) ? l : u;  // d < -eps
-  const double c = (g > 0.0) ? l : ((g < 0.0) ? u : 0.0);              // |d| <= eps
+template <class T>
+__device__ __forceinline__ T iprox_zero(T d, T g, T l, T u) {
+  const T eps = std::numeric_limits<T>::epsilon();
+  const T a = jl_min(jl_max(-g / d, l), u);                          // d > eps
+  const T d_2 = d / 2;
+  const T b = ((d_2 * (l * l) + g * l) < (d_2 * (u * u) + g * u)) ? l : u;  // d < -eps
+  const T c = (g > T(0)) ? l : ((g < T(0)) ? u : T(0));              // |d| <= eps
   return (d > eps) ? a : ((d < -eps) ? b : c);
 }
-struct OpIproxL1 {  // src/shiftedNormL1.jl:60-75
-  double lambda;
+template <class T>
+struct IproxL1 {  // src/shiftedNormL1.jl:60-75
+  T lambda;
   int* flag;  // set when some d[i] <= 0 (the reference's `@assert d[i] > 0`)
   static constexpr bool kBox = false;
-  static constexpr int kLdsKiB = 4;
   static constexpr int kNIn = 4;
-  static constexpr bool kObj = false;
-  __device__ __forceinline__ double call4(double g, double d, double x, double s, double, double, bool) const {
+  __device__ __forceinline__ T call4(T g, T d, T x, T s, T, T, bool) const {
     // (raised once: a d that is wrong everywhere must not queue 1e8 atomics on one address -- 12 ns apiece)
-    if (!(d > 0.0) && __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) atomicOr(flag, 1);
-    const double t = (-x) - s;                                                       // :67
+    if (!(d > T(0)) && __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) atomicOr(flag, 1);
+    const T t = (-x) - s;                                                            // :67
     return jl_min(jl_max(t, -g / d - lambda / d), -g / d + lambda / d);              // :71
   }
 };
-struct OpIproxL0 {  // src/shiftedNormL0.jl:61-80
-  double lambda;
+template <class T>
+struct IproxL0 {  // src/shiftedNormL0.jl:61-80
+  T lambda;
   int* flag;
   static constexpr bool kBox = false;
-  static constexpr int kLdsKiB = 4;
   static constexpr int kNIn = 4;
-  static constexpr bool kObj = false;
-  __device__ __forceinline__ double call4(double g, double d, double x, double s, double, double, bool) const {
+  __device__ __forceinline__ T call4(T g, T d, T x, T s, T, T, bool) const {
     // (raised once: a d that is wrong everywhere must not queue 1e8 atomics on one address -- 12 ns apiece)
-    if (!(d > 0.0) && __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) atomicOr(flag, 1);
-    const double ci = sqrt(2 * lambda * d);                                          // :71
-    const double xps = x + s;
+    if (!(d > T(0)) && __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) atomicOr(flag, 1);
+    const T ci = sqrt(2 * lambda * d);                                               // :71
+    const T xps = x + s;
     return (fabs(d * xps - g) <= ci) ? -xps : (-g / d);                              // :73-77
   }
 };
-struct OpIproxL1Box {  // src/shiftedNormL1Box.jl:131-225
-  double lambda;
+template <class T>
+struct IproxL1Box {  // src/shiftedNormL1Box.jl:131-225
+  T lambda;
   static constexpr bool kBox = true;
-  static constexpr int kLdsKiB = 0;  // register-staged: five fp64 divisions per element want the occupancy (6.10 vs 5.70 TB/s)
   static constexpr int kNIn = 4;
-  static constexpr bool kObj = false;
-  __device__ __forceinline__ double call4(double g, double d, double x, double s, double l, double u, bool sel) const {
-    const double eps = 2.220446049250313e-16;
-    const double xs = x + s;
-    const double left = l - s, right = u - s;
-    double yi;
+  __device__ __forceinline__ T call4(T g, T d, T x, T s, T l, T u, bool sel) const {
+    const T eps = std::numeric_limits<T>::epsilon();
+    const T xs = x + s;
+    const T left = l - s, right = u - s;
+    T yi;
     if (fabs(d) <= eps) {  // :152
-      yi = (fabs(g) <= lambda) ? jl_min(jl_max(left, -xs), right) : ((g > 0) ? left : right);
+      yi = (fabs(g) <= lambda) ? jl_min(jl_max(left, -xs), right) : ((g > T(0)) ? left : right);
     } else {
-      const double d_2 = d / 2;
-      const double lx = l + x, ux = u + x;
-      const double g2_d = g / d_2;
-      const double f2_d = g2_d - 2 * xs;
-      const double l2_d = lambda / d_2;
-      const double val_left = lx * lx + f2_d * lx + l2_d * fabs(lx);
-      const double val_right = ux * ux + f2_d * ux + l2_d * fabs(ux);
+      const T d_2 = d / 2;
+      const T lx = l + x, ux = u + x;
+      const T g2_d = g / d_2;
+      const T f2_d = g2_d - 2 * xs;
+      const T l2_d = lambda / d_2;
+      const T val_left = lx * lx + f2_d * lx + l2_d * fabs(lx);
+      const T val_right = ux * ux + f2_d * ux + l2_d * fabs(ux);
       if (d > eps) {  // :161
-        double val_min = jl_min(val_left, val_right);
+        T val_min = jl_min(val_left, val_right);
         yi = (val_left < val_right) ? left : right;
-        const double y1 = -(g + lambda) / d;
-        const double y2 = (lambda - g) / d;
-        if (lx >= 0.0) {
+        const T y1 = -(g + lambda) / d;
+        const T y2 = (lambda - g) / d;
+        if (lx >= T(0)) {
           if (left <= y1 && y1 <= right) yi = y1;
-        } else if (0.0 >= ux) {
+        } else if (T(0) >= ux) {
           if (left <= y2 && y2 <= right) yi = y2;
         } else {
           if (left <= y1 && y1 <= right) {
-            const double v1 = xs + y1;
-            const double q1 = v1 * v1 + f2_d * v1 + l2_d * fabs(v1);
+            const T v1 = xs + y1;
+            const T q1 = v1 * v1 + f2_d * v1 + l2_d * fabs(v1);
             if (q1 < val_min) yi = y1;
             val_min = jl_min(q1, val_min);
           }
           if (left <= y2 && y2 <= right) {
-            const double v2 = xs + y2;
-            const double q2 = v2 * v2 + f2_d * v2 + l2_d * fabs(v2);
+            const T v2 = xs + y2;
+            const T q2 = v2 * v2 + f2_d * v2 + l2_d * fabs(v2);
             if (q2 < val_min) yi = y2;
             val_min = jl_min(q2, val_min);
           }
-          if (0.0 < val_min) yi = -xs;  // val_0 = 0
+          if (T(0) < val_min) yi = -xs;  // val_0 = 0
         }
       } else {  // d <= -eps, :199
-        const double val_max = jl_max(val_left, val_right);
+        const T val_max = jl_max(val_left, val_right);
         yi = (val_left > val_right) ? left : right;
-        const double mx = -x;
-        if (l <= mx && mx <= u && 0.0 > val_max) yi = -xs;
+        const T mx = -x;
+        if (l <= mx && mx <= u && T(0) > val_max) yi = -xs;
       }
     }
     return sel ? yi : iprox_zero(d, g, left, right);  // :221
   }
 };
-struct OpIproxL0Box {  // src/shiftedNormL0Box.jl:137-231
-  double lambda;
+template <class T>
+struct IproxL0Box {  // src/shiftedNormL0Box.jl:137-231
+  T lambda;
   static constexpr bool kBox = true;
-  static constexpr int kLdsKiB = 4;
   static constexpr int kNIn = 4;
-  static constexpr bool kObj = false;
-  __device__ __forceinline__ double call4(double g, double d, double x, double s, double l, double u, bool sel) const {
-    const double eps = 2.220446049250313e-16;
-    const double xs = x + s;
-    const double mx = -x;
+  __device__ __forceinline__ T call4(T g, T d, T x, T s, T l, T u, bool sel) const {
+    const T eps = std::numeric_limits<T>::epsilon();
+    const T xs = x + s;
+    const T mx = -x;
     const bool zero_ok = (l <= mx && mx <= u);
-    const double left = l - s, right = u - s;
-    double yi;
+    const T left = l - s, right = u - s;
+    T yi;
     if (fabs(d) < eps) {  // :154
-      if (g == 0.0) {
-        yi = zero_ok ? -xs : 0.0;
+      if (g == T(0)) {
+        yi = zero_ok ? -xs : T(0);
       } else {
-        const bool pos = g > 0.0;
-        const double t = pos ? left : right;
-        const double val_min = g * t + ((x == (pos ? -l : -u)) ? 0.0 : lambda);
+        const bool pos = g > T(0);
+        const T t = pos ? left : right;
+        const T val_min = g * t + ((x == (pos ? -l : -u)) ? T(0) : lambda);
         yi = t;
         if (zero_ok && (-g * xs) < val_min) yi = -xs;
       }
     } else {
-      const double d_2 = d / 2;
-      const double lx = l + x, ux = u + x;
-      const double g2_d = g / d_2;
-      const double f2_d = g2_d - 2 * xs;
-      const double l2_d = lambda / d_2;
-      const double val_left = (lx == 0.0) ? 0.0 : (lx * lx + f2_d * lx + l2_d);
-      const double val_right = (ux == 0.0) ? 0.0 : (ux * ux + f2_d * ux + l2_d);
+      const T d_2 = d / 2;
+      const T lx = l + x, ux = u + x;
+      const T g2_d = g / d_2;
+      const T f2_d = g2_d - 2 * xs;
+      const T l2_d = lambda / d_2;
+      const T val_left = (lx == T(0)) ? T(0) : (lx * lx + f2_d * lx + l2_d);
+      const T val_right = (ux == T(0)) ? T(0) : (ux * ux + f2_d * ux + l2_d);
       if (d >= eps) {  // :190
-        const double aqy = -g / d;
-        const double aqv = aqy + xs;
-        double val_min;
+        const T aqy = -g / d;
+        const T aqv = aqy + xs;
+        T val_min;
         if (lx <= aqv && aqv <= ux) {
-          val_min = (aqv == 0.0) ? (-(aqv * aqv)) : (-(aqv * aqv) + l2_d);
+          val_min = (aqv == T(0)) ? (-(aqv * aqv)) : (-(aqv * aqv) + l2_d);
           yi = aqy;
         } else {
           yi = (val_left < val_right) ? left : right;
           val_min = jl_min(val_left, val_right);
         }
-        if (zero_ok && 0.0 < val_min) yi = -xs;
+        if (zero_ok && T(0) < val_min) yi = -xs;
       } else {  // :213
         yi = (val_left > val_right) ? left : right;
-        const double val_max = jl_max(val_left, val_right);
-        if (zero_ok && 0.0 > val_max) yi = -xs;
+        const T val_max = jl_max(val_left, val_right);
+        if (zero_ok && T(0) > val_max) yi = -xs;
       }
     }
     return sel ? yi : iprox_zero(d, g, left, right);  // :227
   }
 };
+struct OpIproxL1 : IproxL1<double> { static constexpr int kLdsKiB = 4; static constexpr bool kObj = false; };
+struct OpIproxL0 : IproxL0<double> { static constexpr int kLdsKiB = 4; static constexpr bool kObj = false; };
+// register-staged: five fp64 divisions per element want the occupancy (6.10 vs 5.70 TB/s)
+struct OpIproxL1Box : IproxL1Box<double> { static constexpr int kLdsKiB = 0; static constexpr bool kObj = false; };
+struct OpIproxL0Box : IproxL0Box<double> { static constexpr int kLdsKiB = 4; static constexpr bool kObj = false; };
 
 // ---------------------------------------------------------------------------------------------
 // prox! fused with the value of h at the result ("fused with prox where possible"): the kernels
 // below add Term((xk + sj) + y) over the selected indices into one partial per wavefront / workgroup
 // (src/ShiftedProximalOperators.jl:51-54 for the association), a second small kernel adds the partials in index order.
 // ---------------------------------------------------------------------------------------------
-struct HTermL1 { __device__ __forceinline__ double operator()(double v) const { return fabs(v); } };               // NormL1 [ext]
-struct HTermL0 { __device__ __forceinline__ double operator()(double v) const { return (v != 0.0) ? 1.0 : 0.0; } };  // NormL0 [ext]
-struct HTermLhalf { __device__ __forceinline__ double operator()(double v) const { return sqrt(fabs(v)); } };      // src/rootNormLhalf.jl:27-29
+// (the element terms of spx_common.hpp under names of this file's own, which the kernel names carry)
+struct HTermL1 : TermL1 {};
+struct HTermL0 : TermL0 {};
+struct HTermLhalf : TermLhalf {};
 template <class Base, class Term>
 struct WithValue : Base {
   static constexpr bool kObj = true;
@@ -506,9 +515,8 @@ __global__ __launch_bounds__(1024) void k_value_reduce(const double* partials, i
 }
 
 // uniform call: 3-input operators ignore d
-template <class Op>
-__device__ __forceinline__ double apply_op(const Op& op, double q, double d, double x, double s, double l, double u,
-                                           bool sel) {
+template <class Op, class T>
+__device__ __forceinline__ T apply_op(const Op& op, T q, T d, T x, T s, T l, T u, bool sel) {
   if constexpr (Op::kNIn == 4) return op.call4(q, d, x, s, l, u, sel);
   else return op(q, x, s, l, u, sel);
 }
@@ -1006,24 +1014,219 @@ SPX_EXPORT int spx_proxval_lhalf_box(spx_ctx* ctx, double* y, const double* q, c
 }
 
 // ---------------------------------------------------------------------------------------------
+// Float32 vectors.  The reference's structs and prox! / iprox! methods are generic in R <: Real (src/shiftedNormL1Box.jl:89-94:
+// `y::AbstractVector{R}, psi::ShiftedNormL1Box{R, ...}, q::AbstractVector{R}, sigma::R`) and its tests build Float32
+// operators on views (test/runtests.jl:196-209): the L1 / L0 bodies above with T = float.  (RootNormLhalf is NOT here: its
+// body mixes Float64 literals -- `^(-3 / 2)`, `54^(1 / 3)` -- into the Float32 data, i.e. the reference itself computes it in
+// Float64 and rounds; the fp64 entry points cover that after a conversion by the caller.)
+//
+// HBM: 16 B/element (read q, xk, sj, write y; +8 with vector bounds, +1 with a mask) -- half the bytes of the fp64 path.
+// Skeleton: one tile of 256 lanes x 4 x (4 floats = 16 bytes) per workgroup, all 12 non-temporal 16-byte loads of a lane
+// issued before first use, 16-byte non-temporal stores.  Views that start at any element (4-byte granularity) are
+// peeled to a 16-byte boundary when all vectors share the misalignment; mixed alignments take 4-byte accesses.
+// y === q is safe (a lane reads q[i] before it writes y[i]; lanes own disjoint indices).
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+struct F32L1 : ProxL1<float> {};
+struct F32L1Aliased : ProxL1Aliased<float> {};
+struct F32L0 : ProxL0<float> {};
+struct F32L1Box : ProxL1Box<float> {};
+struct F32L0Box : ProxL0Box<float> {};
+struct F32IproxL1 : IproxL1<float> {};
+struct F32IproxL0 : IproxL0<float> {};
+struct F32IproxL1Box : IproxL1Box<float> {};
+struct F32IproxL0Box : IproxL0Box<float> {};
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+constexpr int kF32U = 4;                       // 16-byte groups per lane and vector
+constexpr int kF32Tile = 256 * kF32U;          // 16-byte groups per workgroup
+
+// body: `n4` groups of 4 floats starting at the (16-byte aligned) pointers; head: `head` (< 4) elements in front of them
+// (at [-head .. -1]) and tail: `tail` (< 4) elements behind them, taken by single lanes of workgroup 0.
+template <class Op, bool VECB, bool MASK>
+__global__ __launch_bounds__(256) void k_sep_f32(float* y_, const float* q_, const float* d_, const float* xk_, const float* sj_,
+                                                  const float* l_, const float* u_, const uint8_t* mask, float ls,
+                                                  float us, int64_t n4, int head, int tail, Op op) {
+  f32x4* y = reinterpret_cast<f32x4*>(y_);
+  const f32x4* q = reinterpret_cast<const f32x4*>(q_);
+  const f32x4* xk = reinterpret_cast<const f32x4*>(xk_);
+  const f32x4* sj = reinterpret_cast<const f32x4*>(sj_);
+  const f32x4* lv = reinterpret_cast<const f32x4*>(l_);
+  const f32x4* uv = reinterpret_cast<const f32x4*>(u_);
+  const f32x4* dv = reinterpret_cast<const f32x4*>(d_);
+  const int64_t base = (int64_t)blockIdx.x * kF32Tile + threadIdx.x;
+  f32x4 a[kF32U], b[kF32U], c[kF32U], lo[kF32U], up[kF32U], dd[kF32U];
+#pragma unroll
+  for (int k = 0; k < kF32U; ++k) {
+    int64_t i = base + k * 256;
+    if (i >= n4) i = n4 > 0 ? n4 - 1 : 0;
+    if (n4 > 0) {
+      a[k] = __builtin_nontemporal_load(q + i);
+      b[k] = __builtin_nontemporal_load(xk + i);
+      c[k] = __builtin_nontemporal_load(sj + i);
+      if constexpr (Op::kNIn == 4) dd[k] = __builtin_nontemporal_load(dv + i);
+      if constexpr (VECB && Op::kBox) {
+        lo[k] = l_ ? __builtin_nontemporal_load(lv + i) : f32x4{ls, ls, ls, ls};
+        up[k] = u_ ? __builtin_nontemporal_load(uv + i) : f32x4{us, us, us, us};
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < kF32U; ++k) {
+    const int64_t i = base + k * 256;
+    if (i < n4) {
+      f32x4 o;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float l1 = ls, u1 = us;
+        if constexpr (VECB && Op::kBox) { l1 = lo[k][e]; u1 = up[k][e]; }
+        bool sel = true;
+        if constexpr (MASK && Op::kBox) sel = mask[4 * i + e] != 0;
+        float d1 = 0.0f;
+        if constexpr (Op::kNIn == 4) d1 = dd[k][e];
+        o[e] = apply_op(op, a[k][e], d1, b[k][e], c[k][e], l1, u1, sel);
+      }
+      __builtin_nontemporal_store(o, y + i);
+    }
+  }
+  if (blockIdx.x == 0 && (int)threadIdx.x < head + tail) {  // the few elements outside the aligned body
+    const int64_t i = ((int)threadIdx.x < head) ? (int64_t)threadIdx.x - head : 4 * n4 + ((int)threadIdx.x - head);
+    float l1 = ls, u1 = us;
+    if constexpr (Op::kBox) {
+      if (l_) l1 = l_[i];
+      if (u_) u1 = u_[i];
+    }
+    bool sel = true;
+    if constexpr (MASK && Op::kBox) sel = mask[i] != 0;
+    float d1 = 0.0f;
+    if constexpr (Op::kNIn == 4) d1 = d_[i];
+    y_[i] = apply_op(op, q_[i], d1, xk_[i], sj_[i], l1, u1, sel);
+  }
+}
+
+// mixed alignments: 4-byte accesses
+template <class Op>
+__global__ __launch_bounds__(256) void k_sep_f32_scalar(float* y, const float* q, const float* d, const float* xk, const float* sj,
+                                                         const float* l, const float* u, const uint8_t* mask, float ls,
+                                                         float us, int64_t n, Op op) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    float l1 = ls, u1 = us;
+    bool sel = true;
+    if constexpr (Op::kBox) {
+      if (l) l1 = l[i];
+      if (u) u1 = u[i];
+      if (mask) sel = mask[i] != 0;
+    }
+    float d1 = 0.0f;
+    if constexpr (Op::kNIn == 4) d1 = d[i];
+    y[i] = apply_op(op, q[i], d1, xk[i], sj[i], l1, u1, sel);
+  }
+}
+
+template <class Op>
+int run_f32(spx_ctx* ctx, float* y, const float* q, const float* xk, const float* sj, int64_t n, const float* l,
+            const float* u, float ls, float us, const uint8_t* mask, Op op, const float* d = nullptr) {
+  int rc = spx_check_common(ctx, y, q, xk, sj, n);
+  if (rc) return rc;
+  if (n == 0) return SPX_OK;
+  SPX_ON_DEVICE(ctx);
+  auto mis = [](const void* p) { return (unsigned)(reinterpret_cast<uintptr_t>(p) & 15u); };
+  const unsigned m = mis(y);
+  bool same = (m % 4 == 0) && mis(q) == m && mis(xk) == m && mis(sj) == m && (!d || mis(d) == m);
+  if (Op::kBox) same = same && (!l || mis(l) == m) && (!u || mis(u) == m);
+  if (!same) {
+    int64_t blocks = (n + 255) / 256;
+    const int64_t cap = (int64_t)ctx->num_cu * 16;
+    if (blocks > cap) blocks = cap;
+    hipLaunchKernelGGL((k_sep_f32_scalar<Op>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, y, q, d, xk, sj, l, u, mask, ls,
+                       us, n, op);
+    SPX_LAUNCH_CHECK();
+    return SPX_OK;
+  }
+  int head = (int)(((16u - m) / 4u) & 3u);
+  if (head > n) head = (int)n;
+  const int64_t n4 = (n - head) / 4;
+  const int tail = (int)(n - head - 4 * n4);
+  int64_t blocks = (n4 + kF32Tile - 1) / kF32Tile;
+  if (blocks < 1) blocks = 1;
+  const dim3 grid((unsigned)blocks), block(256);
+  const bool vecb = Op::kBox && (l || u);
+  const bool msk = Op::kBox && mask != nullptr;
+  const uint8_t* mk = mask ? mask + head : nullptr;
+  const float* lp = l ? l + head : nullptr;
+  const float* up = u ? u + head : nullptr;
+  const float* dp = d ? d + head : nullptr;
+#define SPX_F32_LAUNCH(VB, MK)                                                                                         \
+  hipLaunchKernelGGL((k_sep_f32<Op, VB, MK>), grid, block, 0, ctx->stream, y + head, q + head, dp, xk + head, sj + head, lp, \
+                     up, mk, ls, us, n4, head, tail, op)
+  if (vecb && msk) SPX_F32_LAUNCH(true, true);
+  else if (vecb) SPX_F32_LAUNCH(true, false);
+  else if (msk) SPX_F32_LAUNCH(false, true);
+  else SPX_F32_LAUNCH(false, false);
+#undef SPX_F32_LAUNCH
+  SPX_LAUNCH_CHECK();
+  return SPX_OK;
+}
+
+}  // namespace
+
+SPX_EXPORT int spx_prox_l1_f32(spx_ctx* ctx, float* y, const float* q, const float* xk, const float* sj, int64_t n,
+                               float lambda, float sigma) {
+  if (y == q && n > 0) return run_f32(ctx, y, q, xk, sj, n, nullptr, nullptr, 0.0f, 0.0f, nullptr, F32L1Aliased{});
+  return run_f32(ctx, y, q, xk, sj, n, nullptr, nullptr, 0.0f, 0.0f, nullptr, F32L1{lambda * sigma});
+}
+
+SPX_EXPORT int spx_prox_l0_f32(spx_ctx* ctx, float* y, const float* q, const float* xk, const float* sj, int64_t n,
+                               float lambda, float sigma) {
+  return run_f32(ctx, y, q, xk, sj, n, nullptr, nullptr, 0.0f, 0.0f, nullptr, F32L0{sqrtf(2 * lambda * sigma)});
+}
+
+SPX_EXPORT int spx_prox_l1_box_f32(spx_ctx* ctx, float* y, const float* q, const float* xk, const float* sj, int64_t n,
+                                   float lambda, float sigma, const float* l_vec, const float* u_vec, float l_scalar,
+                                   float u_scalar, const uint8_t* sel_mask) {
+  return run_f32(ctx, y, q, xk, sj, n, l_vec, u_vec, l_scalar, u_scalar, sel_mask, F32L1Box{sigma * lambda});
+}
+
+SPX_EXPORT int spx_prox_l0_box_f32(spx_ctx* ctx, float* y, const float* q, const float* xk, const float* sj, int64_t n,
+                                   float lambda, float sigma, const float* l_vec, const float* u_vec, float l_scalar,
+                                   float u_scalar, const uint8_t* sel_mask) {
+  return run_f32(ctx, y, q, xk, sj, n, l_vec, u_vec, l_scalar, u_scalar, sel_mask, F32L0Box{2 * lambda * sigma});
+}
+
+
+// ---------------------------------------------------------------------------------------------
 // iprox! entry points
 // ---------------------------------------------------------------------------------------------
+// the skeleton of each precision
 template <class Op>
-static int run_iprox_unboxed(spx_ctx* ctx, double* y, const double* g, const double* d, const double* xk,
-                             const double* sj, int64_t n, double lambda, int check_d) {
+static int run_unboxed(spx_ctx* ctx, double* y, const double* g, const double* d, const double* xk, const double* sj,
+                       int64_t n, Op op) {
+  return run_separable(ctx, y, g, xk, sj, n, nullptr, nullptr, 0.0, 0.0, nullptr, op, d);
+}
+template <class Op>
+static int run_unboxed(spx_ctx* ctx, float* y, const float* g, const float* d, const float* xk, const float* sj, int64_t n,
+                       Op op) {
+  return run_f32(ctx, y, g, xk, sj, n, nullptr, nullptr, 0.0f, 0.0f, nullptr, op, d);
+}
+// check_d: the d > 0 flag is read back, which synchronises the stream -- refused under a capture before anything is enqueued
+template <class Op, class T>
+static int run_iprox_unboxed(spx_ctx* ctx, T* y, const T* g, const T* d, const T* xk, const T* sj, int64_t n, T lambda,
+                             int check_d) {
   int rc = spx_check_common(ctx, y, g, xk, sj, n);
   if (rc) return rc;
   SPX_REQUIRE(n == 0 || d != nullptr, "d is NULL");
   if (n == 0) return SPX_OK;
+  if (check_d) { rc = spx_require_not_capturing(ctx, "the d > 0 check of iprox! (pass check = 0)"); if (rc) return rc; }
   rc = spx_ws_reserve(ctx, 256);
   if (rc) return rc;
   SPX_ON_DEVICE(ctx);
   int* flag = reinterpret_cast<int*>(ctx->ws);
   { const int rz = spx_zero_async(ctx, flag, sizeof(int)); if (rz) return rz; }
-  rc = run_separable(ctx, y, g, xk, sj, n, nullptr, nullptr, 0.0, 0.0, nullptr, Op{lambda, flag}, d);
+  rc = run_unboxed(ctx, y, g, d, xk, sj, n, Op{lambda, flag});
   if (rc || !check_d) return rc;
   int bad = 0;
-  { const int rcc = spx_require_not_capturing(ctx, "the d > 0 check of iprox! (pass check = 0)"); if (rcc) return rcc; }
   SPX_HIP(hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
   SPX_HIP(hipStreamSynchronize(ctx->stream));
   if (bad) {
@@ -1056,4 +1259,29 @@ SPX_EXPORT int spx_iprox_l0_box(spx_ctx* ctx, double* y, const double* g, const 
   if (rc) return rc;
   SPX_REQUIRE(n == 0 || d != nullptr, "d is NULL");
   return run_separable(ctx, y, g, xk, sj, n, l_vec, u_vec, l_scalar, u_scalar, sel_mask, OpIproxL0Box{lambda}, d);
+}
+
+SPX_EXPORT int spx_iprox_l1_f32(spx_ctx* ctx, float* y, const float* g, const float* d, const float* xk, const float* sj,
+                                int64_t n, float lambda, int check_d) {
+  return run_iprox_unboxed<F32IproxL1>(ctx, y, g, d, xk, sj, n, lambda, check_d);
+}
+SPX_EXPORT int spx_iprox_l0_f32(spx_ctx* ctx, float* y, const float* g, const float* d, const float* xk, const float* sj,
+                                int64_t n, float lambda, int check_d) {
+  return run_iprox_unboxed<F32IproxL0>(ctx, y, g, d, xk, sj, n, lambda, check_d);
+}
+SPX_EXPORT int spx_iprox_l1_box_f32(spx_ctx* ctx, float* y, const float* g, const float* d, const float* xk, const float* sj,
+                                    int64_t n, float lambda, const float* l_vec, const float* u_vec, float l_scalar,
+                                    float u_scalar, const uint8_t* sel_mask) {
+  int rc = spx_check_common(ctx, y, g, xk, sj, n);
+  if (rc) return rc;
+  SPX_REQUIRE(n == 0 || d != nullptr, "d is NULL");
+  return run_f32(ctx, y, g, xk, sj, n, l_vec, u_vec, l_scalar, u_scalar, sel_mask, F32IproxL1Box{lambda}, d);
+}
+SPX_EXPORT int spx_iprox_l0_box_f32(spx_ctx* ctx, float* y, const float* g, const float* d, const float* xk, const float* sj,
+                                    int64_t n, float lambda, const float* l_vec, const float* u_vec, float l_scalar,
+                                    float u_scalar, const uint8_t* sel_mask) {
+  int rc = spx_check_common(ctx, y, g, xk, sj, n);
+  if (rc) return rc;
+  SPX_REQUIRE(n == 0 || d != nullptr, "d is NULL");
+  return run_f32(ctx, y, g, xk, sj, n, l_vec, u_vec, l_scalar, u_scalar, sel_mask, F32IproxL0Box{lambda}, d);
 }
