@@ -76,7 +76,10 @@ const char* spx_last_error(void);
 /* device: HIP device ordinal.  spx_ctx_create: the context creates and owns a non-blocking stream.
  * spx_ctx_create_on_stream: enqueue on the caller's hipStream_t (passed as void*; NULL = the legacy
  * default stream), e.g. the array library's current stream, so that calls are ordered with the
- * caller's own kernels; the stream is borrowed, never destroyed. */
+ * caller's own kernels; the stream is borrowed, never destroyed.  Either form allocates the context's synchronisation state
+ * (about 4.5 MiB of device memory for the kernels that synchronise inside one launch), zero-fills it on the stream and
+ * synchronises the stream -- unless the stream is being captured, in which case the first call that needs the state
+ * outside a capture does so.  SPX_ERR_ALLOC if the allocation fails. */
 int spx_ctx_create(int device, spx_ctx** out);
 int spx_ctx_create_on_stream(int device, void* stream, spx_ctx** out);
 int spx_ctx_destroy(spx_ctx* ctx);
@@ -91,8 +94,9 @@ int spx_sync(spx_ctx* ctx);
 int spx_ctx_set_value_target(spx_ctx* ctx, double* device_value);
 /* Stream capture (hipGraph): calls on a context whose stream is being captured are recorded, not run.  Capturable: every
  * prox / iprox (check = 0) / objective / prox-value entry point on device pointers, provided values go to a device double
- * (spx_ctx_set_value_target) and the same call has run once before on this context (workspaces do not grow while
- * capturing).  Not capturable (SPX_ERR_INVALID_ARG, nothing launched): host-valued results, spx_check_bounds, index-set
+ * (spx_ctx_set_value_target) and the same call has run once before on this context (the workspace does not grow while
+ * capturing; the synchronisation state exists from spx_ctx_create on, or -- for a context created during a capture -- from
+ * its first such call outside one).  Not capturable (SPX_ERR_INVALID_ARG, nothing launched): host-valued results, spx_check_bounds, index-set
  * (gather) group layouts, host-pointer forms, ShiftedNormL1B2 on vectors of mixed alignment.  The first capture puts the
  * context into a graph-safe mode for good: the kernels that synchronise inside one launch are then preceded by a zero-fill of
  * the state they use (in the graph and in eager calls alike), ~2-4 us per such call, and a workspace that a LATER, larger

@@ -889,15 +889,15 @@ SPX_EXPORT int spx_prox_l1_b2(spx_ctx* ctx, double* y, const double* q, const do
     if (rc) return rc;
     cand = reinterpret_cast<f64x2*>(ctx->ws);
   }
-  rc = spx_sync_reserve(ctx, kSpxSyncSelBytes + kB2SyncBytes);
+  rc = spx_sync_ready(ctx);
   if (rc) return rc;
   auto disjoint = [&](const double* a) { return (y + n <= a) || (a + n <= y); };
   const int can_spec = (disjoint(q) && disjoint(xk) && disjoint(sj)) ? 1 : 0;
-  SpxSyncHeader* hdr = reinterpret_cast<SpxSyncHeader*>(ctx->sync);
-  unsigned long long* sets = reinterpret_cast<unsigned long long*>(static_cast<char*>(ctx->sync) + kSpxSyncSelBytes);
-  int use = ctx->b2_set, other = use ^ 1;
-  int clear_g = ctx->b2_dirty_g[other];
-  const bool graph_safe = spx_capture_check(ctx) || ctx->graph_safe;  // (see spx_ctx::graph_safe)
+  SpxSyncHeader* hdr = spx_sync_header(ctx);
+  unsigned long long* sets = spx_sync_b2(ctx);
+  int use = ctx->track.b2_set, other = use ^ 1;
+  int clear_g = ctx->track.b2_dirty_g[other];
+  const bool graph_safe = spx_graph_safe(ctx);
   if (graph_safe) {  // set 0, its g columns zeroed by a node in front of the launch; nothing alternates
     use = 0; other = 1; clear_g = 0;
     if (g > 1) {
@@ -924,11 +924,11 @@ SPX_EXPORT int spx_prox_l1_b2(spx_ctx* ctx, double* y, const double* q, const do
                          delta, chi_lambda, rows, clear_rows, clear_g, hdr, can_spec, cand, cand_cap);
   }
   if (graph_safe) {  // both sets count as used by the widest grid from here on (a replay may have touched set 0)
-    ctx->b2_dirty_g[0] = ctx->b2_dirty_g[1] = kB2Cols;
+    ctx->track.b2_dirty_g[0] = ctx->track.b2_dirty_g[1] = kB2Cols;
   } else {
-    ctx->b2_dirty_g[use] = (g > 1) ? (int)g : 0;  // (one workgroup exchanges nothing)
-    ctx->b2_dirty_g[other] = 0;
-    ctx->b2_set = other;
+    ctx->track.b2_dirty_g[use] = (g > 1) ? (int)g : 0;  // (one workgroup exchanges nothing)
+    ctx->track.b2_dirty_g[other] = 0;
+    ctx->track.b2_set = other;
   }
   SPX_LAUNCH_CHECK();
   return SPX_OK;

@@ -25,26 +25,28 @@ struct spx_ctx {
   // device staging area of the host-pointer entry points (spx_host.hip); grown on demand, never shrunk
   void* stage = nullptr;
   size_t stage_bytes = 0;
-  // ShiftedNormL1B2: did the last call take the scaled branch (trust region active)?  Only steers whether the first
-  // reduction pass also stores y (it is the result when the trust region is inactive); never affects results.
-  int b2_last_scaled = 0;
-  // Persistent device state of the multi-workgroup kernels that synchronise inside one launch (grid-barrier counters,
-  // histograms that must be zero on entry): allocated and zeroed once, never shared with `ws` (which every operator
-  // overwrites from offset 0).  coop_parity alternates per such launch: a launch uses counter/histogram set `parity`
-  // and clears set `parity ^ 1`, which the previous launch on this stream used and has finished with.
+  // Persistent device state of the kernels that synchronise inside one launch (grid-barrier counters, histograms that must
+  // be zero on entry, exchange words, tickets): one block of kSpxSyncBytes in a fixed layout (below), allocated and zeroed
+  // when the context is created, never moved and never shared with `ws` (which every operator overwrites from offset 0).
+  // Null only while a context created during a stream capture has not yet run a call that needs it (spx_sync_ready).
   void* sync = nullptr;
-  size_t sync_bytes = 0;
-  int coop_parity = 0;
+  // The host's view of the alternating sets in `sync`: which set the next launch uses and which sets earlier launches left
+  // dirty.  Describes a zero block: reset (value-initialised) whenever the block is zeroed.
+  struct SyncTrack {
+    int coop_parity = 0;             // spx_select.hip: a launch uses counter/histogram set `parity` and clears set `parity ^ 1`,
+                                     // which the previous launch on this stream used and has finished with
+    int sel_hist_next = 0;           // spx_select.hip: histogram set (0/1) the next k_sel_coop launch uses ...
+    int sel_hist_dirty[2] = {0, 0};  // ... and which sets a previous launch left non-zero
+    int b2_set = 0;                  // ShiftedNormL1B2: the set of partial-sum words the next launch uses (spx_b2.hip, b2_put)
+    int b2_dirty_g[2] = {0, 0};      // ... and how many workgroups wrote into each set (0 = clean)
+    int team_set = 0;                // spx_group_team.hip: the set of exchange words the next team launch uses (it clears the other one)
+    int grp_def_set = 0;             // spx_group.hip: which of SpxSyncHeader::grp_deferred the next call uses (it clears the other one)
+  } track;
   // Graph-safe mode (sticky, set the first time a call finds its stream capturing: spx_capture_check).  The kernels that
   // synchronise inside one launch keep device state between launches (barrier counters, histogram sets, exchange words) that
   // the host tracks by alternating sets -- a captured launch would replay ONE set for ever.  In graph-safe mode every such
   // launch is preceded by a memset of exactly the state it uses (a node of the same graph) and the sets are fixed.
   int graph_safe = 0;
-  int b2_set = 0;                 // ShiftedNormL1B2: the set of partial-sum words the next launch uses (spx_b2.hip, b2_put)
-  int b2_dirty_g[2] = {0, 0};     // ... and how many workgroups wrote into each set (0 = clean)
-  int team_set = 0;               // spx_group_team.hip: the set of exchange words the next team launch uses (it clears the other one)
-  int sel_hist_next = 0;            // spx_select.hip: histogram set (0/1) the next k_sel_coop launch uses ...
-  int sel_hist_dirty[2] = {0, 0};   // ... and which sets a previous launch left non-zero
   // spx_ctx_set_value_target: when non-NULL, the value-returning entry points (spx_obj_*, spx_proxval_*) store their
   // result in this DEVICE double and return after enqueueing, without the read-back / stream synchronisation
   double* value_target = nullptr;
@@ -72,7 +74,6 @@ struct spx_ctx {
                                    //         grid (0 = default, see run_group in spx_group.hip); an A/B knob
   int tune_fewer_launches = 1;     // key 17: psi(y) in one launch (the last workgroup finishes: spx_fin_ticket) and the Binf group operators without the
                                    //         zero-fill launch of their deferred list (count words that alternate); 0 = the launches of rounds 1-3
-  int grp_def_set = 0;             // spx_group.hip: which of SpxSyncHeader::grp_deferred the next call uses (it clears the other one)
   int tune_force_grid = 0;         // key 100, test builds only (-DSPX_TEST_HOOKS): launch the one-launch top-r with THIS many workgroups,
                                    //          residency or not -- the planted fault behind tests/test_gpu_robustness.py
   int tune_force_team = 0;         // key 102, test builds only: the last workgroup of every team of k_group_team arrives late (spx_group_team.hip)
@@ -83,14 +84,9 @@ struct spx_ctx {
   // then on, until spx_sync has reported it.  No stream synchronisation and no read-back is involved.
   volatile int* status_host = nullptr;
   int* status_dev = nullptr;
-  // Blocks that a captured graph may still reference (graph_safe): never freed before the context is destroyed.
+  // Workspace blocks that a captured graph may still reference (graph_safe): never freed before the context is destroyed.
   void* retired[64] = {};
   int nretired = 0;
-  // ... those of them that are synchronisation-state blocks (spx_sync_reserve), with their sizes: a captured graph that timed out
-  // on such a block would replay NaN for ever if spx_sync reset the current block only
-  void* retired_sync[16] = {};
-  size_t retired_sync_bytes[16] = {};
-  int nretired_sync = 0;
   // resident workgroups per CU of the in-launch synchronised kernels (hipOccupancyMaxActiveBlocksPerMultiprocessor),
   // queried once per kernel and context: spx_resident_cap
   const void* occ_fn[32] = {};
@@ -104,7 +100,10 @@ constexpr int kSpxStatusCorrupt = 2;    // library-owned device state outside it
 
 void spx_set_error(const char* fmt, ...);
 int spx_ws_reserve(spx_ctx* ctx, size_t bytes);
-int spx_sync_reserve(spx_ctx* ctx, size_t bytes);  // persistent, zero-initialised (see spx_ctx::sync)
+// spx_ctx::sync is there unless the context was created while its stream was being captured: then the first call that needs
+// it allocates it outside a capture and refuses inside one (SPX_ERR_INVALID_ARG, before anything is enqueued)
+int spx_sync_alloc(spx_ctx* ctx);
+static inline int spx_sync_ready(spx_ctx* ctx) { return ctx->sync ? SPX_OK : spx_sync_alloc(ctx); }
 int spx_ctx_count(int device);                     // live contexts on a device
 // How many workgroups of `fn` (block_threads lanes, dyn_lds bytes of dynamic LDS) can be resident at once on the context's
 // device: occupancy query x number of CUs, cached per kernel; spx_ctx_set_tuning key 8 lowers it (tests).  Every launch that
@@ -122,6 +121,8 @@ int spx_zero_async(spx_ctx* ctx, void* ptr, size_t bytes);
 int spx_zero2d_async(spx_ctx* ctx, void* ptr, size_t pitch_bytes, size_t width_bytes, size_t rows);
 bool spx_capture_check(spx_ctx* ctx);
 int spx_require_not_capturing(spx_ctx* ctx, const char* what);
+// Does an in-launch synchronised launch take its graph-safe form (see spx_ctx::graph_safe)?  Switches the mode on if capturing.
+static inline bool spx_graph_safe(spx_ctx* ctx) { return spx_capture_check(ctx) || ctx->graph_safe; }
 
 // spx_group_team.hip (large contiguous groups on teams of workgroups), called from run_group in spx_group.hip
 int spx_group_team_max_grid(spx_ctx* ctx, bool binf);
@@ -298,12 +299,17 @@ __device__ __forceinline__ double fold16_sum(double v) {
   return v;
 }
 
-// spx_ctx::sync: [0, kSpxSyncSelBytes) belongs to spx_select.hip (SelSync, whose head is the SpxSyncHeader below), the
-// partial-sum words of spx_b2.hip follow.  Zero-filled when (re)allocated; the host-side flags are reset with it.
-constexpr size_t kSpxSyncSelBytes = (size_t)2 << 20;  // 2 MiB >= sizeof(SelSync) (static_assert in spx_select.hip)
-constexpr size_t kSpxSyncB2Bytes = (size_t)2 << 20;   // the exchange words of spx_b2.hip (static_assert there)
-constexpr size_t kSpxSyncTeamOffset = kSpxSyncSelBytes + kSpxSyncB2Bytes;  // ... and behind them those of spx_group_team.hip:
-constexpr size_t kSpxSyncTeamBytes = ((size_t)512 << 10) + 4096;           // two sets of kGtSetWords words + two sets of tile counters (static_assert in spx_group_common.hpp)
+// The layout of spx_ctx::sync, one block of kSpxSyncBytes per context (zero-filled when the context is created, and by
+// spx_sync after a timeout; spx_ctx::track is reset with it):
+//   [0, 2 MiB)          spx_select.hip: SelSync, whose head is the SpxSyncHeader below (spx_sync_header)
+//   [2 MiB, 4 MiB)      spx_b2.hip: two sets of partial-sum words (spx_sync_b2)
+//   [4 MiB, 4.5 MiB + 4 KiB)  spx_group_team.hip: two sets of exchange words, two sets of tile counters (spx_sync_team)
+constexpr size_t kSpxSyncSelBytes = (size_t)2 << 20;  // >= sizeof(SelSync) (static_assert in spx_select.hip)
+constexpr size_t kSpxSyncB2Offset = kSpxSyncSelBytes;
+constexpr size_t kSpxSyncB2Bytes = (size_t)2 << 20;   // (static_assert in spx_b2.hip)
+constexpr size_t kSpxSyncTeamOffset = kSpxSyncB2Offset + kSpxSyncB2Bytes;
+constexpr size_t kSpxSyncTeamBytes = ((size_t)512 << 10) + 4096;  // (static_assert in spx_group_common.hpp)
+constexpr size_t kSpxSyncBytes = kSpxSyncTeamOffset + kSpxSyncTeamBytes;
 
 // Head of spx_ctx::sync, shared by every kernel that synchronises inside one launch.
 constexpr int kSpxBarSplit = 8;  // arrival counters per grid barrier (see spx_grid_rendezvous)
@@ -320,6 +326,13 @@ struct SpxSyncHeader {
   unsigned int fin_class[kSpxBarSplit * 32];  // first-level tickets, one 128-byte line each
 };
 static_assert(sizeof(SpxSyncHeader) == 2 * kSpxBarSplit * 32 * 4 + 128 + kSpxBarSplit * 32 * 4, "SpxSyncHeader layout");
+static inline SpxSyncHeader* spx_sync_header(spx_ctx* ctx) { return static_cast<SpxSyncHeader*>(ctx->sync); }
+static inline unsigned long long* spx_sync_b2(spx_ctx* ctx) {
+  return reinterpret_cast<unsigned long long*>(static_cast<char*>(ctx->sync) + kSpxSyncB2Offset);
+}
+static inline unsigned long long* spx_sync_team(spx_ctx* ctx) {
+  return reinterpret_cast<unsigned long long*>(static_cast<char*>(ctx->sync) + kSpxSyncTeamOffset);
+}
 
 // Every wait of one workgroup for others is bounded: kSpxPollLimit polls (each a memory round trip plus a short sleep: a few
 // seconds in all, against microseconds of legitimate waiting).  A workgroup that gives up sets SpxSyncHeader::timed_out,

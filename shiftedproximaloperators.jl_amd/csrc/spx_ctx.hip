@@ -46,6 +46,52 @@ void spx_set_error(const char* fmt, ...) {
 SPX_EXPORT int spx_abi_version(void) { return SPX_ABI_VERSION; }
 SPX_EXPORT const char* spx_last_error(void) { return g_err; }
 
+// The synchronisation state back to its initial state: zero, its header pointing at the status word, and the host's view of
+// its sets reset.  Synchronises the stream: no launch still uses the block when this returns.
+static int sync_init(spx_ctx* ctx) {
+  SPX_HIP(hipMemsetAsync(ctx->sync, 0, kSpxSyncBytes, ctx->stream));
+  SPX_HIP(hipMemcpyAsync(&spx_sync_header(ctx)->status, &ctx->status_dev, sizeof(int*), hipMemcpyHostToDevice, ctx->stream));
+  SPX_HIP(hipStreamSynchronize(ctx->stream));
+  ctx->track = spx_ctx::SyncTrack{};
+  return SPX_OK;
+}
+
+// Called when the context is created, or later by spx_sync_ready if its stream was being captured then.
+int spx_sync_alloc(spx_ctx* ctx) {
+  { const int rc = spx_require_not_capturing(ctx, "allocating the synchronisation state"); if (rc) return rc; }
+  SPX_ON_DEVICE_RAW(ctx);
+  const hipError_t e = hipMalloc(&ctx->sync, kSpxSyncBytes);
+  if (e != hipSuccess) {
+    ctx->sync = nullptr;
+    spx_set_error("sync-state hipMalloc(%zu) failed: %s", kSpxSyncBytes, hipGetErrorString(e));
+    return SPX_ERR_ALLOC;
+  }
+  const int rc = sync_init(ctx);
+  if (rc) {
+    (void)hipFree(ctx->sync);
+    ctx->sync = nullptr;
+  }
+  return rc;
+}
+
+// Frees whatever the context holds (all of it, or what a failed creation got to) and the context itself.  The caller has
+// drained the stream and accounted for the context in g_ctx_count.
+static void ctx_release(spx_ctx* c) {
+  if (c->ws) (void)hipFree(c->ws);
+  if (c->sync) (void)hipFree(c->sync);
+  if (c->stage) (void)hipFree(c->stage);
+  for (int k = 0; k < c->nretired; ++k) (void)hipFree(c->retired[k]);
+  if (c->status_host) (void)hipHostFree(const_cast<int*>(c->status_host));
+  if (c->ev_start) (void)hipEventDestroy(c->ev_start);
+  if (c->ev_stop) (void)hipEventDestroy(c->ev_stop);
+  if (c->owns_stream) (void)hipStreamDestroy(c->stream);
+  {
+    std::lock_guard<std::mutex> lk(g_coop_mu);
+    if (g_coop_last[c->device & 63] == c) g_coop_last[c->device & 63] = nullptr;
+  }
+  delete c;
+}
+
 static int ctx_create_impl(int device, bool borrow, void* stream, spx_ctx** out) {
   SPX_REQUIRE(out != nullptr, "out is NULL");
   *out = nullptr;
@@ -67,22 +113,20 @@ static int ctx_create_impl(int device, bool borrow, void* stream, spx_ctx** out)
   spx_ctx* c = new spx_ctx();
   c->device = device;
   c->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+  auto fail = [c](int rc) { ctx_release(c); return rc; };
   if (borrow) {
     c->stream = reinterpret_cast<hipStream_t>(stream);
-    c->owns_stream = false;
   } else {
     hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
-      delete c;
       spx_set_error("hipStreamCreateWithFlags failed: %s", hipGetErrorString(e));
-      return SPX_ERR_HIP;
+      return fail(SPX_ERR_HIP);
     }
     c->owns_stream = true;
   }
   if (hipEventCreate(&c->ev_start) != hipSuccess || hipEventCreate(&c->ev_stop) != hipSuccess) {
     spx_set_error("hipEventCreate failed");
-    delete c;
-    return SPX_ERR_HIP;
+    return fail(SPX_ERR_HIP);
   }
   {  // the device-side status word: host-mapped pinned memory, so that the host sees a kernel's report without any copy
     void* hp = nullptr;
@@ -90,15 +134,19 @@ static int ctx_create_impl(int device, bool borrow, void* stream, spx_ctx** out)
     if (hipHostMalloc(&hp, 64, hipHostMallocMapped) != hipSuccess || hipHostGetDevicePointer(&dp, hp, 0) != hipSuccess) {
       spx_set_error("hipHostMalloc(mapped) for the status word failed");
       if (hp) (void)hipHostFree(hp);
-      (void)hipEventDestroy(c->ev_start);
-      (void)hipEventDestroy(c->ev_stop);
-      if (c->owns_stream) (void)hipStreamDestroy(c->stream);
-      delete c;
-      return SPX_ERR_ALLOC;
+      return fail(SPX_ERR_ALLOC);
     }
     std::memset(hp, 0, 64);
     c->status_host = static_cast<volatile int*>(hp);
     c->status_dev = static_cast<int*>(dp);
+  }
+  // the synchronisation state -- unless the stream is being captured (no memset, no synchronisation inside a capture): then
+  // the first call that needs it allocates it (spx_sync_ready)
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(c->stream, &cs) != hipSuccess) (void)hipGetLastError();
+  if (cs == hipStreamCaptureStatusNone) {
+    const int rc = spx_sync_alloc(c);
+    if (rc) return fail(rc);
   }
   g_ctx_count[device & 63].fetch_add(1);
   *out = c;
@@ -114,20 +162,8 @@ SPX_EXPORT int spx_ctx_destroy(spx_ctx* ctx) {
   if (!ctx) return SPX_OK;
   SpxDeviceGuard dev_guard(ctx->device);
   (void)hipStreamSynchronize(ctx->stream);
-  if (ctx->ws) (void)hipFree(ctx->ws);
-  if (ctx->sync) (void)hipFree(ctx->sync);
-  if (ctx->stage) (void)hipFree(ctx->stage);
-  for (int k = 0; k < ctx->nretired; ++k) (void)hipFree(ctx->retired[k]);
-  if (ctx->status_host) (void)hipHostFree(const_cast<int*>(ctx->status_host));
-  if (ctx->ev_start) (void)hipEventDestroy(ctx->ev_start);
-  if (ctx->ev_stop) (void)hipEventDestroy(ctx->ev_stop);
-  if (ctx->owns_stream) (void)hipStreamDestroy(ctx->stream);
   g_ctx_count[ctx->device & 63].fetch_sub(1);
-  {
-    std::lock_guard<std::mutex> lk(g_coop_mu);
-    if (g_coop_last[ctx->device & 63] == ctx) g_coop_last[ctx->device & 63] = nullptr;
-  }
-  delete ctx;
+  ctx_release(ctx);
   return SPX_OK;
 }
 
@@ -189,22 +225,9 @@ SPX_EXPORT int spx_sync(spx_ctx* ctx) {
   if (ctx->status_host != nullptr && *ctx->status_host != 0) {  // reported here once, then the context is usable again
     const int rc = spx_status_report(ctx);
     SPX_ON_DEVICE_RAW(ctx);
-    if (ctx->sync) {  // counters, histograms and exchange words of an abandoned launch: back to the initial state
-      SPX_HIP(hipMemset(ctx->sync, 0, ctx->sync_bytes));
-      SPX_HIP(hipMemcpy(&reinterpret_cast<SpxSyncHeader*>(ctx->sync)->status, &ctx->status_dev, sizeof(int*), hipMemcpyHostToDevice));
-      ctx->coop_parity = 0;
-      ctx->b2_set = 0;
-      ctx->b2_dirty_g[0] = ctx->b2_dirty_g[1] = 0;
-      ctx->team_set = 0;
-  ctx->grp_def_set = 0;
-      ctx->grp_def_set = 0;
-      ctx->sel_hist_next = 0;
-      ctx->sel_hist_dirty[0] = ctx->sel_hist_dirty[1] = 0;
-    }
-    // ... and the retired blocks a captured graph may still replay on (their sticky timed_out flag, counters, words)
-    for (int k = 0; k < ctx->nretired_sync; ++k) {
-      SPX_HIP(hipMemset(ctx->retired_sync[k], 0, ctx->retired_sync_bytes[k]));
-      SPX_HIP(hipMemcpy(&reinterpret_cast<SpxSyncHeader*>(ctx->retired_sync[k])->status, &ctx->status_dev, sizeof(int*), hipMemcpyHostToDevice));
+    if (ctx->sync) {  // counters, histograms and exchange words of an abandoned launch (the block a captured graph replays on
+      const int rz = sync_init(ctx);  // too: it never moves) back to the initial state
+      if (rz) return rz;
     }
     *ctx->status_host = 0;
     return rc;
@@ -323,49 +346,6 @@ int spx_ws_reserve(spx_ctx* ctx, size_t bytes) {
     return SPX_ERR_ALLOC;
   }
   ctx->ws_bytes = bytes;
-  return SPX_OK;
-}
-
-// Persistent zero-initialised device state (spx_ctx::sync).  Growing it re-zeroes everything: callers only rely on
-// "zero when no launch of mine is in flight", which holds again after the stream has been drained.
-int spx_sync_reserve(spx_ctx* ctx, size_t bytes) {
-  if (bytes <= ctx->sync_bytes) return SPX_OK;
-  { const int rc = spx_require_not_capturing(ctx, "growing the synchronisation state"); if (rc) return rc; }
-  SPX_ON_DEVICE_RAW(ctx);
-  SPX_HIP(hipStreamSynchronize(ctx->stream));
-  if (ctx->sync) {
-    if (ctx->graph_safe) {  // (as spx_ws_reserve: a captured graph may still point into the old block)
-      if (ctx->nretired >= 64) {
-        spx_set_error("invalid argument: the synchronisation state of a captured context cannot grow any further");
-        return SPX_ERR_INVALID_ARG;
-      }
-      ctx->retired[ctx->nretired++] = ctx->sync;
-      if (ctx->nretired_sync < 16) {
-        ctx->retired_sync[ctx->nretired_sync] = ctx->sync;
-        ctx->retired_sync_bytes[ctx->nretired_sync++] = ctx->sync_bytes;
-      }
-    } else {
-      SPX_HIP(hipFree(ctx->sync));
-    }
-  }
-  ctx->sync = nullptr;
-  ctx->sync_bytes = 0;
-  hipError_t e = hipMalloc(&ctx->sync, bytes);
-  if (e != hipSuccess) {
-    spx_set_error("sync-state hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
-    return SPX_ERR_ALLOC;
-  }
-  SPX_HIP(hipMemsetAsync(ctx->sync, 0, bytes, ctx->stream));
-  SPX_HIP(hipMemcpyAsync(&reinterpret_cast<SpxSyncHeader*>(ctx->sync)->status, &ctx->status_dev, sizeof(int*), hipMemcpyHostToDevice, ctx->stream));
-  SPX_HIP(hipStreamSynchronize(ctx->stream));
-  ctx->sync_bytes = bytes;
-  ctx->coop_parity = 0;
-  ctx->b2_set = 0;
-  ctx->b2_dirty_g[0] = ctx->b2_dirty_g[1] = 0;
-  ctx->team_set = 0;
-  ctx->grp_def_set = 0;
-  ctx->sel_hist_next = 0;
-  ctx->sel_hist_dirty[0] = ctx->sel_hist_dirty[1] = 0;
   return SPX_OK;
 }
 
@@ -491,7 +471,7 @@ SPX_EXPORT int spx_synth_fill(spx_ctx* ctx, double* out, int64_t n, uint64_t see
 SPX_EXPORT int spx_debug_peek(spx_ctx* ctx, int which, size_t offset, size_t nbytes, void* out) {
   SPX_REQUIRE(ctx != nullptr && out != nullptr, "NULL argument");
   const char* base = static_cast<const char*>(which ? ctx->sync : ctx->ws);
-  const size_t cap = which ? ctx->sync_bytes : ctx->ws_bytes;
+  const size_t cap = which ? kSpxSyncBytes : ctx->ws_bytes;
   SPX_REQUIRE(base != nullptr && offset + nbytes <= cap, "range outside the buffer");
   SPX_ON_DEVICE_RAW(ctx);
   SPX_HIP(hipStreamSynchronize(ctx->stream));

@@ -576,14 +576,14 @@ static int run_group(spx_ctx* ctx, double* y, const double* q, const double* xk,
       // two words of the synchronisation state (zero-initialised, never written by another operator): a call uses [set], its
       // LIT launch -- queued unconditionally behind the main one -- zeroes [set ^ 1] for the next call.  Under a stream capture
       // (one set would replay for ever) and for ragged layouts the word in front of the list and its zero-fill node stay.
-      const bool graph_safe = spx_capture_check(ctx) || ctx->graph_safe;
+      const bool graph_safe = spx_graph_safe(ctx);
       if (BINF && !ragged_reg && ctx->tune_fewer_launches && !graph_safe) {
-        rc = spx_sync_reserve(ctx, sizeof(SpxSyncHeader));
+        rc = spx_sync_ready(ctx);
         if (rc) return rc;
-        SpxSyncHeader* hdr = reinterpret_cast<SpxSyncHeader*>(ctx->sync);
-        dcount = reinterpret_cast<unsigned long long*>(&hdr->grp_deferred[ctx->grp_def_set]);
-        dclear = reinterpret_cast<unsigned long long*>(&hdr->grp_deferred[ctx->grp_def_set ^ 1]);
-        ctx->grp_def_set ^= 1;
+        SpxSyncHeader* hdr = spx_sync_header(ctx);
+        dcount = reinterpret_cast<unsigned long long*>(&hdr->grp_deferred[ctx->track.grp_def_set]);
+        dclear = reinterpret_cast<unsigned long long*>(&hdr->grp_deferred[ctx->track.grp_def_set ^ 1]);
+        ctx->track.grp_def_set ^= 1;
       } else {
         rc = spx_zero_async(ctx, deferred, sizeof(long long)); if (rc) return rc;
       }

@@ -976,7 +976,7 @@ int spx_group_team_plan(spx_ctx* ctx, bool binf, const double* y, const double* 
   if (rc) return rc;
   rc = spx_ws_reserve(ctx, L.plan_bytes + L.status_bytes + L.cand_bytes + 256);
   if (rc) return rc;
-  rc = spx_sync_reserve(ctx, kSpxSyncTeamOffset + kSpxSyncTeamBytes);
+  rc = spx_sync_ready(ctx);  // (for spx_group_team_launch: refused, if at all, before anything is enqueued)
   if (rc) return rc;
   TeamPlanHdr* plan = reinterpret_cast<TeamPlanHdr*>(ctx->ws);
   TeamJob* jobs = reinterpret_cast<TeamJob*>(static_cast<char*>(ctx->ws) + sizeof(TeamPlanHdr));
@@ -994,23 +994,23 @@ int spx_group_team_launch(spx_ctx* ctx, bool binf, double* y, const double* q, c
   if (rc) return rc;
   rc = spx_ws_reserve(ctx, L.plan_bytes + L.status_bytes + L.cand_bytes + 256);  // (after spx_group_team_plan: the same size, nothing moves)
   if (rc) return rc;
-  rc = spx_sync_reserve(ctx, kSpxSyncTeamOffset + kSpxSyncTeamBytes);
+  rc = spx_sync_ready(ctx);
   if (rc) return rc;
   char* ws = static_cast<char*>(ctx->ws);
   const TeamPlanHdr* plan = offsets ? reinterpret_cast<const TeamPlanHdr*>(ws) : nullptr;
   const TeamJob* jobs = offsets ? reinterpret_cast<const TeamJob*>(ws + sizeof(TeamPlanHdr)) : nullptr;
   int* job_status = reinterpret_cast<int*>(ws + L.plan_bytes);
   f64x2* cand = L.cand_bytes ? reinterpret_cast<f64x2*>(ws + L.plan_bytes + L.status_bytes) : nullptr;
-  SpxSyncHeader* hdr = reinterpret_cast<SpxSyncHeader*>(ctx->sync);
-  unsigned long long* sets = reinterpret_cast<unsigned long long*>(static_cast<char*>(ctx->sync) + kSpxSyncTeamOffset);
+  SpxSyncHeader* hdr = spx_sync_header(ctx);
+  unsigned long long* sets = spx_sync_team(ctx);
   unsigned int* ctrs = reinterpret_cast<unsigned int*>(sets + 2 * kGtSetWords);  // two sets of kGtCols tile counters
-  const bool graph_safe = spx_capture_check(ctx) || ctx->graph_safe;  // (see spx_ctx::graph_safe)
+  const bool graph_safe = spx_graph_safe(ctx);
   // which forms can occur: uniform groups are all alike; a device-side plan may hold both kinds
   const bool chip_possible = offsets ? true : gsize <= (int64_t)L.Wu * kTmChipElems;
   const bool stream_possible = offsets ? true : !chip_possible;
   const bool fast = binf && ctx->tune_team_fast && cand != nullptr;
   auto launch = [&](int form) -> int {
-    int use = ctx->team_set, other = use ^ 1;
+    int use = ctx->track.team_set, other = use ^ 1;
     if (graph_safe) {  // set 0 (words and counters), zeroed by nodes in front of the launch; nothing alternates
       use = 0;
       other = 1;
@@ -1044,7 +1044,7 @@ int spx_group_team_launch(spx_ctx* ctx, bool binf, double* y, const double* q, c
 #undef SPX_TEAM_LAUNCH_BV
 #undef SPX_TEAM_LAUNCH
     }
-    if (!graph_safe) ctx->team_set = other;
+    if (!graph_safe) ctx->track.team_set = other;
     SPX_LAUNCH_CHECK();
     return SPX_OK;
   };

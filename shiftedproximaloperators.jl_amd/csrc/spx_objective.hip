@@ -516,13 +516,13 @@ int obj_finish(spx_ctx* ctx, ObjWs* ws, int blocks, int rule, double scale, doub
   return SPX_OK;
 }
 
-// The one-launch form (ObjFin): needs the synchronisation state's header; not while a stream capture has to allocate it.
+// The one-launch form (ObjFin) keeps its tickets in the synchronisation state's header.
 int obj_fin_prepare(spx_ctx* ctx, int rule, double scale, double limit, ObjFin* fin) {
   *fin = ObjFin{nullptr, ctx->value_target, scale, limit, rule};
   if (!ctx->tune_fewer_launches) return SPX_OK;
-  const int rc = spx_sync_reserve(ctx, sizeof(SpxSyncHeader));
+  const int rc = spx_sync_ready(ctx);
   if (rc) return rc;
-  fin->hdr = reinterpret_cast<SpxSyncHeader*>(ctx->sync);
+  fin->hdr = spx_sync_header(ctx);
   return SPX_OK;
 }
 

@@ -2388,13 +2388,13 @@ enum class SelForm { kCoopReg, kCoopMem, kLds, kLdsRegX };
 template <bool BINF, class T>
 int launch_sel_exact(spx_ctx* ctx, SelForm form, bool vec, int64_t g, T* y, const T* q, const T* xk, const T* sj, int64_t n,
                      int64_t r, T delta) {
-  int rc = spx_sync_reserve(ctx, sizeof(SelSync));
+  int rc = spx_sync_ready(ctx);
   if (rc) return rc;
   SelSync* ss = reinterpret_cast<SelSync*>(ctx->sync);
-  const bool graph_safe = spx_capture_check(ctx) || ctx->graph_safe;  // (see spx_ctx::graph_safe)
-  int use_set = ctx->sel_hist_next, other = use_set ^ 1;
-  int clear_set = ctx->sel_hist_dirty[other] ? other : -1;
-  int parity = ctx->coop_parity;
+  const bool graph_safe = spx_graph_safe(ctx);
+  int use_set = ctx->track.sel_hist_next, other = use_set ^ 1;
+  int clear_set = ctx->track.sel_hist_dirty[other] ? other : -1;
+  int parity = ctx->track.coop_parity;
   if (graph_safe) {  // the counters and histogram set 0, zeroed by a node in front of the launch; nothing alternates
     rc = spx_zero_async(ctx, &ss->hdr, sizeof(ss->hdr.bar));
     if (rc) return rc;
@@ -2415,12 +2415,12 @@ int launch_sel_exact(spx_ctx* ctx, SelForm form, bool vec, int64_t g, T* y, cons
                        clear_set);
   }
   if (graph_safe) {  // whatever the host believed about the sets no longer holds: both count as used
-    ctx->sel_hist_dirty[0] = ctx->sel_hist_dirty[1] = 1;
+    ctx->track.sel_hist_dirty[0] = ctx->track.sel_hist_dirty[1] = 1;
   } else {
-    ctx->coop_parity ^= 1;
-    ctx->sel_hist_dirty[use_set] = 1;
-    ctx->sel_hist_dirty[other] = 0;
-    ctx->sel_hist_next = other;
+    ctx->track.coop_parity ^= 1;
+    ctx->track.sel_hist_dirty[use_set] = 1;
+    ctx->track.sel_hist_dirty[other] = 0;
+    ctx->track.sel_hist_next = other;
   }
   SPX_LAUNCH_CHECK();
   return SPX_OK;
@@ -2431,10 +2431,10 @@ int launch_sel_exact(spx_ctx* ctx, SelForm form, bool vec, int64_t g, T* y, cons
 template <bool BINF>
 int run_select_fast(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n, int64_t r,
                     double delta, int ioff, int spl) {
-  int rc = spx_sync_reserve(ctx, sizeof(SelSync));
+  int rc = spx_sync_ready(ctx);
   if (rc) return rc;
   SelSync* ss = reinterpret_cast<SelSync*>(ctx->sync);
-  const bool graph_safe = spx_capture_check(ctx) || ctx->graph_safe;  // (see spx_ctx::graph_safe)
+  const bool graph_safe = spx_graph_safe(ctx);
   const int64_t cap_tail = spx_resident_cap(ctx, reinterpret_cast<const void*>(&k_s2_tail<BINF>), 1024, 0);
   if (cap_tail < 1) return SPX_ERR_INTERNAL;
   const int64_t g_tail = cap_tail < 256 ? (cap_tail < ctx->num_cu ? cap_tail : ctx->num_cu) : (ctx->num_cu < 256 ? ctx->num_cu : 256);  // (<= 256: SelSync::tie_part)
@@ -2479,23 +2479,23 @@ int run_select_fast(spx_ctx* ctx, double* y, const double* q, const double* xk, 
     if (rc) return rc;
     rc = spx_zero_async(ctx, &ss->fhist1[0], sizeof(SelSync) - offsetof(SelSync, fhist1));
     if (rc) return rc;
-    ctx->coop_parity = 0;
+    ctx->track.coop_parity = 0;
   }
   {
     SpxCoopLaunchGuard guard(ctx);
     if (spl == 16)
       hipLaunchKernelGGL(k_s2_front<16>, dim3(kFrontBlocks), dim3(1024), 0, ctx->stream, q + ioff, xk + ioff, sj + ioff,
-                         n - ioff, r, ss, ctx->coop_parity);
+                         n - ioff, r, ss, ctx->track.coop_parity);
     else if (spl == 4)
       hipLaunchKernelGGL(k_s2_front<4>, dim3(kFrontBlocks), dim3(1024), 0, ctx->stream, q + ioff, xk + ioff, sj + ioff,
-                         n - ioff, r, ss, ctx->coop_parity);
+                         n - ioff, r, ss, ctx->track.coop_parity);
     else if (spl == 2)
       hipLaunchKernelGGL(k_s2_front<2>, dim3(kFrontBlocks), dim3(1024), 0, ctx->stream, q + ioff, xk + ioff, sj + ioff,
-                         n - ioff, r, ss, ctx->coop_parity);
+                         n - ioff, r, ss, ctx->track.coop_parity);
     else
       hipLaunchKernelGGL(k_s2_front<1>, dim3(kFrontBlocks), dim3(1024), 0, ctx->stream, q + ioff, xk + ioff, sj + ioff,
-                         n - ioff, r, ss, ctx->coop_parity);
-    ctx->coop_parity ^= 1;
+                         n - ioff, r, ss, ctx->track.coop_parity);
+    ctx->track.coop_parity ^= 1;
     if (write)
       hipLaunchKernelGGL((k_s2_main<BINF, true>), mgrid, dim3(256), 0, ctx->stream, y + ioff, q + ioff, xk + ioff,
                          sj + ioff, n - ioff, sws, cand, counts, delta, ioff, ccap, ovf_cap, cls, nregions);
@@ -2518,9 +2518,9 @@ int run_select_fast(spx_ctx* ctx, double* y, const double* q, const double* xk, 
                          (const int64_t*)lidx, (const double*)lval, xk, sj, delta);
     }
     hipLaunchKernelGGL((k_s2_tail<BINF>), dim3((unsigned)g_tail), dim3(1024), 0, ctx->stream, y, q, xk, sj, n, r, delta, ss,
-                       ctx->coop_parity, (const Cand*)cand, (const WaveCount*)counts, nregions, ovf_cap,
+                       ctx->track.coop_parity, (const Cand*)cand, (const WaveCount*)counts, nregions, ovf_cap,
                        (const ClassCount*)cls, ioff, (write ? 1 : 0) | tail_hook);
-    ctx->coop_parity ^= 1;
+    ctx->track.coop_parity ^= 1;
   }
   if (!write)
     hipLaunchKernelGGL((k_sel_final_q<BINF>), dim3((unsigned)((n2 + 1535) / 1536)), dim3(256), 0, ctx->stream,

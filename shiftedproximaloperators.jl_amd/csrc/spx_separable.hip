@@ -816,7 +816,7 @@ static int run_separable(spx_ctx* ctx, double* y, const double* q, const double*
     if (rcw) return rcw;
     partials = reinterpret_cast<double*>(static_cast<char*>(ctx->ws) + 256);
     if (ctx->tune_fewer_launches) {  // (the one-launch form keeps its tickets in the synchronisation state)
-      rcw = spx_sync_reserve(ctx, sizeof(SpxSyncHeader));
+      rcw = spx_sync_ready(ctx);
       if (rcw) return rcw;
     }
   }
@@ -860,7 +860,7 @@ static int run_separable(spx_ctx* ctx, double* y, const double* q, const double*
       op.partials = partials + used;
       // one launch covers the whole vector (no peeled element in front, no odd element behind): it may finish the value
       if (ctx->tune_fewer_launches && head == 0 && 2 * n2 == n) {
-        fh = reinterpret_cast<const SpxSyncHeader*>(ctx->sync);
+        fh = spx_sync_header(ctx);
         op.fin_result = reinterpret_cast<double*>(ctx->ws);
         op.fin_target = ctx->value_target;
         op.fin_scale = value_scale;

@@ -159,6 +159,147 @@ def test_one_group_over_the_vector_in_a_graph(s, orc, n):
             assert got == vr or abs(got - vr) <= 1e-12 * abs(vr), (rep, k, got, vr)
 
 
+def _private_context(s, stream):
+    """A context of our own on `stream`, never shared with another test through the per-stream cache of the Python layer."""
+    import ctypes
+    L = s._lib.load()
+    ctx = ctypes.c_void_p()
+    s._lib.check(L.spx_ctx_create_on_stream(0, ctypes.c_void_p(stream.cuda_stream), ctypes.byref(ctx)))
+    return L, ctx
+
+
+def test_one_launch_values_capture_on_a_context_that_never_synchronised_in_a_launch(s):
+    """psi(y) and prox_value in their one-launch forms (tuning key 17 = 1: tickets in the synchronisation state) captured on a
+    context whose workspace is warm but which has never run a kernel that synchronises inside one launch: the state exists
+    from spx_ctx_create on, so the capture works; replays on new data give the eager one-launch values bit for bit."""
+    import ctypes
+    import torch
+    n = 50_000
+    rng = np.random.default_rng(41)
+    side = torch.cuda.Stream()
+    L, ctx = _private_context(s, side)
+    D = ctypes.c_double
+    try:
+        with torch.cuda.stream(side):
+            xd = torch.from_numpy(rng.normal(size=n)).cuda(); sd = torch.from_numpy(rng.uniform(-0.5, 0.5, size=n)).cuda()
+            yin = torch.zeros(n, dtype=torch.float64, device="cuda"); qd = torch.zeros_like(yin); yv = torch.zeros_like(yin)
+            vals = [torch.zeros(1, dtype=torch.float64, device="cuda") for _ in range(2)]
+            host = D(0.0)
+
+            def obj():
+                return L.spx_obj_l1(ctx, yin.data_ptr(), xd.data_ptr(), sd.data_ptr(), n, D(0.7), ctypes.byref(host))
+
+            def proxval():
+                return L.spx_proxval_l1(ctx, yv.data_ptr(), qd.data_ptr(), xd.data_ptr(), sd.data_ptr(), n, D(0.7), D(1.1),
+                                        D(-0.9), ctypes.byref(host))
+
+            def captured():
+                s._lib.check(L.spx_ctx_set_value_target(ctx, ctypes.c_void_p(vals[0].data_ptr())))
+                s._lib.check(obj())
+                s._lib.check(L.spx_ctx_set_value_target(ctx, ctypes.c_void_p(vals[1].data_ptr())))
+                s._lib.check(proxval())
+                s._lib.check(L.spx_ctx_set_value_target(ctx, None))
+
+            yin.copy_(torch.from_numpy(rng.uniform(-0.3, 0.3, size=n))); qd.copy_(torch.from_numpy(rng.normal(size=n)))
+            s._lib.check(L.spx_ctx_set_tuning(ctx, 17, 0))   # the launches of rounds 1-3: the workspace reaches its size
+            captured()
+            s._lib.check(L.spx_ctx_set_tuning(ctx, 17, 1))
+        side.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=side):
+            captured()
+        for rep in range(3):
+            with torch.cuda.stream(side):
+                yin.copy_(torch.from_numpy(rng.uniform(-0.3, 0.3, size=n) * (1.0 + rep)))
+                qd.copy_(torch.from_numpy(rng.normal(size=n) * (1.0 + rep)))
+                yv.fill_(-777.0)
+                for v in vals:
+                    v.fill_(-1.0)
+                g.replay()
+            side.synchronize()
+            got = [float(v.item()) for v in vals]
+            got_y = yv.clone()
+            with torch.cuda.stream(side):             # the eager one-launch values on the same data, read back to the host
+                s._lib.check(obj())
+                want_obj = host.value
+                s._lib.check(proxval())
+                want_pv = host.value
+            side.synchronize()
+            assert got[0] == want_obj and got[1] == want_pv, (rep, got, want_obj, want_pv)
+            assert torch.equal(got_y.view(torch.int64), yv.view(torch.int64)), rep
+    finally:
+        side.synchronize()
+        L.spx_ctx_destroy(ctx)
+
+
+def test_replays_between_operators_that_used_to_grow_the_synchronisation_state(s, orc):
+    """One context runs psi(y), then top-r, then ShiftedNormL1B2, then one group over the vector -- the order in which the
+    synchronisation state used to be reallocated three times.  A graph of the first call, captured before the others, is
+    replayed after each of them: bit for bit the eager value, and every operator matches the oracle as in the tests above."""
+    import ctypes
+    import torch
+    n = 300_000
+    rng = np.random.default_rng(43)
+    x = rng.normal(size=n); sj = rng.uniform(-0.5, 0.5, size=n); q = rng.normal(size=n)
+    side = torch.cuda.Stream()
+    L, ctx = _private_context(s, side)
+    D = ctypes.c_double
+    try:
+        with torch.cuda.stream(side):
+            xd, sd, qd = (torch.from_numpy(t).cuda() for t in (x, sj, q))
+            yin = torch.from_numpy(rng.uniform(-0.3, 0.3, size=n)).cuda()
+            y = torch.empty_like(qd)
+            val = torch.zeros(1, dtype=torch.float64, device="cuda")
+            lam = torch.tensor([0.4 * n ** 0.5], dtype=torch.float64, device="cuda")
+            host = D(0.0)
+
+            def obj():
+                return L.spx_obj_l1(ctx, yin.data_ptr(), xd.data_ptr(), sd.data_ptr(), n, D(0.7), ctypes.byref(host))
+
+            s._lib.check(obj())
+            want = host.value
+        side.synchronize()
+        s._lib.check(L.spx_ctx_set_value_target(ctx, ctypes.c_void_p(val.data_ptr())))
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=side):
+            s._lib.check(obj())
+        s._lib.check(L.spx_ctx_set_value_target(ctx, None))
+
+        def replay(what):
+            side.synchronize()
+            with torch.cuda.stream(side):
+                val.fill_(-1.0)
+                g.replay()
+            side.synchronize()
+            assert float(val.item()) == want, (what, float(val.item()), want)
+
+        def call(what, rc):
+            side.synchronize()
+            s._lib.check(rc)
+            side.synchronize()
+            replay(what)
+            return y.cpu().numpy()
+
+        replay("psi(y)")
+        r = n // 20
+        got = call("top-r", L.spx_prox_indball_l0_binf(ctx, y.data_ptr(), qd.data_ptr(), xd.data_ptr(), sd.data_ptr(), n, r, D(0.7)))
+        assert _bits(got, orc.prox_indball_l0_binf(q, x, sj, r, 0.7))
+        got = call("B2", L.spx_prox_l1_b2(ctx, y.data_ptr(), qd.data_ptr(), xd.data_ptr(), sd.data_ptr(), n, D(1.0), D(1.0), D(1.0), D(1.0)))
+        ref = orc.prox_l1_b2(q, x, sj, 1.0, 1.0, 1.0, 1.0)
+        assert np.max(np.abs(got - ref)) <= 1e-12 * max(np.linalg.norm(ref), np.linalg.norm(x))
+        got = call("one group", L.spx_prox_group_l2_binf(ctx, y.data_ptr(), qd.data_ptr(), xd.data_ptr(), sd.data_ptr(), n, None, n, 1,
+                                                          lam.data_ptr(), D(0.9), D(0.8)))
+        ref = orc.prox_group_l2_binf(q, x, sj, [float(lam[0])], 0.9, 0.8, offsets=np.array([0, n], dtype=np.int64))
+        scale = np.maximum(np.maximum(np.abs(ref), np.abs(x + sj)), np.linalg.norm((q + x) + sj))
+        assert float(np.max(np.abs(got - ref) / scale)) <= 1e-12
+        with torch.cuda.stream(side):
+            s._lib.check(obj())
+        assert host.value == want
+    finally:
+        side.synchronize()
+        L.spx_ctx_destroy(ctx)
+
+
 def test_calls_that_synchronise_refuse_to_be_captured(s):
     import torch
     n = 10_000
