@@ -7,7 +7,7 @@ calls it.  b is zero on 90 % of the groups, so after the first steps most groups
 sigma*lambda above ||S|| -- the reversed-bracket regime of the reference's root find.  The point of the
 example: the per-iteration prox! time stays at the bandwidth figure while the iterate becomes sparse.
 
-    gpurun -- 'python examples/tr_group_lasso.py'
+    python examples/tr_group_lasso.py [groups]
 """
 import ctypes
 import os
@@ -32,18 +32,24 @@ sj = torch.zeros_like(xk)
 delta, nu = 1.0, 0.5
 psi = s.shifted(s.shifted(h, xk, delta, s.NormLinf(1.0)), sj)
 step = torch.empty_like(xk); q = torch.empty_like(xk)
-obj = lambda: 0.5 * float(torch.dot(xk - b, xk - b)) + float((lam * xk.view(ng, gs).norm(dim=1)).sum())
 torch.mul(xk - b, -nu, out=q)
-s.prox_bang(step, psi, q, nu)                        # untimed first call: the context allocates its scratch here
-print("it   objective      zero groups   prox! ms")
+s.prox_bang(step, psi, q, nu)                        # untimed first calls: the context allocates its scratch here
+s.prox_value_bang(step, psi, q, nu)
+print("it   objective      zero groups   prox! ms   prox!+h ms")
 for it in range(25):
     torch.mul(xk - b, -nu, out=q)                                                   # q = -nu grad f(xk)
     ms = ctypes.c_float(); L.spx_timer_start(ctx)
     s.prox_bang(step, psi, q, nu)
     L.spx_timer_stop(ctx, ctypes.byref(ms))
+    # the same step once more, fused with the regulariser at the new iterate: h(xk + sj + step), sj = 0 -- the launch that
+    # stores the step also returns sum_g lambda_g ||(xk + step)_g|| (spx_proxval_group_l2_binf; no pass over xk on the side)
+    msv = ctypes.c_float(); L.spx_timer_start(ctx)
+    _, hval = s.prox_value_bang(step, psi, q, nu)
+    L.spx_timer_stop(ctx, ctypes.byref(msv))
     xk.add_(step)                                                                   # psi borrows xk: re-centred in place
     zero_groups = int((xk.view(ng, gs).abs().amax(dim=1) == 0).sum())
-    print("%2d   %.6e   %8d      %.3f" % (it, obj(), zero_groups, ms.value), flush=True)
+    obj = 0.5 * float(torch.dot(xk - b, xk - b)) + hval
+    print("%2d   %.6e   %8d      %.3f      %.3f" % (it, obj, zero_groups, ms.value, msv.value), flush=True)
     if float(step.abs().max()) < 1e-9:
         break
     delta = min(4.0 * delta, 64.0)                                                  # every step is a descent step here

@@ -401,6 +401,38 @@ int spx_prox_group_l2_binf(spx_ctx* ctx, double* y, const double* q, const doubl
                            int64_t group_size, int64_t ngroups, const double* lambda_vec,
                            double sigma, double delta);
 
+/* prox! fused with the value of h at the result, group forms -- the semantics of spx_proxval_* of the separable
+ * operators (above) on the pair a solver iteration makes on a group operator: `prox!(s, psi, -nu grad, nu)`, then `h(xk + s)`.
+ *   y      : bit-identical to spx_prox_group_l2[_binf] called on q_scale * q -- on every layout and route, with y aliasing q
+ *            exactly or not, with tuning key 9 at 0 or 1.  q_scale * q[i] is ONE rounded multiply (never contracted into
+ *            the `+ xk` that follows): the same bits as scaling q beforehand.  Pass 1.0 for q itself.
+ *   *value : sum over the groups of lambda_g * sqrt(sum_{i in g} v_i^2), v_i = (xk[i] + sj[i]) + y[i], formed from the
+ *            STORED y in the association of spx_obj_group_l2 -- i.e. what spx_obj_group_l2 returns on that y, up to the
+ *            order of the (non-negative) sums.  Indices inside no group contribute nothing.  The Binf form returns the
+ *            same h part only -- no IndBallLinf(1.1 Delta) scan, the convention of the Box forms of spx_proxval_*: the
+ *            prox lies inside the trust region by construction.  The partial sums are added in a fixed order:
+ *            reproducible run to run.
+ *   return : as spx_obj_*: without a device value target the call synchronises and writes the host double; with
+ *            spx_ctx_set_value_target the last kernel of the call stores the device double, *value is NaN and nothing
+ *            is read back.  Capturable under the conditions stated at spx_ctx_set_value_target (device value target, one
+ *            warm-up call, contiguous layouts).  n == 0 or ngroups == 0: value 0, y as the plain operator leaves it.
+ *            Argument checks as spx_prox_group_l2; value == NULL is SPX_ERR_INVALID_ARG, nothing launched.
+ * FUSED routes -- the value comes out of the launches that store y, no second sweep over the vectors: uniform groups of at
+ * most 512 elements and CSR offsets with a size bound (group_size) of at most 512, the register-tile kernels.  Uniform
+ * layouts: one launch (plain), two (Binf: the main launch and the launch over its deferred list, each adding the terms of
+ * the groups it stores).  CSR: plus the launch over the indices no group contains (plain) / the groups above the bound.
+ * COMPOSED routes -- every other layout (uniform groups above 512: LDS-resident groups, the general kernels, teams of
+ * workgroups incl. one group over the whole vector; CSR without such a bound): inside the same call, on the same stream and
+ * into the same value slot or target, y = q_scale * q (one elementwise launch, only where q_scale != 1), the unchanged
+ * prox at q := y, then the one-launch psi(y) of spx_obj_group_l2.  Same y bits, same value contract; 24 B/element more.
+ * There is no gather-index form. */
+int spx_proxval_group_l2(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
+                         const int64_t* group_offsets, int64_t group_size, int64_t ngroups, const double* lambda_vec,
+                         double sigma, double q_scale, double* value);
+int spx_proxval_group_l2_binf(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
+                              const int64_t* group_offsets, int64_t group_size, int64_t ngroups, const double* lambda_vec,
+                              double sigma, double delta, double q_scale, double* value);
+
 /* ShiftedGroupNormL2.prox! on Float32 vectors (round 3; the method is generic in R, src/shiftedGroupNormL2.jl:52-79): every
  * elementwise operation in Float32; the group norm is accumulated in Float64 and rounded once (the reference's `norm` is
  * BLAS / a generic loop: agreement to a few Float32 ulps of the operands, not bits).  Contiguous groups (uniform or CSR).

@@ -303,6 +303,40 @@ function prox!(y::DVec, ψ::ShiftedGroupNormL2Binf{Float64, RR, I, <:DVec, <:DVe
   group_call(y, ψ, q, σ, ψ.Δ)
 end
 
+# prox! fused with h at the result, group forms (spx_proxval_group_l2[_binf]; contiguous groups only: a gather layout throws).
+# One pass over the vectors for groups of at most 512 elements, the prox followed by ψ's reduction inside the call beyond.
+function group_value_call(y, ψ, q, σ, q_scale, extra...)   # extra = (Δ,) for the Binf form
+  n = length(ψ.xk)
+  (length(y) == n && length(q) == n) || throw(BoundsError())
+  L = layout_for(ψ.h, n)
+  L.gather && throw(ArgumentError("prox_value! needs contiguous groups"))
+  offp = L.offsets === nothing ? Ptr{Int64}(C_NULL) : Ptr{Int64}(UInt(pointer(L.offsets)))
+  out = Ref{Cdouble}(0.0)
+  if isempty(extra)
+    check(ccall((:spx_proxval_group_l2, libspx), Cint,
+                (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int64, Ptr{Int64}, Int64, Int64,
+                 Ptr{Cdouble}, Cdouble, Cdouble, Ptr{Cdouble}),
+                ctx(), dptr(y), dptr(q), dptr(ψ.xk), dptr(ψ.sj), n, offp, L.gsize, L.ngroups, dptr(L.lambda), σ, q_scale, out))
+  else
+    check(ccall((:spx_proxval_group_l2_binf, libspx), Cint,
+                (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int64, Ptr{Int64}, Int64, Int64,
+                 Ptr{Cdouble}, Cdouble, Cdouble, Cdouble, Ptr{Cdouble}),
+                ctx(), dptr(y), dptr(q), dptr(ψ.xk), dptr(ψ.sj), n, offp, L.gsize, L.ngroups, dptr(L.lambda), σ,
+                extra[1], q_scale, out))
+  end
+  return y, out[]
+end
+
+function prox_value!(y::DVec, ψ::ShiftedGroupNormL2{Float64, RR, I, <:DVec, <:DVec, <:DVec}, q::DVec, σ::Float64;
+                     q_scale::Float64 = 1.0) where {RR, I}
+  group_value_call(y, ψ, q, σ, q_scale)
+end
+
+function prox_value!(y::DVec, ψ::ShiftedGroupNormL2Binf{Float64, RR, I, <:DVec, <:DVec, <:DVec}, q::DVec, σ::Float64;
+                     q_scale::Float64 = 1.0) where {RR, I}
+  group_value_call(y, ψ, q, σ, q_scale, ψ.Δ)   # the h part of ψ(y): the prox lies inside the trust region
+end
+
 # ---------------------------------------------------------------------------------------------
 # ψ(y)                        src/ShiftedProximalOperators.jl:51-54, shiftedNormL1Box.jl:70-82 (idem L0Box, L½Box),
 #                             shiftedIndBallL0BInf.jl:44-49, shiftedGroupNormL2Binf.jl:34-39

@@ -13,6 +13,9 @@
 // per-group scalar arithmetic of the Binf root find (divisions, square roots), which every lane of a
 // group executes redundantly.  Other shapes: a wavefront or a 256-lane workgroup per group, elements
 // re-read from L1/L2 for every reduction.
+#include <limits>
+#include <type_traits>
+
 #include "spx_group_common.hpp"
 
 #ifdef SPX_DEBUG_PEEK  // diagnostic builds only: [0] last raw count the LIT launch read, [1] LIT launches that read a count
@@ -32,6 +35,151 @@ extern "C" __attribute__((visibility("default"))) int spx_debug_group_words(long
 
 
 // ---------------------------------------------------------------------------------------------
+// prox! fused with the value of h at the result (spx_proxval_group_l2[_binf]).  A launch that stores groups adds their terms
+// lambda_g * ||((xk + sj) + y)[g]|| into one partial sum per workgroup (one tile per wavefront: tens of thousands of them at
+// n = 1e8).  The call's LAST launch (hdr != NULL) finishes in two levels on the ticket words of the objective kernels
+// (SpxSyncHeader::fin_class / fin_top, the two halves of spx_fin_ticket): the workgroup that takes the last ticket of class j
+// (workgroups j, j + 8, ...) adds the partials j, j + 8, ... -- eight workgroups work side by side, every lane keeps eight loads in
+// flight -- and the one that takes the last of the eight top tickets adds the eight class sums.  Every sum has a fixed shape:
+// the value is reproducible run to run.  The ticket words reset themselves, so the same nodes replay in a graph.
+//   one launch (plain operator, uniform groups): the partials are the launch's own (agent-scope stores / loads);
+//   a launch behind the main one (Binf: the LIT launch; CSR: k_group_list_val): the partials are the finished main launch's.
+// Groups a main launch hands on (deferred list: Binf literal evaluation, ragged groups above the size bound) reach the launch
+// behind it in the order their atomics retired -- not a fixed one.  So that launch adds nothing up: it stores each group's term
+// in dterm[g]; the main launch leaves one 64-bit mask per wavefront tile (bit = the lane that handed a group on) and one flag per
+// workgroup (any); the class sums carry the number of flagged workgroups, and only when there is one does the last workgroup
+// walk the flags and add the terms of the flagged workgroups' tiles in group order -- after the partials, a fixed order whatever
+// the list looked like, and no work at all in the common case of an empty list.
+// ---------------------------------------------------------------------------------------------
+struct GroupNoVal {};
+struct GroupValWs {
+  double result;     // read back by the host
+  double cpart[8];   // class sums of the partials
+  double cany[8];    // ... and of the flags
+  double pad[15];    // (the partials start on a 256-byte boundary)
+};
+struct GroupVal {
+  double qs;           // q_scale: the prox is taken at qs * q
+  double* part;        // partial sums, one per workgroup of the (main) launch ...
+  double* any;         // ... and 1.0 where that workgroup handed a group on (NULL: this call has no list)
+  int nmain;           // workgroups of the main launch (a launch behind it: how many partials there are)
+  bool behind;         // this launch runs behind the main one: it adds the main launch's partials, has none of its own
+  SpxSyncHeader* hdr;  // non-NULL: this is the last launch of the call
+  GroupValWs* ws;
+  double* target;      // spx_ctx::value_target (may be NULL)
+  unsigned long long* dmask;  // [tile] (main launch: written; last launch: read for flagged workgroups)
+  double* dterm;              // [group]
+  int lpg_main;               // lanes per group of the main launch's tile (bit -> group)
+};
+// x[i0], x[i0 + step], ... (cnt of them) added by the workgroup: lane t takes the elements t, t + 256, ..., eight loads in flight
+template <bool ATOMIC>
+__device__ __forceinline__ double gval_strided_sum(const double* x, int64_t i0, int64_t step, int64_t cnt) {
+  double a = 0.0;
+  for (int64_t k0 = threadIdx.x; k0 < cnt; k0 += 256 * 8) {
+    double v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int64_t k = k0 + 256 * u;
+      const double* p = x + i0 + step * (k < cnt ? k : 0);
+      const double w = ATOMIC ? spx_atomic_load_f64(p) : *p;
+      v[u] = k < cnt ? w : 0.0;
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) a += v[u];
+  }
+  return a;
+}
+// `acc`: the lane's sum (non-zero in one lane per group); `handed`: this lane handed a group on.  Every lane of the (256-lane)
+// workgroup must call it.
+__device__ __forceinline__ void gval_finish(double acc, bool handed, const GroupVal& gv) {
+  __shared__ double gv_lds[4];
+  __shared__ int gv_flag;
+  auto block_sum = [&](double v) {
+    v = wave_sum(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) gv_lds[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (gv_lds[0] + gv_lds[1]) + (gv_lds[2] + gv_lds[3]);
+  };
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (this wavefront's dterm stores have left before its workgroup takes a ticket)
+  if (!gv.behind) {
+    acc = block_sum(acc);
+    if (gv.any != nullptr) {
+      const int any = __syncthreads_or(handed ? 1 : 0);
+      if (threadIdx.x == 0) gv.any[blockIdx.x] = any ? 1.0 : 0.0;
+    }
+    if (gv.hdr == nullptr) {
+      if (threadIdx.x == 0) gv.part[blockIdx.x] = acc;
+      return;
+    }
+  }
+  const unsigned int grid = gridDim.x, j = blockIdx.x % (unsigned)kSpxBarSplit;
+  const unsigned int classes = grid < (unsigned)kSpxBarSplit ? grid : (unsigned)kSpxBarSplit;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    if (!gv.behind) spx_atomic_store_f64(&gv.part[blockIdx.x], acc);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const unsigned int want = (grid - j + (unsigned)kSpxBarSplit - 1u) / (unsigned)kSpxBarSplit;  // workgroups j, j + 8, ...
+    const unsigned int c = __hip_atomic_fetch_add(&gv.hdr->fin_class[32u * j], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    gv_flag = (c + 1u == want) ? 1 : 0;
+    if (gv_flag) __hip_atomic_store(&gv.hdr->fin_class[32u * j], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __syncthreads();
+  if (!gv_flag) return;
+  // the last workgroup of class j: the partials j, j + classes, ... (and how many of their workgroups handed a group on)
+  const int64_t cnt = (int64_t)j < gv.nmain ? ((int64_t)gv.nmain - j + classes - 1) / classes : 0;
+  double a = gv.behind ? gval_strided_sum<false>(gv.part, j, classes, cnt) : gval_strided_sum<true>(gv.part, j, classes, cnt);
+  a = block_sum(a);
+  double f = 0.0;
+  if (gv.any != nullptr && gv.behind) f = block_sum(gval_strided_sum<false>(gv.any, j, classes, cnt));
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    spx_atomic_store_f64(&gv.ws->cpart[j], a);
+    spx_atomic_store_f64(&gv.ws->cany[j], f);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const unsigned int t = __hip_atomic_fetch_add(&gv.hdr->fin_top, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    gv_flag = (t + 1u == classes) ? 1 : 0;
+    if (gv_flag) __hip_atomic_store(&gv.hdr->fin_top, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __syncthreads();
+  if (!gv_flag) return;
+  // the last workgroup of the launch: the class sums in class order, then the handed-on groups (usually none)
+  __shared__ double gv_total[2];
+  if (threadIdx.x == 0) {
+    double v = 0.0, n = 0.0;
+    for (unsigned int c = 0; c < classes; ++c) {
+      v += spx_atomic_load_f64(&gv.ws->cpart[c]);
+      n += spx_atomic_load_f64(&gv.ws->cany[c]);
+    }
+    gv_total[0] = v;
+    gv_total[1] = n;
+  }
+  __syncthreads();
+  double total = gv_total[0];
+  if (gv_total[1] != 0.0) {  // (the same in every lane)
+    double d = 0.0;
+    const int gpw = 64 / gv.lpg_main;
+    for (int64_t b = threadIdx.x; b < gv.nmain; b += 256) {
+      if (gv.any[b] == 0.0) continue;
+      for (int w = 0; w < 4; ++w) {
+        unsigned long long m = gv.dmask[4 * b + w];
+        while (m) {
+          const int bit = __ffsll((long long)m) - 1;
+          m &= m - 1;
+          d += spx_atomic_load_f64(&gv.dterm[(4 * b + w) * gpw + bit / gv.lpg_main]);
+        }
+      }
+    }
+    total += block_sum(d);
+  }
+  if (threadIdx.x == 0) {
+    gv.ws->result = total;
+    if (gv.target) *gv.target = total;
+  }
+}
+__device__ __forceinline__ void gval_finish(double, bool, const GroupNoVal&) {}
+
+// ---------------------------------------------------------------------------------------------
 // fast path kernel: uniform groups of LPG*EPL elements; LPG lanes own a group, 64/LPG groups per wave;
 // the group is resident in registers.  Lane j of a group owns the 16-byte pairs j, j + LPG, j + 2 LPG, ...
 // ---------------------------------------------------------------------------------------------
@@ -43,7 +191,7 @@ extern "C" __attribute__((visibility("default"))) int spx_debug_group_words(long
 #endif
 #ifndef SPX_GROUP_WAVES
 #define SPX_GROUP_WAVES 3  // min waves/SIMD (VGPR cap) of the 8-element tiles.  Binf 1e6x128 on 16 lanes x 8: 3 (162 VGPRs, no spill) 0.84 ms; 4 (128, cold paths spill) 0.93 ms; 5: 1.49 ms
-// Binf tiles with 16 elements per lane (8 x 16 for 128-element groups: 8 groups per wave) run at 2 waves/SIMD (253 VGPRs):
+// Binf tiles with 16 elements per lane (8 x 16 for 128-element groups: 8 groups per wave) run at 2 waves/SIMD (220 VGPRs today; the figures in this comment are the compiler's at the time of each measurement):
 // the kernel is VALU-bound and the wave-uniform scalar work of the root find is shared by twice as many elements --
 // 0.79 -> 0.70 ms at 1e6 x 128 in spite of the lower occupancy.
 #endif
@@ -54,7 +202,12 @@ extern "C" __attribute__((visibility("default"))) int spx_debug_group_words(long
 // ids -- evaluating the reference's expressions literally on the register-resident group (binf_literal_reg).
 // FULL (PAIRS only): the group size is exactly LPG * EPL -- no pair of the tile is masked, which takes the zero-fill selects
 // and the clamped addresses (~7 % of the kernel's VALU instructions) out of the BASELINE shapes (128 = 8 x 16 = 16 x 8).
-template <int LPG, int EPL, bool BINF, bool PAIRS, bool LIT = false, bool FULL = false>
+// VALUE (spx_proxval_group_l2[_binf]): the prox is taken at gv.qs * q (one rounded multiply in front of `+ xk`), and the lane
+// that holds a group's y adds the group's term of h((xk + sj) + y) -- lambda_g * sqrt(sum of squares) over the STORED y, in the
+// association of k_obj_group MODE 0 -- into a per-lane sum that gval_finish turns into one partial per workgroup (GroupVal
+// above).  A group this launch does not store (deferred to the LIT launch / the list kernel) is counted by the launch that does.
+// VALUE = false: `gv` is an empty struct and none of this is compiled.
+template <int LPG, int EPL, bool BINF, bool PAIRS, bool LIT = false, bool FULL = false, bool VALUE = false>
 __global__ __launch_bounds__(256, (BINF && EPL >= 16) ? 2 : SPX_GROUP_WAVES) void k_group_reg(double* y_, const double* q_, const double* xk_, const double* sj_,
                                                     int64_t ngroups, int gsize, const double* __restrict__ lambda,
                                                     double sigma, double delta,
@@ -62,7 +215,8 @@ __global__ __launch_bounds__(256, (BINF && EPL >= 16) ? 2 : SPX_GROUP_WAVES) voi
                                                     const int64_t* __restrict__ offsets /* !PAIRS only: ragged groups */,
                                                     int* status /* spx_ctx::status_dev */, int pole_lit /* tuning key 9 */,
                                                     unsigned long long* dcount /* the list's count word: deferred[0], or one of SpxSyncHeader::grp_deferred */,
-                                                    unsigned long long* dclear /* LIT: the count word the NEXT call uses, zeroed here (or NULL) */) {
+                                                    unsigned long long* dclear /* LIT: the count word the NEXT call uses, zeroed here (or NULL) */,
+                                                    typename std::conditional<VALUE, GroupVal, GroupNoVal>::type gv) {
   static_assert((EPL % 2) == 0, "EPL must be even (16-byte pairs)");
   const int64_t GS = gsize;  // <= LPG * EPL
   constexpr int GPW = 64 / LPG;  // groups per wave
@@ -150,6 +304,8 @@ __global__ __launch_bounds__(256, (BINF && EPL >= 16) ? 2 : SPX_GROUP_WAVES) voi
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   };
+  bool handed_on = false;  // (VALUE) this lane put its group on the deferred list
+  double hsum = 0.0;  // (VALUE) lane 0 of each group's lanes: sum of lambda_g * ||((xk + sj) + y)[g]|| over the groups stored here
   for (int64_t g0 = wave * GPW; g0 < ntodo; g0 += nwaves * GPW) {  // wave-uniform trip count
     bool valid = (g0 + slot) < ntodo;
     const int64_t gi = valid ? (g0 + slot) : (ntodo - 1);  // idle slots shadow the last group, no store
@@ -169,7 +325,7 @@ __global__ __launch_bounds__(256, (BINF && EPL >= 16) ? 2 : SPX_GROUP_WAVES) voi
         base = offsets[g];
         const int64_t sz = offsets[g + 1] - base;
         if (sz > LPG * EPL || sz < 0) {  // the hint was wrong for this group: the general kernel takes it
-          if (valid && j == 0) deferred[1 + atomicAdd(dcount, 1ull)] = g;
+          if (valid && j == 0) { deferred[1 + atomicAdd(dcount, 1ull)] = g; handed_on = true; }
           valid = false;
           gs = 0;
         } else {
@@ -226,7 +382,9 @@ __global__ __launch_bounds__(256, (BINF && EPL >= 16) ? 2 : SPX_GROUP_WAVES) voi
         for (int k = 0; k < EPL / 2; ++k) {
           const bool in = FULL || (k * LPG + j) < npairs;
           const f64x2 zero2 = f64x2{0.0, 0.0};
-          const f64x2 a = in ? vq[k] : zero2, b = in ? vx[k] : zero2, c = in ? vs[k] : zero2;
+          f64x2 a = in ? vq[k] : zero2;
+          const f64x2 b = in ? vx[k] : zero2, c = in ? vs[k] : zero2;
+          if constexpr (VALUE) { a.x = gv.qs * a.x; a.y = gv.qs * a.y; }  // (rounded here: never contracted into the sum below)
           grp.S[2 * k] = (a.x + b.x) + c.x;  // shiftedGroupNormL2.jl:65 / shiftedGroupNormL2Binf.jl:80
           grp.S[2 * k + 1] = (a.y + b.y) + c.y;
           grp.X[2 * k] = b.x;
@@ -240,7 +398,9 @@ __global__ __launch_bounds__(256, (BINF && EPL >= 16) ? 2 : SPX_GROUP_WAVES) voi
           const int e = k * LPG + j;
           const bool in = e < gs;
           const int64_t i = base + (in ? e : 0);
-          const double a = in ? q_[i] : 0.0, b = in ? xk_[i] : 0.0, c = in ? sj_[i] : 0.0;
+          double a = in ? q_[i] : 0.0;
+          const double b = in ? xk_[i] : 0.0, c = in ? sj_[i] : 0.0;
+          if constexpr (VALUE) a = gv.qs * a;
           grp.S[k] = (a + b) + c;
           grp.X[k] = b;
           grp.XS[k] = b + c;
@@ -271,7 +431,7 @@ __global__ __launch_bounds__(256, (BINF && EPL >= 16) ? 2 : SPX_GROUP_WAVES) voi
         // (one atomic per group.  A data set whose groups ALL defer is bound by this counter: the hardware already merges
         //  the atomics of a wavefront into one request, ~11 ns each on the one address -- 8e6 groups of 16 = 5e5 requests
         //  = 6 ms; merging them in software changes nothing.  Sharded lists would; not needed for the cases at hand.)
-        if (valid && j == 0) deferred[1 + atomicAdd(dcount, 1ull)] = g;
+        if (valid && j == 0) { deferred[1 + atomicAdd(dcount, 1ull)] = g; handed_on = true; }
         valid = false;
       }
       if (status != BINF_ROOT || ru == 0.0) {  // shiftedGroupNormL2Binf.jl:102-103, :107-108
@@ -281,6 +441,22 @@ __global__ __launch_bounds__(256, (BINF && EPL >= 16) ? 2 : SPX_GROUP_WAVES) voi
         const double tau = ru * fast_rcp(sl + ru);  // = alpha at the root (:83 with ||w|| = n)
 #pragma unroll
         for (int k = 0; k < EPL; ++k) out[k] = binf_y(grp.S[k], grp.X[k], tau, delta) - grp.XS[k];  // :110-116
+      }
+    }
+    if constexpr (VALUE) {
+      // v = (xk + sj) + y of the elements this lane is about to store; slots past the end of the group add nothing
+      double vv = 0.0;
+#pragma unroll
+      for (int k = 0; k < EPL; ++k) {
+        const bool in = FULL || (PAIRS ? ((k >> 1) * LPG + j) < npairs : (k * LPG + j) < gs);
+        const double v = grp.XS[k] + out[k];
+        vv += in ? v * v : 0.0;
+      }
+      vv = lanes_sum<LPG>(vv);
+      if constexpr (LIT) {  // (a handed-on group: its term has a slot of its own, see GroupVal)
+        if (valid && j == 0) spx_atomic_store_f64(&gv.dterm[g], lam * sqrt(vv));
+      } else {
+        if (valid && j == 0) hsum += lam * sqrt(vv);
       }
     }
     if (valid) {
@@ -298,6 +474,15 @@ __global__ __launch_bounds__(256, (BINF && EPL >= 16) ? 2 : SPX_GROUP_WAVES) voi
           if (k * LPG + j < gs) y_[base + k * LPG + j] = out[k];
       }
     }
+  }
+  if constexpr (VALUE) {
+    if constexpr (!LIT) {  // (the host gives every wavefront one tile in these launches: tile = wavefront)
+      if (gv.dmask != nullptr) {
+        const unsigned long long m = __ballot(handed_on);
+        if (lane == 0) gv.dmask[wave] = m;
+      }
+    }
+    gval_finish(hsum, handed_on, gv);
   }
 }
 
@@ -376,6 +561,87 @@ __global__ __launch_bounds__(256) void k_group_mem(double* y, const double* q, c
     group_body<TEAM, BINF>(grp, y, lambda[g], sigma, delta, lds, list != nullptr, pole_lit != 0);
     if constexpr (TEAM == 256) __syncthreads();
   }
+}
+
+// spx_proxval_group_l2[_binf], ragged layouts with a size bound: the groups the register tiles handed on (above the bound /
+// literal evaluation), as k_group_mem<64> does with a list -- a wavefront per group, the prox taken at qs * q -- plus each
+// group's term of the value from the y just stored (every lane re-reads its own elements); the call's last launch.
+template <int TEAM>
+struct ScaledMemGroup {  // MemGroup at qs * q
+  static constexpr bool kReg = false;
+  static constexpr int kEpl = 1;
+  const double* q;
+  const double* xk;
+  const double* sj;
+  int64_t lo, hi;
+  int lane;
+  double qs;
+  template <class F>
+  __device__ __forceinline__ void for_each(F&& f) const {
+    for (int64_t i = lo + lane; i < hi; i += TEAM) {
+      const double x = xk[i], a = qs * q[i];
+      f((a + x) + sj[i], x);
+    }
+  }
+  template <class F>
+  __device__ __forceinline__ void store(double* y, F&& f) const {
+    for (int64_t i = lo + lane; i < hi; i += TEAM) {
+      const double x = xk[i], s = sj[i], a = qs * q[i];
+      const double S = (a + x) + s;
+      y[i] = f(S, x) - (x + s);
+    }
+  }
+};
+template <bool BINF>
+__global__ __launch_bounds__(256) void k_group_list_val(double* y, const double* q, const double* xk, const double* sj,
+                                                         int64_t n, const int64_t* __restrict__ offsets, int64_t gsize,
+                                                         int64_t ngroups, const double* __restrict__ lambda, double sigma,
+                                                         double delta, const long long* list /* [0] = count, [1..] */,
+                                                         int* status, int pole_lit, GroupVal gv) {
+  __shared__ double lds[8];
+  constexpr int TEAM = 64, TPB = 256 / TEAM;
+  const int lane = threadIdx.x % TEAM;
+  const int64_t team = (int64_t)blockIdx.x * TPB + threadIdx.x / TEAM;
+  const int64_t nteams = (int64_t)gridDim.x * TPB;
+  const int64_t nlist = (int64_t)list[0];
+  const bool bad_count = nlist < 0 || nlist > ngroups;  // (as k_group_reg: reported through the status word)
+  if (bad_count && blockIdx.x == 0 && threadIdx.x == 0) spx_raise_status(status, kSpxStatusCorrupt);
+  const int64_t ntodo = bad_count ? 0 : nlist;
+  for (int64_t t = team; t < ntodo; t += nteams) {
+    const int64_t g = (int64_t)list[1 + t];
+    if (g < 0 || g >= ngroups) {
+      if (lane == 0) spx_raise_status(status, kSpxStatusCorrupt);
+      continue;
+    }
+    int64_t lo, hi;
+    if (offsets) { lo = offsets[g]; hi = offsets[g + 1]; }
+    else { lo = g * gsize; hi = lo + gsize; }
+    if (lo < 0) lo = 0;
+    if (hi > n) hi = n;
+    ScaledMemGroup<TEAM> grp{q, xk, sj, lo, hi, lane, gv.qs};
+    group_body<TEAM, BINF>(grp, y, lambda[g], sigma, delta, lds, true, pole_lit != 0);
+    double vv = 0.0;
+    for (int64_t i = lo + lane; i < hi; i += TEAM) {  // (this lane's own stores)
+      const double v = (xk[i] + sj[i]) + y[i];
+      vv += v * v;
+    }
+    vv = lanes_sum<TEAM>(vv);
+    if (lane == 0) spx_atomic_store_f64(&gv.dterm[g], lambda[g] * sqrt(vv));  // (its own slot: GroupVal)
+  }
+  gval_finish(0.0, false, gv);
+}
+// y = c * q, elementwise (the composed routes of spx_proxval_group_* with q_scale != 1: the prox then runs at q := y)
+// CSR layouts: only over [offsets[0], offsets[ngroups]) -- the indices no group contains keep the caller's y for the operator.
+__global__ __launch_bounds__(256) void k_group_scale(double* y, const double* q, double c, int64_t n,
+                                                      const int64_t* __restrict__ offsets, int64_t ngroups) {
+  int64_t lo = 0, hi = n;
+  if (offsets) {
+    lo = offsets[0]; hi = offsets[ngroups];
+    if (lo < 0) lo = 0;
+    if (hi > n) hi = n;
+  }
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = lo + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < hi; i += stride) y[i] = c * q[i];
 }
 
 // Large uniform groups (512 < size <= kLdsGroupMax): one workgroup per group, S = (q + xk) + sj and X = xk staged in
@@ -503,10 +769,31 @@ __global__ __launch_bounds__(256) void k_gather_rest(double* y, const double* xk
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-template <bool BINF>
+// The (lanes per group, elements per lane) tiles run_group selects for each operator.
+constexpr bool group_tile_used(bool binf, int lpg, int epl) {
+  if (lpg == 1 && epl == 2) return true;
+  if (binf) return (lpg == 1 && (epl == 4 || epl == 8)) || (epl == 8 && (lpg == 2 || lpg == 4 || lpg == 8)) ||
+                   (epl == 16 && (lpg == 8 || lpg == 16 || lpg == 32));
+  return (lpg == 2 && epl == 4) || (lpg == 4 && epl == 4) || (lpg == 16 && (epl == 2 || epl == 4 || epl == 8)) ||
+         (lpg == 32 && epl == 8) || (lpg == 64 && (epl == 6 || epl == 8));
+}
+
+// VALUE (run_group_val below, register-tile routes only): the launches also form h at the result, see GroupVal.
+// The value of a fused call: NaN on the host when it goes to the context's device double (nothing read back), else read back.
+static int group_val_return(spx_ctx* ctx, GroupValWs* vws, double* value) {
+  if (ctx->value_target) {
+    *value = std::numeric_limits<double>::quiet_NaN();
+    return SPX_OK;
+  }
+  SPX_HIP(hipMemcpyAsync(value, &vws->result, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  SPX_HIP(hipStreamSynchronize(ctx->stream));
+  return SPX_OK;
+}
+
+template <bool BINF, bool VALUE = false>
 static int run_group(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
                      const int64_t* offsets, int64_t gsize, int64_t ngroups, const double* lambda, double sigma,
-                     double delta) {
+                     double delta, double q_scale = 1.0, double* value = nullptr) {
   int rc = spx_check_common(ctx, y, q, xk, sj, n);
   if (rc) return rc;
   SPX_REQUIRE(ngroups >= 0, "ngroups < 0");
@@ -566,9 +853,34 @@ static int run_group(spx_ctx* ctx, double* y, const double* q, const double* xk,
     dim3 grid((unsigned)blocks), block(256);
     long long* deferred = nullptr;
     unsigned long long *dcount = nullptr, *dclear = nullptr;
-    if (BINF || ragged_reg) {  // list of the groups whose bracket needs the reference's literal evaluation / oversize groups
-      rc = spx_ws_reserve(ctx, (size_t)(ngroups + 1) * sizeof(long long) + 256);
+    // VALUE: one reservation -- [deferred list | GroupValWs | partials and flags of the main launch | tile masks | dterm]
+    [[maybe_unused]] GroupVal gv_main{}, gv_last{};
+    [[maybe_unused]] GroupValWs* vws = nullptr;
+    if constexpr (VALUE) {
+      const size_t list_bytes = (BINF || ragged_reg) ? (((size_t)(ngroups + 1) * sizeof(long long) + 256 + 255) & ~(size_t)255) : 0;
+      // (a wavefront per tile: the masks of the handed-on groups are indexed by wavefront)
+      SPX_REQUIRE(blocks * 4 * gpw >= ngroups, "too many groups for the fused value form");
+      const size_t part_bytes = ((size_t)blocks * 2 * sizeof(double) + 255) & ~(size_t)255;  // partials | flags
+      const size_t mask_bytes = list_bytes ? (size_t)blocks * 4 * sizeof(unsigned long long) : 0;
+      rc = spx_ws_reserve(ctx, list_bytes + sizeof(GroupValWs) + part_bytes + mask_bytes + (list_bytes ? (size_t)ngroups * sizeof(double) : 0) + 256);
       if (rc) return rc;
+      rc = spx_sync_ready(ctx);
+      if (rc) return rc;
+      vws = reinterpret_cast<GroupValWs*>(static_cast<char*>(ctx->ws) + list_bytes);
+      double* part = reinterpret_cast<double*>(vws + 1);
+      const bool one = !(BINF || ragged_reg);  // the main launch is the call's last one
+      unsigned long long* dmask = one ? nullptr : reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(part) + part_bytes);
+      double* dterm = one ? nullptr : reinterpret_cast<double*>(reinterpret_cast<char*>(part) + part_bytes + mask_bytes);
+      gv_main = GroupVal{q_scale, part, one ? nullptr : part + blocks, (int)blocks, false, one ? spx_sync_header(ctx) : nullptr, vws, ctx->value_target, dmask, dterm, lpg};
+      gv_last = gv_main;
+      gv_last.behind = true;
+      gv_last.hdr = spx_sync_header(ctx);
+    }
+    if (BINF || ragged_reg) {  // list of the groups whose bracket needs the reference's literal evaluation / oversize groups
+      if constexpr (!VALUE) {
+        rc = spx_ws_reserve(ctx, (size_t)(ngroups + 1) * sizeof(long long) + 256);
+        if (rc) return rc;
+      }
       deferred = reinterpret_cast<long long*>(ctx->ws);
       dcount = reinterpret_cast<unsigned long long*>(deferred);
       // Round 4: the zero-fill of the count word was a launch of its own in front of every call (a Binf call at solver sizes:
@@ -593,15 +905,27 @@ static int run_group(spx_ctx* ctx, double* y, const double* q, const double* xk,
       hipLaunchKernelGGL(k_csr_uncovered<double>, dim3(256), dim3(256), 0, ctx->stream, y, xk, sj, offsets, ngroups, n);
 #define SPX_LAUNCH_REG(LPG, EPL)                                                                                    \
   do {                                                                                                              \
-    if (pairs && gsize == (LPG) * (EPL)) {                                                                          \
+    if constexpr (VALUE && !group_tile_used(BINF, LPG, EPL)) {                                                      \
+      /* (a tile the other operator uses: never selected above, not instantiated with the value) */               \
+    } else if constexpr (VALUE) {                                                                                   \
+      if (pairs && gsize == (LPG) * (EPL)) {                                                                        \
+        hipLaunchKernelGGL((k_group_reg<LPG, EPL, BINF, true, false, true, true>), grid, block, 0, ctx->stream, y, q, xk, sj, \
+                           ngroups, (int)gsize, lambda, sigma, delta, deferred, (const int64_t*)nullptr, ctx->status_dev, ctx->tune_binf_literal, dcount, (unsigned long long*)nullptr, gv_main); \
+      } else if (pairs) {                                                                                           \
+        hipLaunchKernelGGL((k_group_reg<LPG, EPL, BINF, true, false, false, true>), grid, block, 0, ctx->stream, y, q, xk, sj, ngroups, \
+                           (int)gsize, lambda, sigma, delta, deferred, (const int64_t*)nullptr, ctx->status_dev, ctx->tune_binf_literal, dcount, (unsigned long long*)nullptr, gv_main); \
+      } else                                                                                                        \
+        hipLaunchKernelGGL((k_group_reg<LPG, EPL, BINF, false, false, false, true>), grid, block, 0, ctx->stream, y, q, xk, sj, ngroups, \
+                           (int)gsize, lambda, sigma, delta, deferred, ragged_reg ? offsets : (const int64_t*)nullptr, ctx->status_dev, ctx->tune_binf_literal, dcount, (unsigned long long*)nullptr, gv_main); \
+    } else if (pairs && gsize == (LPG) * (EPL)) {                                                                          \
       hipLaunchKernelGGL((k_group_reg<LPG, EPL, BINF, true, false, true>), grid, block, 0, ctx->stream, y, q, xk, sj, \
-                         ngroups, (int)gsize, lambda, sigma, delta, deferred, (const int64_t*)nullptr, ctx->status_dev, ctx->tune_binf_literal, dcount, (unsigned long long*)nullptr); \
+                         ngroups, (int)gsize, lambda, sigma, delta, deferred, (const int64_t*)nullptr, ctx->status_dev, ctx->tune_binf_literal, dcount, (unsigned long long*)nullptr, GroupNoVal{}); \
     } else if (pairs) {                                                                                             \
       hipLaunchKernelGGL((k_group_reg<LPG, EPL, BINF, true>), grid, block, 0, ctx->stream, y, q, xk, sj, ngroups,   \
-                         (int)gsize, lambda, sigma, delta, deferred, (const int64_t*)nullptr, ctx->status_dev, ctx->tune_binf_literal, dcount, (unsigned long long*)nullptr);    \
+                         (int)gsize, lambda, sigma, delta, deferred, (const int64_t*)nullptr, ctx->status_dev, ctx->tune_binf_literal, dcount, (unsigned long long*)nullptr, GroupNoVal{});    \
     } else                                                                                                            \
       hipLaunchKernelGGL((k_group_reg<LPG, EPL, BINF, false>), grid, block, 0, ctx->stream, y, q, xk, sj, ngroups,  \
-                         (int)gsize, lambda, sigma, delta, deferred, ragged_reg ? offsets : (const int64_t*)nullptr, ctx->status_dev, ctx->tune_binf_literal, dcount, (unsigned long long*)nullptr); \
+                         (int)gsize, lambda, sigma, delta, deferred, ragged_reg ? offsets : (const int64_t*)nullptr, ctx->status_dev, ctx->tune_binf_literal, dcount, (unsigned long long*)nullptr, GroupNoVal{}); \
   } while (0)
     if (lpg == 1 && epl == 2) SPX_LAUNCH_REG(1, 2);
     else if (lpg == 1 && epl == 4) SPX_LAUNCH_REG(1, 4);
@@ -628,12 +952,19 @@ static int run_group(spx_ctx* ctx, double* y, const double* q, const double* xk,
         const dim3 lgrid((unsigned)(blocks < (int64_t)ctx->num_cu * 8 ? blocks : (int64_t)ctx->num_cu * 8));
 #define SPX_LAUNCH_LIT(LPG, EPL)                                                                                     \
   do {                                                                                                               \
-    if (pairs)                                                                                                       \
+    if constexpr (VALUE) {                                                                                           \
+      if (pairs)                                                                                                     \
+        hipLaunchKernelGGL((k_group_reg<LPG, EPL, true, true, true, false, true>), lgrid, block, 0, ctx->stream, y, q, xk, sj, \
+                           ngroups, (int)gsize, lambda, sigma, delta, deferred, (const int64_t*)nullptr, ctx->status_dev, ctx->tune_binf_literal, dcount, dclear, gv_last); \
+      else                                                                                                           \
+        hipLaunchKernelGGL((k_group_reg<LPG, EPL, true, false, true, false, true>), lgrid, block, 0, ctx->stream, y, q, xk, sj, \
+                           ngroups, (int)gsize, lambda, sigma, delta, deferred, (const int64_t*)nullptr, ctx->status_dev, ctx->tune_binf_literal, dcount, dclear, gv_last); \
+    } else if (pairs)                                                                                                \
       hipLaunchKernelGGL((k_group_reg<LPG, EPL, true, true, true>), lgrid, block, 0, ctx->stream, y, q, xk, sj,      \
-                         ngroups, (int)gsize, lambda, sigma, delta, deferred, (const int64_t*)nullptr, ctx->status_dev, ctx->tune_binf_literal, dcount, dclear); \
+                         ngroups, (int)gsize, lambda, sigma, delta, deferred, (const int64_t*)nullptr, ctx->status_dev, ctx->tune_binf_literal, dcount, dclear, GroupNoVal{}); \
     else                                                                                                             \
       hipLaunchKernelGGL((k_group_reg<LPG, EPL, true, false, true>), lgrid, block, 0, ctx->stream, y, q, xk, sj,     \
-                         ngroups, (int)gsize, lambda, sigma, delta, deferred, (const int64_t*)nullptr, ctx->status_dev, ctx->tune_binf_literal, dcount, dclear); \
+                         ngroups, (int)gsize, lambda, sigma, delta, deferred, (const int64_t*)nullptr, ctx->status_dev, ctx->tune_binf_literal, dcount, dclear, GroupNoVal{}); \
   } while (0)
         // (its own tiles, by the group size: the list is short, the literal evaluation wants lanes)
         if (gsize <= 16) SPX_LAUNCH_LIT(4, 4);
@@ -644,16 +975,27 @@ static int run_group(spx_ctx* ctx, double* y, const double* q, const double* xk,
         else SPX_LAUNCH_LIT(32, 16);
 #undef SPX_LAUNCH_LIT
         SPX_LAUNCH_CHECK();
+        if constexpr (VALUE) return group_val_return(ctx, vws, value);
         return SPX_OK;
       }
     }
     if (BINF || ragged_reg) {  // usually an empty list: the kernel returns at once
+      if constexpr (VALUE)
+        hipLaunchKernelGGL((k_group_list_val<BINF>), dim3((unsigned)(ctx->num_cu * 2)), dim3(256), 0, ctx->stream, y, q, xk,
+                           sj, n, ragged_reg ? offsets : (const int64_t*)nullptr, gsize, ngroups, lambda, sigma, delta,
+                           (const long long*)deferred, ctx->status_dev, ctx->tune_binf_literal, gv_last);
+      else
       hipLaunchKernelGGL((k_group_mem<64, BINF>), dim3((unsigned)(ctx->num_cu * 2)), dim3(256), 0, ctx->stream, y, q, xk,
                          sj, n, ragged_reg ? offsets : (const int64_t*)nullptr, gsize, ngroups, lambda, sigma, delta,
                          (const long long*)deferred, ctx->status_dev, ctx->tune_binf_literal, (const int*)nullptr, (int64_t)0);
     }
     SPX_LAUNCH_CHECK();
+    if constexpr (VALUE) return group_val_return(ctx, vws, value);
     return SPX_OK;
+  }
+  if constexpr (VALUE) {  // (run_group_val composes the other routes from the plain operator and psi(y))
+    spx_set_error("internal: no fused value form for this group layout");
+    return SPX_ERR_INVALID_ARG;
   }
   // team width: wavefront per group unless groups are large on average
   if (gsize > 512 && gsize <= (BINF ? kLdsGroupMax : kLdsGroupMaxPlain)) {
@@ -734,6 +1076,67 @@ SPX_EXPORT int spx_prox_group_l2_binf(spx_ctx* ctx, double* y, const double* q, 
                                       int64_t n, const int64_t* group_offsets, int64_t group_size, int64_t ngroups,
                                       const double* lambda_vec, double sigma, double delta) {
   return run_group<true>(ctx, y, q, xk, sj, n, group_offsets, group_size, ngroups, lambda_vec, sigma, delta);
+}
+
+// ---------------------------------------------------------------------------------------------
+// prox! fused with h at the result (include/spx.h, "group forms").  Register-tile routes (uniform groups of at most 512
+// elements, CSR offsets with a size bound of at most 512): the value comes out of the launches that store y.  Every other
+// route (LDS-resident groups, the general kernels, teams of workgroups): composed in this call -- y = q_scale * q where the
+// scale is not 1, the unchanged prox at q := y, then the one-launch psi(y) (spx_obj_group_l2) on the same stream.
+// ---------------------------------------------------------------------------------------------
+template <bool BINF>
+static int run_group_val(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
+                         const int64_t* offsets, int64_t gsize, int64_t ngroups, const double* lambda, double sigma,
+                         double delta, double q_scale, double* value) {
+  SPX_REQUIRE(value != nullptr, "value is NULL");
+  int rc = spx_check_common(ctx, y, q, xk, sj, n);
+  if (rc) return rc;
+  SPX_REQUIRE(ngroups >= 0, "ngroups < 0");
+  if (n > 0 && ngroups > 0) {  // (run_group's checks, before the first launch of a composed call)
+    SPX_REQUIRE(lambda != nullptr, "lambda_vec is NULL");
+    if (!offsets) {
+      SPX_REQUIRE(gsize > 0, "group_size <= 0 with NULL group_offsets");
+      SPX_REQUIRE(ngroups <= n / gsize && ngroups * gsize == n, "ngroups * group_size != n");
+    }
+  }
+  if (!ctx->value_target) {  // (refused before anything is enqueued)
+    const int rcc = spx_require_not_capturing(ctx, "returning the value to the host");
+    if (rcc) return rcc;
+  }
+  *value = 0.0;
+  if (n == 0 || ngroups == 0) {  // h of no group at all; y as the plain operator leaves it (it does not read q)
+    rc = run_group<BINF>(ctx, y, q, xk, sj, n, offsets, gsize, ngroups, lambda, sigma, delta);
+    if (rc) return rc;
+    if (ctx->value_target) return spx_zero_async(ctx, ctx->value_target, sizeof(double));
+    return SPX_OK;
+  }
+  if ((!offsets && gsize <= 512) || (offsets && gsize > 0 && gsize <= 512))
+    return run_group<BINF, true>(ctx, y, q, xk, sj, n, offsets, gsize, ngroups, lambda, sigma, delta, q_scale, value);
+  const double* qq = q;
+  if (q_scale != 1.0) {
+    SPX_ON_DEVICE(ctx);
+    int64_t eb = (n + 255) / 256;
+    if (eb > (int64_t)ctx->num_cu * 8) eb = (int64_t)ctx->num_cu * 8;
+    hipLaunchKernelGGL(k_group_scale, dim3((unsigned)eb), dim3(256), 0, ctx->stream, y, q, q_scale, n, offsets, ngroups);
+    SPX_LAUNCH_CHECK();
+    qq = y;
+  }
+  rc = run_group<BINF>(ctx, y, qq, xk, sj, n, offsets, gsize, ngroups, lambda, sigma, delta);
+  if (rc) return rc;
+  return spx_obj_group_l2(ctx, y, xk, sj, n, offsets, gsize, ngroups, lambda, value);
+}
+
+SPX_EXPORT int spx_proxval_group_l2(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
+                                    const int64_t* group_offsets, int64_t group_size, int64_t ngroups,
+                                    const double* lambda_vec, double sigma, double q_scale, double* value) {
+  return run_group_val<false>(ctx, y, q, xk, sj, n, group_offsets, group_size, ngroups, lambda_vec, sigma, 0.0, q_scale, value);
+}
+
+SPX_EXPORT int spx_proxval_group_l2_binf(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj,
+                                         int64_t n, const int64_t* group_offsets, int64_t group_size, int64_t ngroups,
+                                         const double* lambda_vec, double sigma, double delta, double q_scale,
+                                         double* value) {
+  return run_group_val<true>(ctx, y, q, xk, sj, n, group_offsets, group_size, ngroups, lambda_vec, sigma, delta, q_scale, value);
 }
 
 // ---------------------------------------------------------------------------------------------

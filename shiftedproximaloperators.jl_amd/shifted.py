@@ -752,13 +752,20 @@ def prox(ψ, q, σ):
 
 
 def prox_value_bang(y, ψ, q, σ, q_scale=1.0):
-    """prox!(y, ψ, q_scale .* q, σ) and h(xk + sj + y) of the result in ONE pass over the vectors (the pair a solver iteration makes:
-    R2's `prox!(s, ψ, …)` followed by `ψ(s)`): returns (y, value).  Device vectors, the separable operators
-    (ShiftedNormL1 / NormL0 / RootNormLhalf and their Box forms); synchronises to return the value.  The Box forms
-    return the h part of ψ(y): the prox lies inside the box by construction.  q_scale: the prox is taken at q_scale * q,
-    formed on the fly (R2: `prox_value(ψ, ∇f, ν, q_scale=-ν)` instead of materialising -ν∇f)."""
+    """prox!(y, ψ, q_scale .* q, σ) and h(xk + sj + y) of the result in ONE call (the pair a solver iteration makes:
+    R2's `prox!(s, ψ, …)` followed by `ψ(s)`): returns (y, value).  Device vectors; synchronises to return the value
+    (unless inside `device_values`).  The separable operators (ShiftedNormL1 / NormL0 / RootNormLhalf and their Box
+    forms) and, on Float64 vectors with contiguous groups, ShiftedGroupNormL2 / ShiftedGroupNormL2Binf: one pass over the
+    vectors for groups of at most 512 elements (uniform, or ragged with that bound), the prox followed by ψ's reduction
+    inside the same library call beyond.  The Box and Binf forms return the h part of ψ(y): the prox lies inside the box /
+    trust region by construction.  q_scale: the prox is taken at q_scale * q, formed on the fly (R2:
+    `prox_value(ψ, ∇f, ν, q_scale=-ν)` instead of materialising -ν∇f).  Float32 group operators, host ψ, index-set
+    (gather) layouts and the remaining operators raise TypeError."""
+    if isinstance(ψ, (ShiftedGroupNormL2, ShiftedGroupNormL2Binf)):
+        return _group_prox_value_bang(y, ψ, q, σ, q_scale)
     if not isinstance(ψ, (_Unboxed, _Boxed)) or ψ.host:
-        raise TypeError("prox_value is available for the separable operators on device vectors")
+        raise TypeError("prox_value is available for the separable operators and the contiguous Float64 group operators "
+                        "on device vectors")
     n = _n(ψ.xk)
     _vec(q, "q", n, like=ψ.xk)
     _vec(y, "y", n, like=ψ.xk)
@@ -778,8 +785,26 @@ def prox_value_bang(y, ψ, q, σ, q_scale=1.0):
     return y, out.value
 
 
+def _group_prox_value_bang(y, ψ, q, σ, q_scale):
+    g = ψ._layout
+    if _is_host(ψ.xk) or ψ.xk.dtype != torch.float64 or g.index is not None:
+        raise TypeError("prox_value on a group operator needs device Float64 vectors and contiguous groups")
+    n = _n(ψ.xk)
+    _vec(q, "q", n, like=ψ.xk)
+    _vec(y, "y", n, like=ψ.xk)
+    ψ._refresh()
+    L, ctx = _lib.load(), _ctx(_dev(y))
+    out = ctypes.c_double(0.0)
+    head = (ctx, _ptr(y), _ptr(q), _ptr(ψ.xk), _ptr(ψ.sj), n, _ptr(g.offsets), g.group_size, g.ngroups, _ptr(g.lam), float(σ))
+    if isinstance(ψ, ShiftedGroupNormL2Binf):
+        _lib.check(L.spx_proxval_group_l2_binf(*head, ψ.Δ, float(q_scale), ctypes.byref(out)))
+    else:
+        _lib.check(L.spx_proxval_group_l2(*head, float(q_scale), ctypes.byref(out)))
+    return y, out.value
+
+
 def prox_value(ψ, q, σ, q_scale=1.0):
-    """(prox(ψ, q_scale .* q, σ), h(xk + sj + prox)) in one pass; see prox_value_bang"""
+    """(prox(ψ, q_scale .* q, σ), h(xk + sj + prox)) in one call; see prox_value_bang"""
     return prox_value_bang(ψ.sol, ψ, q, σ, q_scale)
 
 
