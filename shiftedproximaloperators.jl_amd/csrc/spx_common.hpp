@@ -71,7 +71,7 @@ struct spx_ctx {
   int tune_team_fast = 1;          // key 14: ... and the Binf form of that takes its sample-predicted two-pass path (0 = generic body: one
                                    //         streaming pass per reduction)
   int tune_team_factor = 0;        // key 16: the team form serves uniform large groups while there are fewer than this many per workgroup of its
-                                   //         grid (0 = default, see run_group in spx_group.hip); an A/B knob
+                                   //         grid (0 = default, see group_route_general in spx_group.hip); an A/B knob
   int tune_fewer_launches = 1;     // key 17: psi(y) in one launch (the last workgroup finishes: spx_fin_ticket) and the Binf group operators without the
                                    //         zero-fill launch of their deferred list (count words that alternate); 0 = the launches of rounds 1-3
   int tune_force_grid = 0;         // key 100, test builds only (-DSPX_TEST_HOOKS): launch the one-launch top-r with THIS many workgroups,
@@ -124,7 +124,7 @@ int spx_require_not_capturing(spx_ctx* ctx, const char* what);
 // Does an in-launch synchronised launch take its graph-safe form (see spx_ctx::graph_safe)?  Switches the mode on if capturing.
 static inline bool spx_graph_safe(spx_ctx* ctx) { return spx_capture_check(ctx) || ctx->graph_safe; }
 
-// spx_group_team.hip (large contiguous groups on teams of workgroups), called from run_group in spx_group.hip
+// spx_group_team.hip (large contiguous groups on teams of workgroups), called from group_route_general in spx_group.hip
 int spx_group_team_max_grid(spx_ctx* ctx, bool binf);
 int spx_group_team_plan(spx_ctx* ctx, bool binf, const double* y, const double* q, const double* xk, const double* sj,
                         int64_t n, const int64_t* offsets, int64_t ngroups, int64_t big_min, const int** active_dev);

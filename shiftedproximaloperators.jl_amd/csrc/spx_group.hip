@@ -769,16 +769,100 @@ __global__ __launch_bounds__(256) void k_gather_rest(double* y, const double* xk
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-// The (lanes per group, elements per lane) tiles run_group selects for each operator.
-constexpr bool group_tile_used(bool binf, int lpg, int epl) {
-  if (lpg == 1 && epl == 2) return true;
-  if (binf) return (lpg == 1 && (epl == 4 || epl == 8)) || (epl == 8 && (lpg == 2 || lpg == 4 || lpg == 8)) ||
-                   (epl == 16 && (lpg == 8 || lpg == 16 || lpg == 32));
-  return (lpg == 2 && epl == 4) || (lpg == 4 && epl == 4) || (lpg == 16 && (epl == 2 || epl == 4 || epl == 8)) ||
-         (lpg == 32 && epl == 8) || (lpg == 64 && (epl == 6 || epl == 8));
+// The arguments of a contiguous-group call (spx_prox_group_l2[_binf], spx_proxval_group_l2[_binf]).
+struct GroupCall {
+  spx_ctx* ctx;
+  double* y;
+  const double *q, *xk, *sj;
+  int64_t n;
+  const int64_t* offsets;
+  int64_t gsize, ngroups;
+  const double* lambda;
+  double sigma, delta;
+};
+
+// Register tiles.  A row GroupTile<MAXG, LPG, EPL> sends the group sizes (uniform, or the caller's bound on ragged sizes) up to
+// MAXG that no earlier row takes to LPG lanes per group x EPL elements per lane: the smallest tile that holds a group, partly
+// filled tiles are padded with zeros.  A table states each bound with its tile, once; the launch site receives the row as a type.
+constexpr int kGroupRegMax = 512;  // the largest size on the register tiles
+template <int MAXG, int LPG, int EPL>
+struct GroupTile {
+  static_assert(LPG * EPL >= MAXG, "tile cannot hold the sizes routed to it");
+  static_assert(64 % LPG == 0 && EPL % 2 == 0, "LPG lanes of a wavefront, 16-byte pairs");
+  static constexpr int maxg = MAXG, lpg = LPG, epl = EPL;
+};
+constexpr bool group_bounds_ok(std::initializer_list<int> bounds) {  // ascending, up to kGroupRegMax
+  int prev = 0;
+  for (const int b : bounds) {
+    if (b <= prev) return false;
+    prev = b;
+  }
+  return prev == kGroupRegMax;
+}
+template <class... Rows>
+struct GroupTiles {
+  static_assert(group_bounds_ok({Rows::maxg...}), "row bounds must ascend to kGroupRegMax");
+  // f(row) for the row of this size (0 < gsize <= kGroupRegMax)
+  template <class F>
+  static bool select(int64_t gsize, F&& f) {
+    return ((gsize <= Rows::maxg ? (f(Rows{}), true) : false) || ...);
+  }
+  static int lpg(int64_t gsize) {
+    int lanes = 0;
+    select(gsize, [&](auto row) { lanes = decltype(row)::lpg; });
+    return lanes;
+  }
+};
+// Binf: as few lanes per group as the registers allow (4 x 4/8, 8 x 8/16, 16 x 16, 32 x 16 elements) -- the wave-uniform
+// scalar work of the root find, which every lane executes, is then shared by more groups per wave
+// Small groups (round 3): tiles that FIT -- a 4 x 4 tile spent four lanes' worth of root find (Binf) or reduction on a group
+// of two, and three quarters of its loads on padding.  us per call at n = 1.6e7, old -> new tile (tools/r3/binf_small_groups.py):
+// Binf groups of 2: 1305 -> 368, of 4: 680 -> 208, of 8: 317 -> 174, of 16: 155 -> 142; plain groups of 2: 508 -> 89, of 4:
+// 283 -> 92, of 8: 162 -> 90, of 10: 132 -> 107.  (One lane per group beyond 8 elements loses more to the 64-byte strides
+// between its lanes' loads than it saves: Binf 1 x 16 on groups of 16 270 us.)
+using GroupTilesBinf = GroupTiles<GroupTile<2, 1, 2>, GroupTile<4, 1, 4>, GroupTile<8, 1, 8>, GroupTile<16, 2, 8>, GroupTile<32, 4, 8>,
+                                  GroupTile<64, 8, 8>,  // (4 x 16 is slower here: 64-byte runs per group and load)
+                                  GroupTile<128, 8, 16>, GroupTile<256, 16, 16>, GroupTile<512, 32, 16>>;
+using GroupTilesPlain = GroupTiles<GroupTile<2, 1, 2>, GroupTile<4, 2, 4>, GroupTile<12, 4, 4>, GroupTile<32, 16, 2>, GroupTile<64, 16, 4>,
+                                   GroupTile<128, 16, 8>, GroupTile<256, 32, 8>, GroupTile<384, 64, 6>, GroupTile<512, 64, 8>>;
+// The LIT launch of the Binf form (its own tiles, by the group size: the list is short, the literal evaluation wants lanes)
+using GroupTilesLit = GroupTiles<GroupTile<16, 4, 4>, GroupTile<32, 4, 8>, GroupTile<64, 8, 8>, GroupTile<128, 8, 16>,
+                                 GroupTile<256, 16, 16>, GroupTile<512, 32, 16>>;
+
+// What the k_group_reg launches of a call share.
+struct GroupRegArgs {
+  const GroupCall& c;
+  long long* deferred;
+  unsigned long long* dcount;
+  bool pairs;  // 16-byte loads: uniform groups of even size in 16-byte aligned vectors; otherwise 8-byte loads
+};
+// One k_group_reg launch.  PAIRS by the loads; FULL (main launches only) when the groups fill the tile; `gv` is passed on by VALUE.
+// dclear: the LIT launch's, NULL for a main launch.
+template <int LPG, int EPL, bool BINF, bool LIT, bool VALUE>
+static void launch_group_reg(const GroupRegArgs& a, dim3 grid, unsigned long long* dclear, const GroupVal& gv) {
+  const GroupCall& c = a.c;
+  typename std::conditional<VALUE, GroupVal, GroupNoVal>::type v{};
+  if constexpr (VALUE) v = gv;
+  auto launch = [&](auto pairs, auto full) {
+    hipLaunchKernelGGL((k_group_reg<LPG, EPL, BINF, decltype(pairs)::value, LIT, decltype(full)::value, VALUE>), grid, dim3(256), 0,
+                       c.ctx->stream, c.y, c.q, c.xk, c.sj, c.ngroups, (int)c.gsize, c.lambda, c.sigma, c.delta, a.deferred,
+                       c.offsets, c.ctx->status_dev, c.ctx->tune_binf_literal, a.dcount, dclear, v);
+  };
+  if (!a.pairs) return launch(std::false_type{}, std::false_type{});
+  if constexpr (!LIT) {
+    if (c.gsize == LPG * EPL) return launch(std::true_type{}, std::true_type{});
+  }
+  launch(std::true_type{}, std::false_type{});
 }
 
-// VALUE (run_group_val below, register-tile routes only): the launches also form h at the result, see GroupVal.
+// ShiftedGroupNormL2 with CSR offsets, which need not span 0:n (src/shiftedGroupNormL2.jl:77 runs over every index): the
+// indices no group covers.  Enqueued only; the caller's SPX_LAUNCH_CHECK follows.
+template <bool BINF>
+static void group_uncovered(const GroupCall& c) {
+  if (!BINF && c.offsets)
+    hipLaunchKernelGGL(k_csr_uncovered<double>, dim3(256), dim3(256), 0, c.ctx->stream, c.y, c.xk, c.sj, c.offsets, c.ngroups, c.n);
+}
+
 // The value of a fused call: NaN on the host when it goes to the context's device double (nothing read back), else read back.
 static int group_val_return(spx_ctx* ctx, GroupValWs* vws, double* value) {
   if (ctx->value_target) {
@@ -790,353 +874,280 @@ static int group_val_return(spx_ctx* ctx, GroupValWs* vws, double* value) {
   return SPX_OK;
 }
 
-template <bool BINF, bool VALUE = false>
-static int run_group(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
-                     const int64_t* offsets, int64_t gsize, int64_t ngroups, const double* lambda, double sigma,
-                     double delta, double q_scale = 1.0, double* value = nullptr) {
-  int rc = spx_check_common(ctx, y, q, xk, sj, n);
+// The routes of a contiguous-group call, by the group size (uniform) or the caller's bound on the sizes (CSR offsets).
+enum class GroupRoute {
+  None,     // n == 0 or no group at all
+  Reg,      // at most kGroupRegMax elements: register tiles
+  Lds,      // up to kLdsGroupMax[Plain]: LDS-resident group per workgroup
+  General,  // larger, or ragged without a bound: wavefront / workgroup per group, teams of workgroups for the large ones
+};
+// Validates the arguments and names the route.  Enqueues nothing.
+template <bool BINF>
+static int group_classify(const GroupCall& c, GroupRoute* route) {
+  int rc = spx_check_common(c.ctx, c.y, c.q, c.xk, c.sj, c.n);
   if (rc) return rc;
-  SPX_REQUIRE(ngroups >= 0, "ngroups < 0");
-  if (n == 0) return SPX_OK;
-  if (ngroups == 0) {  // no group at all: ShiftedGroupNormL2 still subtracts the shift everywhere (:77)
-    if (!BINF && offsets) {
-      SPX_ON_DEVICE(ctx);
-      hipLaunchKernelGGL(k_csr_uncovered<double>, dim3(256), dim3(256), 0, ctx->stream, y, xk, sj, offsets, ngroups, n);
-      SPX_LAUNCH_CHECK();
-    }
-    return SPX_OK;
+  SPX_REQUIRE(c.ngroups >= 0, "ngroups < 0");
+  *route = GroupRoute::None;
+  if (c.n == 0 || c.ngroups == 0) return SPX_OK;
+  SPX_REQUIRE(c.lambda != nullptr, "lambda_vec is NULL");
+  if (!c.offsets) {
+    SPX_REQUIRE(c.gsize > 0, "group_size <= 0 with NULL group_offsets");
+    SPX_REQUIRE(c.ngroups <= c.n / c.gsize && c.ngroups * c.gsize == c.n, "ngroups * group_size != n");
   }
-  SPX_REQUIRE(lambda != nullptr, "lambda_vec is NULL");
-  if (!offsets) {
-    SPX_REQUIRE(gsize > 0, "group_size <= 0 with NULL group_offsets");
-    SPX_REQUIRE(ngroups <= n / gsize && ngroups * gsize == n, "ngroups * group_size != n");
-  }
-  // y may alias q: every kernel finishes all reductions of a group (team barrier / wave lockstep) before
-  // the group's first store, and the storing lane re-reads q[i] itself just before writing y[i].
+  if (c.gsize > 0 && c.gsize <= kGroupRegMax) *route = GroupRoute::Reg;
+  else if (c.gsize > kGroupRegMax && c.gsize <= (BINF ? kLdsGroupMax : kLdsGroupMaxPlain)) *route = GroupRoute::Lds;
+  else *route = GroupRoute::General;
+  return SPX_OK;
+}
+
+// y may alias q on every route: every kernel finishes all reductions of a group (team barrier / wave lockstep) before
+// the group's first store, and the storing lane re-reads q[i] itself just before writing y[i].
+
+// Register tiles.  Ragged groups (CSR offsets + an upper bound on the sizes in group_size) use the same tiles through the 8-byte
+// loads; a group that exceeds the bound after all is handed to the general kernel.
+// VALUE (run_group_val below): the launches also form h at the result, see GroupVal.
+template <bool BINF, bool VALUE>
+static int group_route_reg(const GroupCall& c, double q_scale = 1.0, double* value = nullptr) {
+  using Tiles = typename std::conditional<BINF, GroupTilesBinf, GroupTilesPlain>::type;
+  spx_ctx* ctx = c.ctx;
+  const int64_t ngroups = c.ngroups;
   SPX_ON_DEVICE(ctx);
-  const int64_t cap_blocks = (int64_t)ctx->num_cu * 8;
-  const bool aligned = spx_aligned16(y) && spx_aligned16(q) && spx_aligned16(xk) && spx_aligned16(sj);
-  const bool ragged_reg = offsets && gsize > 0 && gsize <= 512;  // ragged groups with a size bound from the caller
-  if ((!offsets && gsize <= 512) || ragged_reg) {
-    // register path: the smallest (LPG, EPL) tile that holds a group; partly filled tiles are padded with zeros.
-    // Ragged groups (CSR offsets + an upper bound on the sizes in group_size) use the same tiles through the 8-byte
-    // loads; a group that exceeds the bound after all is handed to the general kernel.
-    int lpg, epl;
-    // Binf: as few lanes per group as the registers allow (4 x 4/8, 8 x 8/16, 16 x 16, 32 x 16 elements) -- the wave-uniform
-    // scalar work of the root find, which every lane executes, is then shared by more groups per wave
-    // Small groups (round 3): tiles that FIT -- a 4 x 4 tile spent four lanes' worth of root find (Binf) or reduction on a group
-    // of two, and three quarters of its loads on padding.  us per call at n = 1.6e7, old -> new tile (tools/r3/binf_small_groups.py):
-    // Binf groups of 2: 1305 -> 368, of 4: 680 -> 208, of 8: 317 -> 174, of 16: 155 -> 142; plain groups of 2: 508 -> 89, of 4:
-    // 283 -> 92, of 8: 162 -> 90, of 10: 132 -> 107.  (One lane per group beyond 8 elements loses more to the 64-byte strides
-    // between its lanes' loads than it saves: Binf 1 x 16 on groups of 16 270 us.)
-    if (BINF && gsize <= 2) { lpg = 1; epl = 2; }
-    else if (BINF && gsize <= 4) { lpg = 1; epl = 4; }
-    else if (BINF && gsize <= 8) { lpg = 1; epl = 8; }
-    else if (BINF && gsize <= 16) { lpg = 2; epl = 8; }
-    else if (BINF && gsize <= 32) { lpg = 4; epl = 8; }
-    else if (BINF && gsize <= 64) { lpg = 8; epl = 8; }  // (4 x 16 is slower here: 64-byte runs per group and load)
-    else if (BINF && gsize <= 128) { lpg = 8; epl = 16; }
-    else if (BINF && gsize <= 256) { lpg = 16; epl = 16; }
-    else if (BINF && gsize <= 512) { lpg = 32; epl = 16; }
-    else if (gsize <= 2) { lpg = 1; epl = 2; }
-    else if (gsize <= 4) { lpg = 2; epl = 4; }
-    else if (gsize <= 12) { lpg = 4; epl = 4; }
-    else if (gsize <= 32) { lpg = 16; epl = 2; }
-    else if (gsize <= 64) { lpg = 16; epl = 4; }
-    else if (gsize <= 128) { lpg = 16; epl = 8; }
-    else if (gsize <= 256) { lpg = 32; epl = 8; }
-    else if (gsize <= 384) { lpg = 64; epl = 6; }
-    else { lpg = 64; epl = 8; }
-    const int gpw = 64 / lpg;
-    int64_t blocks = (ngroups + 4 * gpw - 1) / (4 * gpw);  // 4 waves per 256-thread block
-    if (blocks > 0x7fffffff) blocks = 0x7fffffff;
-    dim3 grid((unsigned)blocks), block(256);
-    long long* deferred = nullptr;
-    unsigned long long *dcount = nullptr, *dclear = nullptr;
-    // VALUE: one reservation -- [deferred list | GroupValWs | partials and flags of the main launch | tile masks | dterm]
-    [[maybe_unused]] GroupVal gv_main{}, gv_last{};
-    [[maybe_unused]] GroupValWs* vws = nullptr;
-    if constexpr (VALUE) {
-      const size_t list_bytes = (BINF || ragged_reg) ? (((size_t)(ngroups + 1) * sizeof(long long) + 256 + 255) & ~(size_t)255) : 0;
-      // (a wavefront per tile: the masks of the handed-on groups are indexed by wavefront)
-      SPX_REQUIRE(blocks * 4 * gpw >= ngroups, "too many groups for the fused value form");
-      const size_t part_bytes = ((size_t)blocks * 2 * sizeof(double) + 255) & ~(size_t)255;  // partials | flags
-      const size_t mask_bytes = list_bytes ? (size_t)blocks * 4 * sizeof(unsigned long long) : 0;
-      rc = spx_ws_reserve(ctx, list_bytes + sizeof(GroupValWs) + part_bytes + mask_bytes + (list_bytes ? (size_t)ngroups * sizeof(double) : 0) + 256);
+  const bool ragged = c.offsets != nullptr;  // ragged groups with a size bound from the caller
+  const int lpg = Tiles::lpg(c.gsize);
+  const int gpw = 64 / lpg;
+  int64_t blocks = (ngroups + 4 * gpw - 1) / (4 * gpw);  // 4 waves per 256-thread block
+  if (blocks > 0x7fffffff) blocks = 0x7fffffff;
+  const dim3 grid((unsigned)blocks);
+  int rc;
+  long long* deferred = nullptr;
+  unsigned long long *dcount = nullptr, *dclear = nullptr;
+  // VALUE: one reservation -- [deferred list | GroupValWs | partials and flags of the main launch | tile masks | dterm]
+  GroupVal gv_main{}, gv_last{};
+  [[maybe_unused]] GroupValWs* vws = nullptr;
+  if constexpr (VALUE) {
+    const size_t list_bytes = (BINF || ragged) ? (((size_t)(ngroups + 1) * sizeof(long long) + 256 + 255) & ~(size_t)255) : 0;
+    // (a wavefront per tile: the masks of the handed-on groups are indexed by wavefront)
+    SPX_REQUIRE(blocks * 4 * gpw >= ngroups, "too many groups for the fused value form");
+    const size_t part_bytes = ((size_t)blocks * 2 * sizeof(double) + 255) & ~(size_t)255;  // partials | flags
+    const size_t mask_bytes = list_bytes ? (size_t)blocks * 4 * sizeof(unsigned long long) : 0;
+    rc = spx_ws_reserve(ctx, list_bytes + sizeof(GroupValWs) + part_bytes + mask_bytes + (list_bytes ? (size_t)ngroups * sizeof(double) : 0) + 256);
+    if (rc) return rc;
+    rc = spx_sync_ready(ctx);
+    if (rc) return rc;
+    vws = reinterpret_cast<GroupValWs*>(static_cast<char*>(ctx->ws) + list_bytes);
+    double* part = reinterpret_cast<double*>(vws + 1);
+    const bool one = !(BINF || ragged);  // the main launch is the call's last one
+    unsigned long long* dmask = one ? nullptr : reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(part) + part_bytes);
+    double* dterm = one ? nullptr : reinterpret_cast<double*>(reinterpret_cast<char*>(part) + part_bytes + mask_bytes);
+    gv_main = GroupVal{q_scale, part, one ? nullptr : part + blocks, (int)blocks, false, one ? spx_sync_header(ctx) : nullptr, vws, ctx->value_target, dmask, dterm, lpg};
+    gv_last = gv_main;
+    gv_last.behind = true;
+    gv_last.hdr = spx_sync_header(ctx);
+  }
+  if (BINF || ragged) {  // list of the groups whose bracket needs the reference's literal evaluation / oversize groups
+    if constexpr (!VALUE) {
+      rc = spx_ws_reserve(ctx, (size_t)(ngroups + 1) * sizeof(long long) + 256);
       if (rc) return rc;
+    }
+    deferred = reinterpret_cast<long long*>(ctx->ws);
+    dcount = reinterpret_cast<unsigned long long*>(deferred);
+    // Round 4: the zero-fill of the count word was a launch of its own in front of every call (a Binf call at solver sizes:
+    // 17 us against 10.5 for the plain operator, tools/r4/small_latency_all.py).  Uniform Binf layouts now count in one of
+    // two words of the synchronisation state (zero-initialised, never written by another operator): a call uses [set], its
+    // LIT launch -- queued unconditionally behind the main one -- zeroes [set ^ 1] for the next call.  Under a stream capture
+    // (one set would replay for ever) and for ragged layouts the word in front of the list and its zero-fill node stay.
+    const bool graph_safe = spx_graph_safe(ctx);
+    if (BINF && !ragged && ctx->tune_fewer_launches && !graph_safe) {
       rc = spx_sync_ready(ctx);
       if (rc) return rc;
-      vws = reinterpret_cast<GroupValWs*>(static_cast<char*>(ctx->ws) + list_bytes);
-      double* part = reinterpret_cast<double*>(vws + 1);
-      const bool one = !(BINF || ragged_reg);  // the main launch is the call's last one
-      unsigned long long* dmask = one ? nullptr : reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(part) + part_bytes);
-      double* dterm = one ? nullptr : reinterpret_cast<double*>(reinterpret_cast<char*>(part) + part_bytes + mask_bytes);
-      gv_main = GroupVal{q_scale, part, one ? nullptr : part + blocks, (int)blocks, false, one ? spx_sync_header(ctx) : nullptr, vws, ctx->value_target, dmask, dterm, lpg};
-      gv_last = gv_main;
-      gv_last.behind = true;
-      gv_last.hdr = spx_sync_header(ctx);
+      SpxSyncHeader* hdr = spx_sync_header(ctx);
+      dcount = reinterpret_cast<unsigned long long*>(&hdr->grp_deferred[ctx->track.grp_def_set]);
+      dclear = reinterpret_cast<unsigned long long*>(&hdr->grp_deferred[ctx->track.grp_def_set ^ 1]);
+      ctx->track.grp_def_set ^= 1;
+    } else {
+      rc = spx_zero_async(ctx, deferred, sizeof(long long)); if (rc) return rc;
     }
-    if (BINF || ragged_reg) {  // list of the groups whose bracket needs the reference's literal evaluation / oversize groups
-      if constexpr (!VALUE) {
-        rc = spx_ws_reserve(ctx, (size_t)(ngroups + 1) * sizeof(long long) + 256);
-        if (rc) return rc;
-      }
-      deferred = reinterpret_cast<long long*>(ctx->ws);
-      dcount = reinterpret_cast<unsigned long long*>(deferred);
-      // Round 4: the zero-fill of the count word was a launch of its own in front of every call (a Binf call at solver sizes:
-      // 17 us against 10.5 for the plain operator, tools/r4/small_latency_all.py).  Uniform Binf layouts now count in one of
-      // two words of the synchronisation state (zero-initialised, never written by another operator): a call uses [set], its
-      // LIT launch -- queued unconditionally behind the main one -- zeroes [set ^ 1] for the next call.  Under a stream capture
-      // (one set would replay for ever) and for ragged layouts the word in front of the list and its zero-fill node stay.
-      const bool graph_safe = spx_graph_safe(ctx);
-      if (BINF && !ragged_reg && ctx->tune_fewer_launches && !graph_safe) {
-        rc = spx_sync_ready(ctx);
-        if (rc) return rc;
-        SpxSyncHeader* hdr = spx_sync_header(ctx);
-        dcount = reinterpret_cast<unsigned long long*>(&hdr->grp_deferred[ctx->track.grp_def_set]);
-        dclear = reinterpret_cast<unsigned long long*>(&hdr->grp_deferred[ctx->track.grp_def_set ^ 1]);
-        ctx->track.grp_def_set ^= 1;
-      } else {
-        rc = spx_zero_async(ctx, deferred, sizeof(long long)); if (rc) return rc;
-      }
-    }
-    const bool pairs = !ragged_reg && (gsize & 1) == 0 && aligned;  // otherwise 8-byte loads
-    if (!BINF && ragged_reg)  // offsets need not span 0:n (src/shiftedGroupNormL2.jl:77 runs over every index)
-      hipLaunchKernelGGL(k_csr_uncovered<double>, dim3(256), dim3(256), 0, ctx->stream, y, xk, sj, offsets, ngroups, n);
-#define SPX_LAUNCH_REG(LPG, EPL)                                                                                    \
-  do {                                                                                                              \
-    if constexpr (VALUE && !group_tile_used(BINF, LPG, EPL)) {                                                      \
-      /* (a tile the other operator uses: never selected above, not instantiated with the value) */               \
-    } else if constexpr (VALUE) {                                                                                   \
-      if (pairs && gsize == (LPG) * (EPL)) {                                                                        \
-        hipLaunchKernelGGL((k_group_reg<LPG, EPL, BINF, true, false, true, true>), grid, block, 0, ctx->stream, y, q, xk, sj, \
-                           ngroups, (int)gsize, lambda, sigma, delta, deferred, (const int64_t*)nullptr, ctx->status_dev, ctx->tune_binf_literal, dcount, (unsigned long long*)nullptr, gv_main); \
-      } else if (pairs) {                                                                                           \
-        hipLaunchKernelGGL((k_group_reg<LPG, EPL, BINF, true, false, false, true>), grid, block, 0, ctx->stream, y, q, xk, sj, ngroups, \
-                           (int)gsize, lambda, sigma, delta, deferred, (const int64_t*)nullptr, ctx->status_dev, ctx->tune_binf_literal, dcount, (unsigned long long*)nullptr, gv_main); \
-      } else                                                                                                        \
-        hipLaunchKernelGGL((k_group_reg<LPG, EPL, BINF, false, false, false, true>), grid, block, 0, ctx->stream, y, q, xk, sj, ngroups, \
-                           (int)gsize, lambda, sigma, delta, deferred, ragged_reg ? offsets : (const int64_t*)nullptr, ctx->status_dev, ctx->tune_binf_literal, dcount, (unsigned long long*)nullptr, gv_main); \
-    } else if (pairs && gsize == (LPG) * (EPL)) {                                                                          \
-      hipLaunchKernelGGL((k_group_reg<LPG, EPL, BINF, true, false, true>), grid, block, 0, ctx->stream, y, q, xk, sj, \
-                         ngroups, (int)gsize, lambda, sigma, delta, deferred, (const int64_t*)nullptr, ctx->status_dev, ctx->tune_binf_literal, dcount, (unsigned long long*)nullptr, GroupNoVal{}); \
-    } else if (pairs) {                                                                                             \
-      hipLaunchKernelGGL((k_group_reg<LPG, EPL, BINF, true>), grid, block, 0, ctx->stream, y, q, xk, sj, ngroups,   \
-                         (int)gsize, lambda, sigma, delta, deferred, (const int64_t*)nullptr, ctx->status_dev, ctx->tune_binf_literal, dcount, (unsigned long long*)nullptr, GroupNoVal{});    \
-    } else                                                                                                            \
-      hipLaunchKernelGGL((k_group_reg<LPG, EPL, BINF, false>), grid, block, 0, ctx->stream, y, q, xk, sj, ngroups,  \
-                         (int)gsize, lambda, sigma, delta, deferred, ragged_reg ? offsets : (const int64_t*)nullptr, ctx->status_dev, ctx->tune_binf_literal, dcount, (unsigned long long*)nullptr, GroupNoVal{}); \
-  } while (0)
-    if (lpg == 1 && epl == 2) SPX_LAUNCH_REG(1, 2);
-    else if (lpg == 1 && epl == 4) SPX_LAUNCH_REG(1, 4);
-    else if (lpg == 1 && epl == 8) SPX_LAUNCH_REG(1, 8);
-    else if (lpg == 2 && epl == 4) SPX_LAUNCH_REG(2, 4);
-    else if (lpg == 2 && epl == 8) SPX_LAUNCH_REG(2, 8);
-    else if (lpg == 4 && epl == 4) SPX_LAUNCH_REG(4, 4);
-    else if (lpg == 4 && epl == 8) SPX_LAUNCH_REG(4, 8);
-    else if (lpg == 8 && epl == 8) { if constexpr (BINF) SPX_LAUNCH_REG(8, 8); }
-    else if (lpg == 8) { if constexpr (BINF) SPX_LAUNCH_REG(8, 16); }
-    else if (lpg == 16 && epl == 16) { if constexpr (BINF) SPX_LAUNCH_REG(16, 16); }
-    else if (lpg == 32 && epl == 16) { if constexpr (BINF) SPX_LAUNCH_REG(32, 16); }
-    else if (lpg == 16 && epl == 2) SPX_LAUNCH_REG(16, 2);
-    else if (lpg == 16 && epl == 4) SPX_LAUNCH_REG(16, 4);
-    else if (lpg == 16) SPX_LAUNCH_REG(16, 8);
-    else if (lpg == 32) SPX_LAUNCH_REG(32, 8);
-    else if (epl == 6) SPX_LAUNCH_REG(64, 6);
-    else SPX_LAUNCH_REG(64, 8);
-#undef SPX_LAUNCH_REG
+  }
+  const bool aligned = spx_aligned16(c.y) && spx_aligned16(c.q) && spx_aligned16(c.xk) && spx_aligned16(c.sj);
+  const GroupRegArgs args{c, deferred, dcount, !ragged && (c.gsize & 1) == 0 && aligned};
+  group_uncovered<BINF>(c);
+  Tiles::select(c.gsize, [&](auto row) {
+    launch_group_reg<decltype(row)::lpg, decltype(row)::epl, BINF, false, VALUE>(args, grid, nullptr, gv_main);
+  });
+  if (BINF && !ragged) {
+    // The deferred list (usually empty: the kernel returns at once) on register tiles as well.  The literal
+    // evaluation is ~60 dependent passes over a group; from memory (k_group_mem) a long list is bound by L2 misses.
     if constexpr (BINF) {
-      if (!ragged_reg) {
-        // The deferred list (usually empty: the kernel returns at once) on the same register tiles.  The literal
-        // evaluation is ~60 dependent passes over a group; from memory (k_group_mem) a long list is bound by L2 misses.
-        const dim3 lgrid((unsigned)(blocks < (int64_t)ctx->num_cu * 8 ? blocks : (int64_t)ctx->num_cu * 8));
-#define SPX_LAUNCH_LIT(LPG, EPL)                                                                                     \
-  do {                                                                                                               \
-    if constexpr (VALUE) {                                                                                           \
-      if (pairs)                                                                                                     \
-        hipLaunchKernelGGL((k_group_reg<LPG, EPL, true, true, true, false, true>), lgrid, block, 0, ctx->stream, y, q, xk, sj, \
-                           ngroups, (int)gsize, lambda, sigma, delta, deferred, (const int64_t*)nullptr, ctx->status_dev, ctx->tune_binf_literal, dcount, dclear, gv_last); \
-      else                                                                                                           \
-        hipLaunchKernelGGL((k_group_reg<LPG, EPL, true, false, true, false, true>), lgrid, block, 0, ctx->stream, y, q, xk, sj, \
-                           ngroups, (int)gsize, lambda, sigma, delta, deferred, (const int64_t*)nullptr, ctx->status_dev, ctx->tune_binf_literal, dcount, dclear, gv_last); \
-    } else if (pairs)                                                                                                \
-      hipLaunchKernelGGL((k_group_reg<LPG, EPL, true, true, true>), lgrid, block, 0, ctx->stream, y, q, xk, sj,      \
-                         ngroups, (int)gsize, lambda, sigma, delta, deferred, (const int64_t*)nullptr, ctx->status_dev, ctx->tune_binf_literal, dcount, dclear, GroupNoVal{}); \
-    else                                                                                                             \
-      hipLaunchKernelGGL((k_group_reg<LPG, EPL, true, false, true>), lgrid, block, 0, ctx->stream, y, q, xk, sj,     \
-                         ngroups, (int)gsize, lambda, sigma, delta, deferred, (const int64_t*)nullptr, ctx->status_dev, ctx->tune_binf_literal, dcount, dclear, GroupNoVal{}); \
-  } while (0)
-        // (its own tiles, by the group size: the list is short, the literal evaluation wants lanes)
-        if (gsize <= 16) SPX_LAUNCH_LIT(4, 4);
-        else if (gsize <= 32) SPX_LAUNCH_LIT(4, 8);
-        else if (gsize <= 64) SPX_LAUNCH_LIT(8, 8);
-        else if (gsize <= 128) SPX_LAUNCH_LIT(8, 16);
-        else if (gsize <= 256) SPX_LAUNCH_LIT(16, 16);
-        else SPX_LAUNCH_LIT(32, 16);
-#undef SPX_LAUNCH_LIT
-        SPX_LAUNCH_CHECK();
-        if constexpr (VALUE) return group_val_return(ctx, vws, value);
-        return SPX_OK;
-      }
+      const dim3 lgrid((unsigned)(blocks < (int64_t)ctx->num_cu * 8 ? blocks : (int64_t)ctx->num_cu * 8));
+      GroupTilesLit::select(c.gsize, [&](auto row) {
+        launch_group_reg<decltype(row)::lpg, decltype(row)::epl, true, true, VALUE>(args, lgrid, dclear, gv_last);
+      });
     }
-    if (BINF || ragged_reg) {  // usually an empty list: the kernel returns at once
-      if constexpr (VALUE)
-        hipLaunchKernelGGL((k_group_list_val<BINF>), dim3((unsigned)(ctx->num_cu * 2)), dim3(256), 0, ctx->stream, y, q, xk,
-                           sj, n, ragged_reg ? offsets : (const int64_t*)nullptr, gsize, ngroups, lambda, sigma, delta,
-                           (const long long*)deferred, ctx->status_dev, ctx->tune_binf_literal, gv_last);
-      else
-      hipLaunchKernelGGL((k_group_mem<64, BINF>), dim3((unsigned)(ctx->num_cu * 2)), dim3(256), 0, ctx->stream, y, q, xk,
-                         sj, n, ragged_reg ? offsets : (const int64_t*)nullptr, gsize, ngroups, lambda, sigma, delta,
-                         (const long long*)deferred, ctx->status_dev, ctx->tune_binf_literal, (const int*)nullptr, (int64_t)0);
-    }
-    SPX_LAUNCH_CHECK();
-    if constexpr (VALUE) return group_val_return(ctx, vws, value);
-    return SPX_OK;
+  } else if (ragged) {  // usually an empty list: the kernel returns at once
+    if constexpr (VALUE)
+      hipLaunchKernelGGL((k_group_list_val<BINF>), dim3((unsigned)(ctx->num_cu * 2)), dim3(256), 0, ctx->stream, c.y, c.q, c.xk,
+                         c.sj, c.n, c.offsets, c.gsize, ngroups, c.lambda, c.sigma, c.delta, (const long long*)deferred,
+                         ctx->status_dev, ctx->tune_binf_literal, gv_last);
+    else
+      hipLaunchKernelGGL((k_group_mem<64, BINF>), dim3((unsigned)(ctx->num_cu * 2)), dim3(256), 0, ctx->stream, c.y, c.q, c.xk,
+                         c.sj, c.n, c.offsets, c.gsize, ngroups, c.lambda, c.sigma, c.delta, (const long long*)deferred,
+                         ctx->status_dev, ctx->tune_binf_literal, (const int*)nullptr, (int64_t)0);
   }
-  if constexpr (VALUE) {  // (run_group_val composes the other routes from the plain operator and psi(y))
-    spx_set_error("internal: no fused value form for this group layout");
-    return SPX_ERR_INVALID_ARG;
-  }
-  // team width: wavefront per group unless groups are large on average
-  if (gsize > 512 && gsize <= (BINF ? kLdsGroupMax : kLdsGroupMaxPlain)) {
-    // 512 < group size (uniform) or size bound (ragged, CSR offsets): LDS-resident group per workgroup
-    if (!BINF && offsets)
-      hipLaunchKernelGGL(k_csr_uncovered<double>, dim3(256), dim3(256), 0, ctx->stream, y, xk, sj, offsets, ngroups, n);
-    const size_t dyn = (size_t)gsize * 2 * sizeof(double);
-    // per device (the attribute belongs to the function ON the current device) and cheap: set on every call that needs it,
-    // no process-wide cache that a second GPU or a second thread would find in the wrong state
-    if (dyn > 48 * 1024)
-      SPX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_group_lds<BINF>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, kLdsGroupMax * 2 * (int)sizeof(double)));
-    int64_t blocks = ngroups < cap_blocks ? ngroups : cap_blocks;
-    hipLaunchKernelGGL((k_group_lds<BINF>), dim3((unsigned)blocks), dim3(256), dyn, ctx->stream, y, q, xk, sj, n, offsets,
-                       gsize, ngroups, lambda, sigma, delta, ctx->tune_binf_literal);
-    SPX_LAUNCH_CHECK();
-    return SPX_OK;
-  }
-  // Large groups -- first of all ONE group over the whole vector, the reference's default GroupNormL2
-  // (src/groupNormL2.jl:30-31, shifted(NormL2(lambda), xk): src/shiftedGroupNormL2.jl:34-35): a team of workgroups per
-  // group (spx_group_team.hip) instead of one workgroup (n = 1e8: 384 ms plain / 1349 ms Binf that way).
+  SPX_LAUNCH_CHECK();
+  if constexpr (VALUE) return group_val_return(ctx, vws, value);
+  return SPX_OK;
+}
+
+// kGroupRegMax < group size (uniform) or size bound (ragged, CSR offsets) <= kLdsGroupMax[Plain]: LDS-resident group per workgroup
+template <bool BINF>
+static int group_route_lds(const GroupCall& c) {
+  spx_ctx* ctx = c.ctx;
+  SPX_ON_DEVICE(ctx);
+  group_uncovered<BINF>(c);
+  const size_t dyn = (size_t)c.gsize * 2 * sizeof(double);
+  // per device (the attribute belongs to the function ON the current device) and cheap: set on every call that needs it,
+  // no process-wide cache that a second GPU or a second thread would find in the wrong state
+  if (dyn > 48 * 1024)
+    SPX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_group_lds<BINF>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, kLdsGroupMax * 2 * (int)sizeof(double)));
+  const int64_t cap_blocks = (int64_t)ctx->num_cu * 8;
+  const int64_t blocks = c.ngroups < cap_blocks ? c.ngroups : cap_blocks;
+  hipLaunchKernelGGL((k_group_lds<BINF>), dim3((unsigned)blocks), dim3(256), dyn, ctx->stream, c.y, c.q, c.xk, c.sj, c.n, c.offsets,
+                     c.gsize, c.ngroups, c.lambda, c.sigma, c.delta, ctx->tune_binf_literal);
+  SPX_LAUNCH_CHECK();
+  return SPX_OK;
+}
+
+// Everything else: ragged groups without a size bound from the caller (or with one above the LDS-resident form's), and
+// large groups -- first of all ONE group over the whole vector, the reference's default GroupNormL2
+// (src/groupNormL2.jl:30-31, shifted(NormL2(lambda), xk): src/shiftedGroupNormL2.jl:34-35): a team of workgroups per
+// group (spx_group_team.hip) instead of one workgroup (n = 1e8: 384 ms plain / 1349 ms Binf that way).
+template <bool BINF>
+static int group_route_general(const GroupCall& c) {
+  spx_ctx* ctx = c.ctx;
+  const int64_t ngroups = c.ngroups;
+  SPX_ON_DEVICE(ctx);
   const int* big_active = nullptr;   // ragged layouts: device word of the team plan, "the large groups are taken care of"
   const int64_t big_min = (BINF ? kLdsGroupMax : kLdsGroupMaxPlain) + 1;  // ragged layouts: a group of at least this many elements is
                                                                           // a large one (what the LDS-resident kernel does not hold, as for uniform groups)
   if (ctx->tune_team) {
-    if (!offsets) {
+    if (!c.offsets) {
       const int tg = spx_group_team_max_grid(ctx, BINF);
       // (teams of ONE workgroup that take several groups in turn beat the one-workgroup-per-group kernels below at every count
       //  of large groups -- 1e8 elements in groups of 5000 ... 200 000: plain 0.88-1.07 -> 0.62-0.99 ms, Binf 2.0-3.4 -> 1.0-1.8 ms,
       //  tools/r4/team_crossover.py -- on chip up to 9216 elements, two passes instead of one per reduction beyond; tuning key 16
       //  = groups per workgroup up to which the team form is used, for that A/B)
       if (tg >= 1 && (ctx->tune_team_factor == 0 || ngroups < (int64_t)ctx->tune_team_factor * tg))
-        return spx_group_team_launch(ctx, BINF, y, q, xk, sj, n, nullptr, gsize, ngroups, lambda, sigma, delta);
+        return spx_group_team_launch(ctx, BINF, c.y, c.q, c.xk, c.sj, c.n, nullptr, c.gsize, ngroups, c.lambda, c.sigma, c.delta);
     } else if (ngroups <= 65536) {
-      rc = spx_group_team_plan(ctx, BINF, y, q, xk, sj, n, offsets, ngroups, big_min, &big_active);
+      const int rc = spx_group_team_plan(ctx, BINF, c.y, c.q, c.xk, c.sj, c.n, c.offsets, ngroups, big_min, &big_active);
       if (rc) return rc;
     }
   }
-  if (!BINF && offsets)
-    hipLaunchKernelGGL(k_csr_uncovered<double>, dim3(256), dim3(256), 0, ctx->stream, y, xk, sj, offsets, ngroups, n);
-  const double avg = (double)n / (double)ngroups;
-  if (avg <= 2048.0) {
-    // lanes per group by the average size (ragged groups without a size bound from the caller, or with one above 512): a
-    // whole wavefront per group of a handful of elements left most lanes idle (round 3)
-    const int team = avg <= 8.0 ? 4 : avg <= 24.0 ? 8 : avg <= 64.0 ? 16 : avg <= 160.0 ? 32 : 64;
-    const int tpb = 256 / team;
-    int64_t blocks = (ngroups + tpb - 1) / tpb;
-    if (blocks > cap_blocks) blocks = cap_blocks;
-#define SPX_LAUNCH_MEM(TEAM)                                                                                              \
-  hipLaunchKernelGGL((k_group_mem<TEAM, BINF>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, y, q, xk, sj, n, offsets, \
-                     gsize, ngroups, lambda, sigma, delta, (const long long*)nullptr, ctx->status_dev, ctx->tune_binf_literal, \
-                     big_active, big_min)
-    if (team == 4) SPX_LAUNCH_MEM(4);
-    else if (team == 8) SPX_LAUNCH_MEM(8);
-    else if (team == 16) SPX_LAUNCH_MEM(16);
-    else if (team == 32) SPX_LAUNCH_MEM(32);
-    else SPX_LAUNCH_MEM(64);
-#undef SPX_LAUNCH_MEM
-  } else {
-    int64_t blocks = ngroups < cap_blocks ? ngroups : cap_blocks;
-    hipLaunchKernelGGL((k_group_mem<256, BINF>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, y, q, xk, sj, n,
-                       offsets, gsize, ngroups, lambda, sigma, delta, (const long long*)nullptr, ctx->status_dev, ctx->tune_binf_literal,
-                       big_active, big_min);
-  }
+  group_uncovered<BINF>(c);
+  const int team = spx_group_lanes_by_avg((double)c.n / (double)ngroups);
+  const int tpb = 256 / team;
+  const int64_t cap_blocks = (int64_t)ctx->num_cu * 8;
+  int64_t blocks = (ngroups + tpb - 1) / tpb;
+  if (blocks > cap_blocks) blocks = cap_blocks;
+  spx_with_lanes<4, 8, 16, 32, 64, 256>(team, [&](auto lanes) {
+    hipLaunchKernelGGL((k_group_mem<decltype(lanes)::value, BINF>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, c.y, c.q, c.xk,
+                       c.sj, c.n, c.offsets, c.gsize, ngroups, c.lambda, c.sigma, c.delta, (const long long*)nullptr, ctx->status_dev,
+                       ctx->tune_binf_literal, big_active, big_min);
+  });
   SPX_LAUNCH_CHECK();
   if (big_active)  // the large groups of a ragged layout (the kernel returns at once when the plan found none)
-    return spx_group_team_launch(ctx, BINF, y, q, xk, sj, n, offsets, gsize, ngroups, lambda, sigma, delta);
+    return spx_group_team_launch(ctx, BINF, c.y, c.q, c.xk, c.sj, c.n, c.offsets, c.gsize, ngroups, c.lambda, c.sigma, c.delta);
   return SPX_OK;
+}
+
+// The prox on the route group_classify named.
+template <bool BINF>
+static int group_run(const GroupCall& c, GroupRoute route) {
+  switch (route) {
+    case GroupRoute::Reg: return group_route_reg<BINF, false>(c);
+    case GroupRoute::Lds: return group_route_lds<BINF>(c);
+    case GroupRoute::General: return group_route_general<BINF>(c);
+    case GroupRoute::None: break;
+  }
+  // no group at all: ShiftedGroupNormL2 still subtracts the shift everywhere (:77)
+  if (c.n == 0 || BINF || !c.offsets) return SPX_OK;
+  SPX_ON_DEVICE(c.ctx);
+  group_uncovered<BINF>(c);
+  SPX_LAUNCH_CHECK();
+  return SPX_OK;
+}
+
+template <bool BINF>
+static int run_group(const GroupCall& c) {
+  GroupRoute route;
+  const int rc = group_classify<BINF>(c, &route);
+  if (rc) return rc;
+  return group_run<BINF>(c, route);
 }
 
 SPX_EXPORT int spx_prox_group_l2(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj,
                                  int64_t n, const int64_t* group_offsets, int64_t group_size, int64_t ngroups,
                                  const double* lambda_vec, double sigma) {
-  return run_group<false>(ctx, y, q, xk, sj, n, group_offsets, group_size, ngroups, lambda_vec, sigma, 0.0);
+  return run_group<false>({ctx, y, q, xk, sj, n, group_offsets, group_size, ngroups, lambda_vec, sigma, 0.0});
 }
 
 SPX_EXPORT int spx_prox_group_l2_binf(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj,
                                       int64_t n, const int64_t* group_offsets, int64_t group_size, int64_t ngroups,
                                       const double* lambda_vec, double sigma, double delta) {
-  return run_group<true>(ctx, y, q, xk, sj, n, group_offsets, group_size, ngroups, lambda_vec, sigma, delta);
+  return run_group<true>({ctx, y, q, xk, sj, n, group_offsets, group_size, ngroups, lambda_vec, sigma, delta});
 }
 
 // ---------------------------------------------------------------------------------------------
-// prox! fused with h at the result (include/spx.h, "group forms").  Register-tile routes (uniform groups of at most 512
-// elements, CSR offsets with a size bound of at most 512): the value comes out of the launches that store y.  Every other
-// route (LDS-resident groups, the general kernels, teams of workgroups): composed in this call -- y = q_scale * q where the
-// scale is not 1, the unchanged prox at q := y, then the one-launch psi(y) (spx_obj_group_l2) on the same stream.
+// prox! fused with h at the result (include/spx.h, "group forms").  The register-tile route: the value comes out of the
+// launches that store y.  Every other route (LDS-resident groups, the general kernels, teams of workgroups): composed in
+// this call -- y = q_scale * q where the scale is not 1, the unchanged prox at q := y, then the one-launch psi(y)
+// (spx_obj_group_l2) on the same stream.
 // ---------------------------------------------------------------------------------------------
 template <bool BINF>
-static int run_group_val(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
-                         const int64_t* offsets, int64_t gsize, int64_t ngroups, const double* lambda, double sigma,
-                         double delta, double q_scale, double* value) {
+static int run_group_val(const GroupCall& c, double q_scale, double* value) {
   SPX_REQUIRE(value != nullptr, "value is NULL");
-  int rc = spx_check_common(ctx, y, q, xk, sj, n);
+  GroupRoute route;
+  int rc = group_classify<BINF>(c, &route);
   if (rc) return rc;
-  SPX_REQUIRE(ngroups >= 0, "ngroups < 0");
-  if (n > 0 && ngroups > 0) {  // (run_group's checks, before the first launch of a composed call)
-    SPX_REQUIRE(lambda != nullptr, "lambda_vec is NULL");
-    if (!offsets) {
-      SPX_REQUIRE(gsize > 0, "group_size <= 0 with NULL group_offsets");
-      SPX_REQUIRE(ngroups <= n / gsize && ngroups * gsize == n, "ngroups * group_size != n");
-    }
-  }
+  spx_ctx* ctx = c.ctx;
   if (!ctx->value_target) {  // (refused before anything is enqueued)
     const int rcc = spx_require_not_capturing(ctx, "returning the value to the host");
     if (rcc) return rcc;
   }
   *value = 0.0;
-  if (n == 0 || ngroups == 0) {  // h of no group at all; y as the plain operator leaves it (it does not read q)
-    rc = run_group<BINF>(ctx, y, q, xk, sj, n, offsets, gsize, ngroups, lambda, sigma, delta);
+  if (route == GroupRoute::Reg) return group_route_reg<BINF, true>(c, q_scale, value);
+  if (route == GroupRoute::None) {  // h of no group at all; y as the plain operator leaves it (it does not read q)
+    rc = group_run<BINF>(c, route);
     if (rc) return rc;
     if (ctx->value_target) return spx_zero_async(ctx, ctx->value_target, sizeof(double));
     return SPX_OK;
   }
-  if ((!offsets && gsize <= 512) || (offsets && gsize > 0 && gsize <= 512))
-    return run_group<BINF, true>(ctx, y, q, xk, sj, n, offsets, gsize, ngroups, lambda, sigma, delta, q_scale, value);
-  const double* qq = q;
+  GroupCall scaled = c;
   if (q_scale != 1.0) {
     SPX_ON_DEVICE(ctx);
-    int64_t eb = (n + 255) / 256;
+    int64_t eb = (c.n + 255) / 256;
     if (eb > (int64_t)ctx->num_cu * 8) eb = (int64_t)ctx->num_cu * 8;
-    hipLaunchKernelGGL(k_group_scale, dim3((unsigned)eb), dim3(256), 0, ctx->stream, y, q, q_scale, n, offsets, ngroups);
+    hipLaunchKernelGGL(k_group_scale, dim3((unsigned)eb), dim3(256), 0, ctx->stream, c.y, c.q, q_scale, c.n, c.offsets, c.ngroups);
     SPX_LAUNCH_CHECK();
-    qq = y;
+    scaled.q = c.y;
   }
-  rc = run_group<BINF>(ctx, y, qq, xk, sj, n, offsets, gsize, ngroups, lambda, sigma, delta);
+  rc = group_run<BINF>(scaled, route);
   if (rc) return rc;
-  return spx_obj_group_l2(ctx, y, xk, sj, n, offsets, gsize, ngroups, lambda, value);
+  return spx_obj_group_l2(ctx, c.y, c.xk, c.sj, c.n, c.offsets, c.gsize, c.ngroups, c.lambda, value);
 }
 
 SPX_EXPORT int spx_proxval_group_l2(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
                                     const int64_t* group_offsets, int64_t group_size, int64_t ngroups,
                                     const double* lambda_vec, double sigma, double q_scale, double* value) {
-  return run_group_val<false>(ctx, y, q, xk, sj, n, group_offsets, group_size, ngroups, lambda_vec, sigma, 0.0, q_scale, value);
+  return run_group_val<false>({ctx, y, q, xk, sj, n, group_offsets, group_size, ngroups, lambda_vec, sigma, 0.0}, q_scale, value);
 }
 
 SPX_EXPORT int spx_proxval_group_l2_binf(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj,
                                          int64_t n, const int64_t* group_offsets, int64_t group_size, int64_t ngroups,
                                          const double* lambda_vec, double sigma, double delta, double q_scale,
                                          double* value) {
-  return run_group_val<true>(ctx, y, q, xk, sj, n, group_offsets, group_size, ngroups, lambda_vec, sigma, delta, q_scale, value);
+  return run_group_val<true>({ctx, y, q, xk, sj, n, group_offsets, group_size, ngroups, lambda_vec, sigma, delta}, q_scale, value);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1182,26 +1193,14 @@ static int run_group_gather(spx_ctx* ctx, double* y, const double* q, const doub
     SPX_HIP(hipStreamSynchronize(ctx->stream));
     if (hflag & 2) { spx_set_error("invalid argument: group_ptr is not a non-decreasing sequence inside [0, nnz]"); return SPX_ERR_INVALID_ARG; }
     if (hflag & 1) { spx_set_error("invalid argument: group index outside [0, n) (BoundsError)"); return SPX_ERR_INVALID_ARG; }
-    const double avg = (double)nnz / (double)ngroups;
-    if (avg <= 2048.0) {
-      const int team = avg <= 8.0 ? 4 : avg <= 24.0 ? 8 : avg <= 64.0 ? 16 : avg <= 160.0 ? 32 : 64;  // (as run_group)
-      const int tpb = 256 / team;
-      int64_t tb = (ngroups + tpb - 1) / tpb;
-      if (tb > cap_blocks) tb = cap_blocks;
-#define SPX_LAUNCH_GATHER(TEAM)                                                                                           \
-  hipLaunchKernelGGL((k_group_gather<TEAM, BINF>), dim3((unsigned)tb), dim3(256), 0, ctx->stream, y, sol, xk, sj, owner, ptr, \
-                     index, ngroups, lambda, sigma, delta, ctx->tune_binf_literal)
-      if (team == 4) SPX_LAUNCH_GATHER(4);
-      else if (team == 8) SPX_LAUNCH_GATHER(8);
-      else if (team == 16) SPX_LAUNCH_GATHER(16);
-      else if (team == 32) SPX_LAUNCH_GATHER(32);
-      else SPX_LAUNCH_GATHER(64);
-#undef SPX_LAUNCH_GATHER
-    } else {
-      int64_t blocks = ngroups < cap_blocks ? ngroups : cap_blocks;
-      hipLaunchKernelGGL((k_group_gather<256, BINF>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, y, sol, xk, sj,
+    const int team = spx_group_lanes_by_avg((double)nnz / (double)ngroups);
+    const int tpb = 256 / team;
+    int64_t tb = (ngroups + tpb - 1) / tpb;
+    if (tb > cap_blocks) tb = cap_blocks;
+    spx_with_lanes<4, 8, 16, 32, 64, 256>(team, [&](auto lanes) {
+      hipLaunchKernelGGL((k_group_gather<decltype(lanes)::value, BINF>), dim3((unsigned)tb), dim3(256), 0, ctx->stream, y, sol, xk, sj,
                          owner, ptr, index, ngroups, lambda, sigma, delta, ctx->tune_binf_literal);
-    }
+    });
   }
   // :77 subtracts the shift at EVERY index; the Binf form does so per group (:116) and leaves the rest of y alone
   if (!BINF) hipLaunchKernelGGL(k_gather_rest, dim3((unsigned)eb), dim3(256), 0, ctx->stream, y, xk, sj, owner, n);

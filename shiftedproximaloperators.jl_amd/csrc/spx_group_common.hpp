@@ -1,9 +1,11 @@
 // spx_group_common.hpp -- device code shared by the group kernels (spx_group.hip: register tiles, wavefront / workgroup per
 // group; spx_group_team.hip: a TEAM OF WORKGROUPS per group): team reductions, element providers, the Binf root find
 // (src/shiftedGroupNormL2Binf.jl:85-108) and the per-group body (src/shiftedGroupNormL2.jl:67-76, shiftedGroupNormL2Binf.jl:84-117).
-// k_csr_uncovered, at the end, serves both precisions (spx_group.hip, spx_group_f32.hip).
+// k_csr_uncovered, at the end, serves both precisions (spx_group.hip, spx_group_f32.hip); behind it, the host's choice of the
+// lanes per group for the kernels that take that width as a template argument.
 #pragma once
 #include <cmath>
+#include <type_traits>
 
 #include "spx_common.hpp"
 
@@ -1006,4 +1008,24 @@ __global__ __launch_bounds__(256) void k_csr_uncovered(T* y, const T* xk, const 
     const int64_t i = (t < head) ? t : tail0 + (t - head);
     y[i] = y[i] - (xk[i] + sj[i]);
   }
+}
+
+// ---------------------------------------------------------------------------------------------
+// host side: lanes per group of the kernels that re-read a group from memory
+// ---------------------------------------------------------------------------------------------
+// By the average group size (k_group_mem, k_group_gather): 4 ... 64 lanes of a wavefront -- a whole wavefront per group of a
+// handful of elements left most lanes idle (round 3) -- and the 256-lane workgroup above 2048 elements.
+static inline int spx_group_lanes_by_avg(double avg) {
+  return avg <= 8.0 ? 4 : avg <= 24.0 ? 8 : avg <= 64.0 ? 16 : avg <= 160.0 ? 32 : avg <= 2048.0 ? 64 : 256;
+}
+// About four elements per lane of a typical group (k_group_l2_f32, k_obj_group): 1 ... 64 lanes.
+static inline int spx_group_lanes_by_typical(int64_t typical) {
+  int lanes = 1;
+  while (lanes < 64 && (int64_t)lanes * 4 < typical) lanes *= 2;
+  return lanes;
+}
+// f(std::integral_constant<int, W>{}) for the W among WS... that equals lanes: the runtime width as a template argument.
+template <int... WS, class F>
+static inline bool spx_with_lanes(int lanes, F&& f) {
+  return ((lanes == WS ? (f(std::integral_constant<int, WS>{}), true) : false) || ...);
 }

@@ -75,25 +75,15 @@ SPX_EXPORT int spx_prox_group_l2_f32(spx_ctx* ctx, float* y, const float* q, con
     SPX_REQUIRE(ngroups <= n / group_size && ngroups * group_size == n, "ngroups * group_size != n");
   }
   const int64_t typical = group_size > 0 ? group_size : (n + ngroups - 1) / ngroups;
-  int team = 1;
-  while (team < 64 && (int64_t)team * 4 < typical) team *= 2;
+  const int team = spx_group_lanes_by_typical(typical);
   const int gpw = 64 / team;
   int64_t blocks = (ngroups + 4 * gpw - 1) / (4 * gpw);
   const int64_t cap = (int64_t)ctx->num_cu * 16;
   if (blocks > cap) blocks = cap;
-#define SPX_GROUP_F32(TEAM)                                                                                             \
-  hipLaunchKernelGGL(k_group_l2_f32<TEAM>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, y, q, xk, sj, n, group_offsets, \
-                     group_size, ngroups, lambda_vec, sigma)
-  switch (team) {
-    case 1: SPX_GROUP_F32(1); break;
-    case 2: SPX_GROUP_F32(2); break;
-    case 4: SPX_GROUP_F32(4); break;
-    case 8: SPX_GROUP_F32(8); break;
-    case 16: SPX_GROUP_F32(16); break;
-    case 32: SPX_GROUP_F32(32); break;
-    default: SPX_GROUP_F32(64); break;
-  }
-#undef SPX_GROUP_F32
+  spx_with_lanes<1, 2, 4, 8, 16, 32, 64>(team, [&](auto lanes) {
+    hipLaunchKernelGGL(k_group_l2_f32<decltype(lanes)::value>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, y, q, xk, sj, n,
+                       group_offsets, group_size, ngroups, lambda_vec, sigma);
+  });
   SPX_LAUNCH_CHECK();
   return SPX_OK;
 }

@@ -902,7 +902,7 @@ extern "C" __attribute__((visibility("default"))) int spx_debug_team_stamps(unsi
 #endif
 
 // ---------------------------------------------------------------------------------------------
-// Host side: called by run_group (spx_group.hip) for contiguous groups too large for its one-workgroup-per-group kernels.
+// Host side: called by group_route_general (spx_group.hip) for contiguous groups too large for its one-workgroup-per-group kernels.
 //   uniform groups (offsets == NULL):  spx_group_team_launch
 //   CSR offsets:  spx_group_team_plan (k_team_plan: which groups are large, which workgroups own them; *active_dev points at
 //   the plan's `active` word, which the caller's kernel for the OTHER groups reads to skip the large ones), the caller's

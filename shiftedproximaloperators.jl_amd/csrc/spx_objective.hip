@@ -15,7 +15,7 @@
 #include <cmath>
 #include <limits>
 
-#include "spx_common.hpp"
+#include "spx_group_common.hpp"  // (the lanes-per-group helpers; no kernel of it is instantiated here)
 
 namespace {
 
@@ -624,8 +624,7 @@ int run_obj_group(spx_ctx* ctx, const T* y, const T* xk, const T* sj, int64_t n,
   }
   // lanes per group: about four elements per lane of a typical group (uniform size, the caller's size bound, or the average)
   const int64_t typical = gsize > 0 ? gsize : (ngroups > 0 ? ((index ? nnz : n) + ngroups - 1) / ngroups : 1);
-  int team = 1;
-  while (team < 64 && (int64_t)team * 4 < typical) team *= 2;
+  const int team = spx_group_lanes_by_typical(typical);
   const int gpw = 64 / team;
   int64_t blocks = (ngroups + 4 * gpw - 1) / (4 * gpw);
   if (blocks > kObjBlocks) blocks = kObjBlocks;
@@ -640,28 +639,18 @@ int run_obj_group(spx_ctx* ctx, const T* y, const T* xk, const T* sj, int64_t n,
   if (!fin.hdr) { const int rz = spx_zero_async(ctx, &ws->infeasible, sizeof(int)); if (rz) return rz; }
   constexpr bool kF64 = std::is_same<T, double>::value;
   const bool pairs = kF64 && !offsets && !index && gsize > 0 && (gsize & 1) == 0 && spx_aligned16(y) && spx_aligned16(xk) && spx_aligned16(sj);
-#define SPX_OBJ_GROUP(TEAM)                                                                                                  \
-  do {                                                                                                                       \
-    if constexpr (kF64) {                                                                                                    \
-      if (pairs) {                                                                                                           \
-        hipLaunchKernelGGL((k_obj_group<T, MODE, TEAM, true>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, y, xk, sj, n, \
-                           offsets, gsize, ngroups, index, nnz, lambda, rad, ws, fin);                                       \
-        break;                                                                                                               \
-      }                                                                                                                      \
-    }                                                                                                                        \
-    hipLaunchKernelGGL((k_obj_group<T, MODE, TEAM>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, y, xk, sj, n, offsets, \
-                       gsize, ngroups, index, nnz, lambda, rad, ws, fin);                                                    \
-  } while (0)
-  switch (team) {
-    case 1: SPX_OBJ_GROUP(1); break;
-    case 2: SPX_OBJ_GROUP(2); break;
-    case 4: SPX_OBJ_GROUP(4); break;
-    case 8: SPX_OBJ_GROUP(8); break;
-    case 16: SPX_OBJ_GROUP(16); break;
-    case 32: SPX_OBJ_GROUP(32); break;
-    default: SPX_OBJ_GROUP(64); break;
-  }
-#undef SPX_OBJ_GROUP
+  spx_with_lanes<1, 2, 4, 8, 16, 32, 64>(team, [&](auto lanes) {
+    constexpr int TEAM = decltype(lanes)::value;
+    if constexpr (kF64) {
+      if (pairs) {
+        hipLaunchKernelGGL((k_obj_group<T, MODE, TEAM, true>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, y, xk, sj, n,
+                           offsets, gsize, ngroups, index, nnz, lambda, rad, ws, fin);
+        return;
+      }
+    }
+    hipLaunchKernelGGL((k_obj_group<T, MODE, TEAM>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, y, xk, sj, n, offsets,
+                       gsize, ngroups, index, nnz, lambda, rad, ws, fin);
+  });
   if (MODE == 2 && offsets) {  // the groups need not tile 0:n: the trust-region indicator covers every index
     int64_t sb = (n + 256 * 8 - 1) / (256 * 8);
     if (sb > kObjBlocks) sb = kObjBlocks;

@@ -455,7 +455,8 @@ def _binf_check(orc, y, ref, q, x, sj, lam, sigma, delta, offsets, what=""):
 
 
 @pytest.mark.parametrize("gsize", [64, 128, 256, 512, 1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 13, 16, 17, 33, 66, 100, 130, 250, 257,
-                                   383, 386, 510, 511, 513, 1024, 2048, 2049, 3000, 4096, 4097, 8200])
+                                   383, 386, 510, 511, 513, 1024, 2048, 2049, 3000, 4096, 4097, 8200,
+                                   9, 32, 65, 129, 384, 385])  # (the last six: just above / at the tile tables' bounds)
 @pytest.mark.parametrize("binf", [False, True])
 @pytest.mark.parametrize("misaligned", [False, True])
 def test_group_uniform(s, orc, gsize, binf, misaligned):
