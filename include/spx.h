@@ -370,6 +370,33 @@ int spx_prox_l1_b2(spx_ctx* ctx, double* y, const double* q, const double* xk, c
  * written on the host (synchronous). */
 int spx_obj_l1_b2(spx_ctx* ctx, const double* y, const double* xk, const double* sj, int64_t n, double lambda,
                   double delta, double* value);
+/* prox! fused with the value of h at the result -- the semantics of spx_proxval_* of the separable operators and of
+ * spx_proxval_group_l2 on the pair a trust-region iteration makes on this operator: `prox!(s, psi, -nu grad, nu)`, then
+ * `h(xk + s)`.  ONE launch, the launch of spx_prox_l1_b2 with the value formed on the way.
+ *   y      : bit-identical to spx_prox_l1_b2 called on q_scale * q -- on every form (register-resident, xk in LDS, streaming
+ *            with 16-byte accesses, streaming with 8-byte accesses), with y aliasing q exactly or not, with the trust region
+ *            active or inactive, whichever pass of the launch ends up being the one whose stores stand.  q_scale * q[i] is
+ *            ONE rounded multiply formed before `sj[i] + ...` (never contracted): the same bits as scaling q beforehand.
+ *            Pass 1.0 for q itself.  y == q is allowed with any q_scale: each lane reads its q before it stores the same
+ *            element.
+ *   *value : lambda * sum_i |(xk[i] + sj[i]) + y[i]|, formed from the STORED y in the association of spx_obj_l1_b2 -- i.e.
+ *            the h part of what spx_obj_l1_b2 returns on that y, up to the order of the (non-negative) sums.  The h part
+ *            only: no IndBallL2(Delta) term, the convention of the Box and Binf forms of spx_proxval_*: the prox lies in
+ *            the ball by construction.  Every sum is formed in a fixed order (static partition of the vector over the
+ *            workgroups in every pass that stores y, partial sums exchanged in workgroup order): repeating the call gives
+ *            the same bits, and the value does not depend on which workgroup happened to take which tile.
+ *   return : as the other spx_proxval_*: without a device value target the call synchronises and writes the host double;
+ *            with spx_ctx_set_value_target the kernel stores the device double (one 8-byte store), *value is NaN and nothing
+ *            is read back.  A launch poisoned by an expired wait stores NaN as the value, and NaN in y as spx_prox_l1_b2
+ *            does.  n == 0: value 0 (on the host, or the device target zeroed).  value == NULL is SPX_ERR_INVALID_ARG,
+ *            nothing launched.  Capturable exactly where spx_prox_l1_b2 is, given a device value target and one warm-up call.
+ * FUSED route -- all four forms: the value comes out of the launch that stores y, nothing is read a second time.  The grid
+ * and the form are the ones spx_prox_l1_b2 takes for the same arguments (y's bits depend on the partition of its sums).
+ * COMPOSED route -- none: no form composes y = q_scale * q, the plain prox and spx_obj_l1 inside this call.  (The fused
+ * kernel of the 8-byte streaming form is the one instantiation that gains scratch over its plain twin, 20 B per lane; whether
+ * that form should compose instead is decided by tools/b2_proxval_timing.py on vectors of mixed alignment.) */
+int spx_proxval_l1_b2(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
+                      double lambda, double sigma, double delta, double chi_lambda, double q_scale, double* value);
 
 /* ---- group operators -------------------------------------------------------------------- */
 /* Groups are contiguous index ranges (the reference's `idx` entries as UnitRanges / [:]):

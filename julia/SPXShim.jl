@@ -337,6 +337,21 @@ function prox_value!(y::DVec, ψ::ShiftedGroupNormL2Binf{Float64, RR, I, <:DVec,
   group_value_call(y, ψ, q, σ, q_scale, ψ.Δ)   # the h part of ψ(y): the prox lies inside the trust region
 end
 
+# prox! fused with h at the result, ShiftedNormL1B2 (spx_proxval_l1_b2): the one launch of prox! with λ‖xk + sj + y‖₁ formed
+# from the stored y on the way -- the h part of ψ(y): the prox lies inside the ℓ2 ball.  (Like the rest of this shim, never
+# executed where the library is built and tested: there is no Julia toolchain there.)
+function prox_value!(y::DVec, ψ::ShiftedProximalOperators.ShiftedNormL1B2{Float64, <:DVec, <:DVec, <:DVec}, q::DVec, σ::Float64;
+                     q_scale::Float64 = 1.0)   # prox at q_scale .* q (TR: q = ∇fk, q_scale = -ν)
+  n = length(ψ.xk)
+  (length(y) == n && length(q) == n) || throw(BoundsError())
+  out = Ref{Cdouble}(0.0)
+  check(ccall((:spx_proxval_l1_b2, libspx), Cint,
+              (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int64, Cdouble, Cdouble, Cdouble, Cdouble,
+               Cdouble, Ptr{Cdouble}),
+              ctx(), dptr(y), dptr(q), dptr(ψ.xk), dptr(ψ.sj), n, ψ.λ, σ, ψ.Δ, ψ.χ.lambda, q_scale, out))
+  return y, out[]
+end
+
 # ---------------------------------------------------------------------------------------------
 # ψ(y)                        src/ShiftedProximalOperators.jl:51-54, shiftedNormL1Box.jl:70-82 (idem L0Box, L½Box),
 #                             shiftedIndBallL0BInf.jl:44-49, shiftedGroupNormL2Binf.jl:34-39

@@ -188,11 +188,45 @@ constexpr double kB2Bracket = 1.5e-2;   // half-width of the bracket around the 
 // LDSX (round 3; REG with 1024 lanes x 16 elements): xk sits in LDS (128 KiB), sj + q in registers and the box ends are formed
 // from it on the fly -- 16 Ki elements per workgroup, 4 Mi on 256 CUs, where the streaming form pays for its sample, its
 // bracket and two passes over memory (n = 4e6: 111 us per call).
-template <bool REG, int EPL, int THREADS, bool VEC, bool LDSX = false>
+//
+// VALUE (spx_proxval_l1_b2): the prox is taken at qs * q (one rounded multiply in front of `sj + ...`, at every read of q),
+// and the launch also forms h at the result, lambda sum |(xk + sj) + y| over the STORED y.  y is stored at five sites and any
+// of them can be the store that stands (store_pass: register and streaming branch; pass_small(store); pass_stream(store); the
+// speculative pass and the first streaming pass under store_first): at each the lane holds x, s and the stored o and adds
+// fabs((x + s) + o) to ONE accumulator (hv), reset at the start of every storing pass -- a later pass supersedes an earlier
+// one.  At the exit that follows the store that stands (the two early returns, the end of store_pass) one more exchange gives
+// every workgroup the total (row 63: never reached by a reduction; its word 7 of slot 0 is the tile counter, word 0 of every
+// slot is free), and lane 0 of workgroup 0 stores lambda * total (NaN after an expired wait).  The storing passes keep the
+// STATIC partition: the sum a workgroup forms must not depend on which tiles it happened to be handed.
+// The extra arguments travel as a trailing pack that is EMPTY for the plain prox: its signature -- the offsets of the
+// implicit arguments behind it included -- and with it its device code are what they were before VALUE existed.
+struct B2Val {
+  double qs;      // q_scale
+  double lambda;  // h = lambda ||.||_1
+  double* out;    // device double that receives the value
+};
+__device__ __forceinline__ B2Val b2_val(B2Val v) { return v; }
+// q as the prox reads it: qs * q, ONE rounded multiply (-ffp-contract=off: never contracted into the sum that follows); q itself
+// for the plain prox.  (The streaming forms and the tails.  The loads of the register-resident forms write the product out
+// under `if constexpr`: even an identity call there changes the code of the PLAIN kernel -- in the arm of the select it
+// makes the clamped-index loads conditional, next to it it renames registers.)
+template <bool VALUE>
+__device__ __forceinline__ double b2_qs(double qs, double qv) { if constexpr (VALUE) return qs * qv; else return qv; }
+template <bool VALUE>
+__device__ __forceinline__ f64x2 b2_qs(double qs, f64x2 a) { if constexpr (VALUE) return f64x2{qs * a.x, qs * a.y}; else return a; }
+
+template <bool REG, int EPL, int THREADS, bool VEC, bool LDSX = false, bool VALUE = false, class... VA>
 __global__ __launch_bounds__(THREADS) void k_b2_coop(double* y, const double* q, const double* xk, const double* sj, int64_t n,
                                                    double ls, double delta, double chil, unsigned long long* rows,
                                                    unsigned long long* clear_rows, int clear_g, SpxSyncHeader* hdr,
-                                                   int can_spec, f64x2* cand, unsigned int cand_cap) {
+                                                   int can_spec, f64x2* cand, unsigned int cand_cap, VA... va) {
+  static_assert(sizeof...(VA) == (VALUE ? 1 : 0), "VALUE: one B2Val behind the plain arguments");
+  double qsc = 1.0, vlam = 0.0, hv = 0.0;  // (VALUE) q_scale, lambda, this lane's sum of |(xk + sj) + y| over the pass that stores y
+  double* vout = nullptr;
+  if constexpr (VALUE) {
+    const B2Val bv = b2_val(va...);
+    qsc = bv.qs; vlam = bv.lambda; vout = bv.out;
+  }
   __shared__ double lds6[6][16];
   const int t = threadIdx.x;
   const int G = (int)gridDim.x;
@@ -229,7 +263,9 @@ __global__ __launch_bounds__(THREADS) void k_b2_coop(double* y, const double* q,
         const int64_t i = gtid + (int64_t)k * NT;
         const int64_t ic = i < n ? i : n - 1;
         const double xv = __builtin_nontemporal_load(xk + ic), sv = __builtin_nontemporal_load(sj + ic), qv = __builtin_nontemporal_load(q + ic);
-        SQ[k] = i < n ? (sv + qv) : 0.0;   // `sj .+ q` (:56)
+        // (VALUE: the scaled q written out in a branch of its own -- even an inlined identity call here reorders the plain kernel's code)
+        if constexpr (VALUE) SQ[k] = i < n ? (sv + qsc * qv) : 0.0;
+        else SQ[k] = i < n ? (sv + qv) : 0.0;   // `sj .+ q` (:56)
         lx[k * THREADS + t] = i < n ? xv : 0.0;
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -242,7 +278,9 @@ __global__ __launch_bounds__(THREADS) void k_b2_coop(double* y, const double* q,
       const int64_t i = gtid + (int64_t)k * NT;
       const int64_t ic = i < n ? i : n - 1;
       const double xv = xk[ic], sv = sj[ic], qv = q[ic];
-      const double sq = i < n ? (sv + qv) : 0.0;   // `sj .+ q` (:56)
+      double sq;
+      if constexpr (VALUE) sq = i < n ? (sv + qsc * qv) : 0.0;
+      else sq = i < n ? (sv + qv) : 0.0;   // `sj .+ q` (:56)
       X[k] = i < n ? xv : 0.0;
       LO[k] = sq - ls;
       HI[k] = sq + ls;
@@ -260,7 +298,7 @@ __global__ __launch_bounds__(THREADS) void k_b2_coop(double* y, const double* q,
   double sx = 0.0, ss = 0.0, ssq = 0.0;
   if (has_sample) {
     const int64_t i = (int64_t)((double)chunk * (double)(n - 32) / (double)(kChunks - 1)) + (t & 31);
-    sx = xk[i]; ss = sj[i]; ssq = ss + q[i];
+    sx = xk[i]; ss = sj[i]; ssq = ss + b2_qs<VALUE>(qsc, q[i]);
   }
   const int64_t n2 = n >> 1;
   int np = 0;  // reductions exchanged so far (row of the exchange words)
@@ -302,6 +340,16 @@ __global__ __launch_bounds__(THREADS) void k_b2_coop(double* y, const double* q,
     }
     ++np;
   };
+  // (VALUE) the exit exchange: hv of the pass whose stores stand -> the same total in every workgroup -> lambda * total.  Once
+  // per launch, in row 63 whatever np has reached: the root loop may have used every row below it.
+  auto publish = [&]() {
+    if constexpr (VALUE) {
+      double v[6] = {hv, 0.0, 0.0, 0.0, 0.0, 0.0};
+      np = kB2MaxPass - 1;
+      reduce(v, 1u);
+      if (blockIdx.x == 0 && t == 0) *vout = spx_poisoned(hdr) ? __longlong_as_double(0x7ff8000000000000ll) : vlam * v[0];
+    }
+  };
   // the sums at scale r (= eta / Delta) over one element; the Julia-semantics min / max cost six instructions each and matter
   // only for the bits of a STORED y (signed zeros, NaN propagation): the sums take v_max_f64 / v_min_f64 and masked fma
   // operands; a NaN operand -- which v_max / v_min would drop -- is tracked separately and poisons P, as the reference's norm would be NaN
@@ -324,6 +372,7 @@ __global__ __launch_bounds__(THREADS) void k_b2_coop(double* y, const double* q,
   auto pass_small = [&](double r, double rinv, bool first, bool store, bool sample) {
     double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     bad = false;
+    if constexpr (VALUE) { if (store) hv = 0.0; }
     auto one = [&](double lo, double hi, double x) {
       const double pz = acc(lo, hi, x, r, v[0], v[1]);
       if (first) {
@@ -343,7 +392,15 @@ __global__ __launch_bounds__(THREADS) void k_b2_coop(double* y, const double* q,
           double x, lo, hi;
           elem(k, lsv, x, lo, hi);
           one(lo, hi, x);
-          if (store) y[i] = outv(lo, hi, x, sj[i], r, rinv);
+          if constexpr (VALUE) {
+            if (store) {
+              const double s = sj[i], o = outv(lo, hi, x, s, r, rinv);
+              y[i] = o;
+              hv += fabs((x + s) + o);
+            }
+          } else {
+            if (store) y[i] = outv(lo, hi, x, sj[i], r, rinv);
+          }
         }
         __builtin_amdgcn_sched_barrier(0);  // one element at a time: interleaved, the unrolled visits spill
       }
@@ -375,7 +432,10 @@ __global__ __launch_bounds__(THREADS) void k_b2_coop(double* y, const double* q,
   __shared__ unsigned int next_tile;
   unsigned int* const tile_ctr = reinterpret_cast<unsigned int*>(rows + (size_t)(kB2MaxPass - 1) * kB2Cols * kB2Words + 7);  // (row 63 is
   // never reached by a reduction; word 7 of a slot is never a partial sum; zeroed with the set like everything else in it)
-  auto stream = [&](auto&& visit_pair, bool dynamic = false) {  // visit_pair(valid, pair index, q pair, xk pair, sj pair), called by every lane
+  auto stream = [&](auto&& visit_pair, bool dynamic = false) {  // visit_pair(valid, pair index, q pair (VALUE: scaled), xk pair, sj pair), called by every lane
+#ifndef SPX_B2_VALUE_DYNAMIC_AB  // (A/B builds only, tools/b2_proxval_timing.py --ab-lib: what on-demand tiles would buy; hv then varies run to run)
+    if constexpr (VALUE) dynamic = false;  // (the sums of a storing pass must not depend on who took which tile)
+#endif
     if constexpr (VEC && !REG) {
       typedef __attribute__((address_space(3))) void lds_void;
       const int wave = t >> 6, lane = t & 63;
@@ -410,7 +470,7 @@ __global__ __launch_bounds__(THREADS) void k_b2_coop(double* y, const double* q,
           const f64x2 a = *reinterpret_cast<const f64x2*>(wl + (0 * kB2DmaKiB + k) * 1024 + lane * 16);
           const f64x2 b = *reinterpret_cast<const f64x2*>(wl + (1 * kB2DmaKiB + k) * 1024 + lane * 16);
           const f64x2 d = *reinterpret_cast<const f64x2*>(wl + (2 * kB2DmaKiB + k) * 1024 + lane * 16);
-          visit_pair(i < n2, i, a, b, d);
+          visit_pair(i < n2, i, b2_qs<VALUE>(qsc, a), b, d);
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this tile's LDS reads are done before the next tile's loads are issued
         if (dynamic) {
@@ -435,7 +495,7 @@ __global__ __launch_bounds__(THREADS) void k_b2_coop(double* y, const double* q,
 #pragma unroll
       for (int k = 0; k < KP; ++k) {
         const int64_t i = tile * kTilePairs + t + k * THREADS;
-        visit_pair(i < n2, i, a[k], b[k], d[k]);
+        visit_pair(i < n2, i, b2_qs<VALUE>(qsc, a[k]), b[k], d[k]);
       }
     };
     f64x2 a0[KP], b0[KP], d0[KP], a1[KP], b1[KP], d1[KP];
@@ -457,17 +517,31 @@ __global__ __launch_bounds__(THREADS) void k_b2_coop(double* y, const double* q,
   // the storing pass: y = ProjB((-xk) r) rinv - sj
   bool y_written = false;  // (!REG) an earlier pass of this launch stored y: the storing pass must then keep the static mapping
   auto store_pass = [&](double r, double rinv) {
+    if constexpr (VALUE) hv = 0.0;
     if constexpr (!REG) {
       if (n2 > 0)
         stream([&](bool valid, int64_t i, f64x2 a, f64x2 b, f64x2 d) {
           if (valid) {
             const double sq0 = d.x + a.x, sq1 = d.y + a.y;
-            b2_st<VEC>(y, i, f64x2{outv(sq0 - ls, sq0 + ls, b.x, d.x, r, rinv), outv(sq1 - ls, sq1 + ls, b.y, d.y, r, rinv)});
+            if constexpr (VALUE) {
+              const f64x2 o{outv(sq0 - ls, sq0 + ls, b.x, d.x, r, rinv), outv(sq1 - ls, sq1 + ls, b.y, d.y, r, rinv)};
+              b2_st<VEC>(y, i, o);
+              hv += fabs((b.x + d.x) + o.x);
+              hv += fabs((b.y + d.y) + o.y);
+            } else {
+              b2_st<VEC>(y, i, f64x2{outv(sq0 - ls, sq0 + ls, b.x, d.x, r, rinv), outv(sq1 - ls, sq1 + ls, b.y, d.y, r, rinv)});
+            }
           }
         }, !y_written && G > 1 && ntiles >= 8 * (int64_t)G);  // (a few tiles per workgroup: the hand-out costs more than it balances -- n = 6e6, 4 tiles each: 128 -> 135 us; n = 1.6e7, 10 each: 220 -> 212)
       if ((n & 1) && blockIdx.x == 0 && t == 0) {
-        const double sql = sj[n - 1] + q[n - 1];
-        y[n - 1] = outv(sql - ls, sql + ls, xk[n - 1], sj[n - 1], r, rinv);
+        const double sql = sj[n - 1] + b2_qs<VALUE>(qsc, q[n - 1]);
+        if constexpr (VALUE) {
+          const double xl = xk[n - 1], sl = sj[n - 1], o = outv(sql - ls, sql + ls, xl, sl, r, rinv);
+          y[n - 1] = o;
+          hv += fabs((xl + sl) + o);
+        } else {
+          y[n - 1] = outv(sql - ls, sql + ls, xk[n - 1], sj[n - 1], r, rinv);
+        }
       }
     } else {
 #pragma unroll
@@ -476,7 +550,13 @@ __global__ __launch_bounds__(THREADS) void k_b2_coop(double* y, const double* q,
         if (i < n) {
           double x, lo, hi;
           elem(k, ls, x, lo, hi);
-          y[i] = outv(lo, hi, x, sj[i], r, rinv);
+          if constexpr (VALUE) {
+            const double s = sj[i], o = outv(lo, hi, x, s, r, rinv);
+            y[i] = o;
+            hv += fabs((x + s) + o);
+          } else {
+            y[i] = outv(lo, hi, x, sj[i], r, rinv);
+          }
         }
         if constexpr (LDSX) __builtin_amdgcn_sched_barrier(0);
       }
@@ -487,11 +567,19 @@ __global__ __launch_bounds__(THREADS) void k_b2_coop(double* y, const double* q,
     double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     bad = false;
     if (store) y_written = true;
+    if constexpr (VALUE) { if (store) hv = 0.0; }
     if constexpr (!REG) {
       auto one = [&](double qv, double x, double s) -> double {
         const double sq = s + qv;
         acc(sq - ls, sq + ls, x, r, v[0], v[1]);
-        return store ? outv(sq - ls, sq + ls, x, s, r, rinv) : 0.0;
+        if constexpr (VALUE) {
+          if (!store) return 0.0;
+          const double o = outv(sq - ls, sq + ls, x, s, r, rinv);
+          hv += fabs((x + s) + o);
+          return o;
+        } else {
+          return store ? outv(sq - ls, sq + ls, x, s, r, rinv) : 0.0;
+        }
       };
       if (n2 > 0)
         stream([&](bool valid, int64_t i, f64x2 a, f64x2 b, f64x2 d) {
@@ -501,7 +589,7 @@ __global__ __launch_bounds__(THREADS) void k_b2_coop(double* y, const double* q,
           }
         });
       if ((n & 1) && blockIdx.x == 0 && t == 0) {
-        const double o = one(q[n - 1], xk[n - 1], sj[n - 1]);
+        const double o = one(b2_qs<VALUE>(qsc, q[n - 1]), xk[n - 1], sj[n - 1]);
         if (store) y[n - 1] = o;
       }
     }
@@ -527,13 +615,20 @@ __global__ __launch_bounds__(THREADS) void k_b2_coop(double* y, const double* q,
         const double sq = s + qv;
         const double lo = sq - ls, hi = sq + ls;
         acc(lo, hi, x, 1.0, v[0], v[1]);
-        return outv(lo, hi, x, s, 1.0, 1.0);
+        if constexpr (VALUE) {
+          const double o = outv(lo, hi, x, s, 1.0, 1.0);
+          hv += fabs((x + s) + o);
+          return o;
+        } else {
+          return outv(lo, hi, x, s, 1.0, 1.0);
+        }
       };
+      if constexpr (VALUE) hv = 0.0;
       if (n2 > 0)
         stream([&](bool valid, int64_t i, f64x2 a, f64x2 b, f64x2 d) {
           if (valid) b2_st<VEC>(y, i, f64x2{one0(a.x, b.x, d.x), one0(a.y, b.y, d.y)});
         }, true);
-      if ((n & 1) && blockIdx.x == 0 && t == 0) y[n - 1] = one0(q[n - 1], xk[n - 1], sj[n - 1]);
+      if ((n & 1) && blockIdx.x == 0 && t == 0) y[n - 1] = one0(b2_qs<VALUE>(qsc, q[n - 1]), xk[n - 1], sj[n - 1]);
       // (one wavefront per workgroup issues the write-back, after all of the workgroup's stores have left: a fence per
       //  wavefront -- 4096 L2 write-back scans -- made the pass slower than the static one)
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -547,6 +642,7 @@ __global__ __launch_bounds__(THREADS) void k_b2_coop(double* y, const double* q,
       const double chi0 = chil * sqrt(v[0] + v[1]);
       if (delta > chi0 * (1.0 + 1e-12)) {  // (NaN sums compare false: the ordinary pass decides)
         if (blockIdx.x == 0 && t == 0) hdr->b2_last_scaled = 0;
+        publish();
         return;  // (after the exchange: every workgroup formed the same sums and takes the same way)
       }
       store_first = false;
@@ -613,7 +709,10 @@ __global__ __launch_bounds__(THREADS) void k_b2_coop(double* y, const double* q,
         const double pz = acc(lo, hi, x, 1.0, v[0], v[1]);
         const double far = (x < 0.0) ? hi : (x > 0.0) ? lo : pz;
         v[2] = __builtin_fma(far, far, v[2]);
-        if (store_first) o = outv(lo, hi, x, s, 1.0, 1.0);
+        if (store_first) {
+          o = outv(lo, hi, x, s, 1.0, 1.0);
+          if constexpr (VALUE) hv += fabs((x + s) + o);
+        }
       }
       if (have_bracket) {  // (wave-uniform; every lane takes part in the ballot)
         const double za = (-x) * ra, zb = (-x) * rb;
@@ -637,6 +736,7 @@ __global__ __launch_bounds__(THREADS) void k_b2_coop(double* y, const double* q,
       return o;
     };
     if (store_first) y_written = true;
+    if constexpr (VALUE) hv = 0.0;
     if (n2 > 0)
       stream([&](bool valid, int64_t i, f64x2 a, f64x2 b, f64x2 d) {
         const f64x2 o{one(valid, a.x, b.x, d.x), one(valid, a.y, b.y, d.y)};
@@ -644,7 +744,7 @@ __global__ __launch_bounds__(THREADS) void k_b2_coop(double* y, const double* q,
       });
     if (n & 1) {  // the odd last element rides with wavefront 0 of workgroup 0 (all of its lanes call `one`)
       if (blockIdx.x == 0 && t < 64) {
-        const double o = one(t == 0, q[n - 1], xk[n - 1], sj[n - 1]);
+        const double o = one(t == 0, b2_qs<VALUE>(qsc, q[n - 1]), xk[n - 1], sj[n - 1]);
         if (store_first && t == 0) y[n - 1] = o;
       }
     }
@@ -767,12 +867,16 @@ __global__ __launch_bounds__(THREADS) void k_b2_coop(double* y, const double* q,
 #ifdef SPX_B2_PROFILE
   if (stored && blockIdx.x == 0 && t == 0) g_b2_nstamp = nst;
 #endif
-  if (stored && !spx_poisoned(hdr)) return;  // (after the last exchange; every workgroup takes the same path)
+  if (stored && !spx_poisoned(hdr)) {  // (after the last exchange; every workgroup takes the same path)
+    publish();
+    return;
+  }
   // final: y = ProjB((-xk) r) rinv - sj   (:63, :65), or ProjB(-xk) - sj (:59) when the trust region is inactive.  A workgroup
   // that gave up waiting (spx_wait_expired) has made every sum garbage: NaN everywhere, the next libspx call reports it.
   double r = scaled ? eta / delta : 1.0, rinv = scaled ? delta / eta : 1.0;
   if (spx_poisoned(hdr)) r = rinv = __longlong_as_double(0x7ff8000000000000ll);
   store_pass(r, rinv);
+  publish();
 #ifdef SPX_B2_PROFILE
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   B2_STAMP();
@@ -837,19 +941,40 @@ SPX_EXPORT int spx_obj_l1_b2(spx_ctx* ctx, const double* y, const double* xk, co
   return SPX_OK;
 }
 
-SPX_EXPORT int spx_prox_l1_b2(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
-                              double lambda, double sigma, double delta, double chi_lambda) {
+namespace {
+
+// the kernel of one form; VALUE: with the B2Val argument behind the plain ones
+template <bool REG, int EPL, int THREADS, bool VEC, bool LDSX, bool VALUE>
+constexpr auto b2_kernel() {
+  if constexpr (VALUE) return &k_b2_coop<REG, EPL, THREADS, VEC, LDSX, true, B2Val>;
+  else return &k_b2_coop<REG, EPL, THREADS, VEC, LDSX, false>;
+}
+
+// One host body for spx_prox_l1_b2 (VALUE = false: q_scale and value are not looked at) and spx_proxval_l1_b2.  The form and
+// the grid are chosen from the PLAIN kernels' residency in both: y's bits depend on the grid (the partition of every sum).
+template <bool VALUE>
+int run_b2(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n, double lambda, double sigma,
+           double delta, double chi_lambda, double q_scale, double* value) {
+  if constexpr (VALUE) SPX_REQUIRE(value != nullptr, "value is NULL");
   int rc = spx_check_common(ctx, y, q, xk, sj, n);
   if (rc) return rc;
+  if constexpr (VALUE) {
+    if (!ctx->value_target) {  // (refused before anything is enqueued)
+      const int rcc = spx_require_not_capturing(ctx, "returning the value to the host");
+      if (rcc) return rcc;
+    }
+    *value = 0.0;
+    if (n == 0 && ctx->value_target) return spx_zero_async(ctx, ctx->value_target, sizeof(double));
+  }
   if (n == 0) return SPX_OK;
   SPX_ON_DEVICE(ctx);
   const double ls = lambda * sigma;  // `psi.lambda * sigma`, :56
   const bool vec = n >= 2 && spx_aligned16(y) && spx_aligned16(q) && spx_aligned16(xk) && spx_aligned16(sj);
   // Residency (spx_resident_cap): the grid of a launch that synchronises inside itself never exceeds what can be resident
   // at once; the streaming form works with any grid >= 1, the register-resident one needs ceil(n / 8192) workgroups.
-  const int64_t cap_reg = spx_resident_cap(ctx, reinterpret_cast<const void*>(&k_b2_coop<true, kB2Epl, kB2RegThreads, true>), kB2RegThreads, 0);
-  const int64_t cap_mem = vec ? spx_resident_cap(ctx, reinterpret_cast<const void*>(&k_b2_coop<false, 1, 1024, true>), 1024, 0)
-                              : spx_resident_cap(ctx, reinterpret_cast<const void*>(&k_b2_coop<false, 1, 1024, false>), 1024, 0);
+  const int64_t cap_reg = spx_resident_cap(ctx, reinterpret_cast<const void*>(b2_kernel<true, kB2Epl, kB2RegThreads, true, false, false>()), kB2RegThreads, 0);
+  const int64_t cap_mem = vec ? spx_resident_cap(ctx, reinterpret_cast<const void*>(b2_kernel<false, 1, 1024, true, false, false>()), 1024, 0)
+                              : spx_resident_cap(ctx, reinterpret_cast<const void*>(b2_kernel<false, 1, 1024, false, false, false>()), 1024, 0);
   if (cap_mem < 1) return SPX_ERR_INTERNAL;  // (message set by spx_resident_cap)
   const int64_t gmax_reg = cap_reg < kB2Cols ? cap_reg : kB2Cols;
   const int64_t gmax_mem = cap_mem < kB2Cols ? cap_mem : kB2Cols;
@@ -859,7 +984,7 @@ SPX_EXPORT int spx_prox_l1_b2(spx_ctx* ctx, double* y, const double* q, const do
   bool ldsx = false;
   int64_t gmax_lds = 0;
   if (!reg && ctx->tune_b2_lds) {
-    const int64_t cap_lds = spx_resident_cap(ctx, reinterpret_cast<const void*>(&k_b2_coop<true, kB2Epl, 1024, true, true>), 1024, 0);
+    const int64_t cap_lds = spx_resident_cap(ctx, reinterpret_cast<const void*>(b2_kernel<true, kB2Epl, 1024, true, true, false>()), 1024, 0);
     gmax_lds = cap_lds < kB2Cols ? cap_lds : kB2Cols;
     ldsx = n <= (int64_t)kB2Epl * 1024 * gmax_lds;
   }
@@ -875,6 +1000,21 @@ SPX_EXPORT int spx_prox_l1_b2(spx_ctx* ctx, double* y, const double* q, const do
     if (gg > g) g = gg;
   }
   if (g < 1) g = 1;
+  if constexpr (VALUE) {
+    // FUSED on all four forms: the VALUE kernel of the form runs with the grid chosen above (same LDS, same lanes per workgroup as
+    // its plain twin: resident wherever that one is)
+    const int64_t cap_val =
+        ldsx  ? spx_resident_cap(ctx, reinterpret_cast<const void*>(b2_kernel<true, kB2Epl, 1024, true, true, true>()), 1024, 0)
+        : reg ? spx_resident_cap(ctx, reinterpret_cast<const void*>(b2_kernel<true, kB2Epl, kB2RegThreads, true, false, true>()), kB2RegThreads, 0)
+        : vec ? spx_resident_cap(ctx, reinterpret_cast<const void*>(b2_kernel<false, 1, 1024, true, false, true>()), 1024, 0)
+              : spx_resident_cap(ctx, reinterpret_cast<const void*>(b2_kernel<false, 1, 1024, false, false, true>()), 1024, 0);
+    if (cap_val < 1) return SPX_ERR_INTERNAL;  // (message set by spx_resident_cap)
+    if (cap_val < g) {
+      spx_set_error("internal error: the fused ShiftedNormL1B2 kernel is resident with %lld workgroups, the prox takes %lld",
+                    (long long)cap_val, (long long)g);
+      return SPX_ERR_INTERNAL;
+    }
+  }
   // streaming form: candidate regions, one per wavefront of the grid -- room for 8 % of its share of the vector (the bracket
   // of +-1.5 % around the sample's root holds the breakpoints of 1-2 % on ordinary data; a full region = plain iteration)
   f64x2* cand = nullptr;
@@ -910,18 +1050,19 @@ SPX_EXPORT int spx_prox_l1_b2(spx_ctx* ctx, double* y, const double* q, const do
   unsigned long long* clear_rows = sets + (size_t)other * kB2SetWords;
   {
     SpxCoopLaunchGuard guard(ctx);
-    if (ldsx)
-      hipLaunchKernelGGL((k_b2_coop<true, kB2Epl, 1024, true, true>), dim3((unsigned)g), dim3(1024), 0, ctx->stream, y, q,
-                         xk, sj, n, ls, delta, chi_lambda, rows, clear_rows, clear_g, hdr, can_spec, (f64x2*)nullptr, 0u);
-    else if (reg)
-      hipLaunchKernelGGL((k_b2_coop<true, kB2Epl, kB2RegThreads, true>), dim3((unsigned)g), dim3(kB2RegThreads), 0, ctx->stream, y, q,
-                         xk, sj, n, ls, delta, chi_lambda, rows, clear_rows, clear_g, hdr, can_spec, (f64x2*)nullptr, 0u);
-    else if (vec)
-      hipLaunchKernelGGL((k_b2_coop<false, 1, 1024, true>), dim3((unsigned)g), dim3(1024), 0, ctx->stream, y, q, xk, sj, n, ls,
-                         delta, chi_lambda, rows, clear_rows, clear_g, hdr, can_spec, cand, cand_cap);
-    else
-      hipLaunchKernelGGL((k_b2_coop<false, 1, 1024, false>), dim3((unsigned)g), dim3(1024), 0, ctx->stream, y, q, xk, sj, n, ls,
-                         delta, chi_lambda, rows, clear_rows, clear_g, hdr, can_spec, cand, cand_cap);
+    auto launch = [&](auto kern, int threads) {
+      if constexpr (VALUE)
+        hipLaunchKernelGGL(kern, dim3((unsigned)g), dim3(threads), 0, ctx->stream, y, q, xk, sj, n, ls, delta, chi_lambda, rows,
+                           clear_rows, clear_g, hdr, can_spec, cand, cand_cap,
+                           B2Val{q_scale, lambda, ctx->value_target ? ctx->value_target : &hdr->b2_value});
+      else
+        hipLaunchKernelGGL(kern, dim3((unsigned)g), dim3(threads), 0, ctx->stream, y, q, xk, sj, n, ls, delta, chi_lambda, rows,
+                           clear_rows, clear_g, hdr, can_spec, cand, cand_cap);
+    };
+    if (ldsx) launch(b2_kernel<true, kB2Epl, 1024, true, true, VALUE>(), 1024);
+    else if (reg) launch(b2_kernel<true, kB2Epl, kB2RegThreads, true, false, VALUE>(), kB2RegThreads);
+    else if (vec) launch(b2_kernel<false, 1, 1024, true, false, VALUE>(), 1024);
+    else launch(b2_kernel<false, 1, 1024, false, false, VALUE>(), 1024);
   }
   if (graph_safe) {  // both sets count as used by the widest grid from here on (a replay may have touched set 0)
     ctx->track.b2_dirty_g[0] = ctx->track.b2_dirty_g[1] = kB2Cols;
@@ -931,5 +1072,26 @@ SPX_EXPORT int spx_prox_l1_b2(spx_ctx* ctx, double* y, const double* q, const do
     ctx->track.b2_set = other;
   }
   SPX_LAUNCH_CHECK();
+  if constexpr (VALUE) {
+    if (ctx->value_target) {  // device-resident value: nothing is read back, the call returns after enqueueing
+      *value = std::nan("");
+      return SPX_OK;
+    }
+    SPX_HIP(hipMemcpyAsync(value, &hdr->b2_value, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    SPX_HIP(hipStreamSynchronize(ctx->stream));
+  }
   return SPX_OK;
+}
+
+}  // namespace
+
+SPX_EXPORT int spx_prox_l1_b2(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
+                              double lambda, double sigma, double delta, double chi_lambda) {
+  return run_b2<false>(ctx, y, q, xk, sj, n, lambda, sigma, delta, chi_lambda, 1.0, nullptr);
+}
+
+// prox! fused with h at the result (include/spx.h): the value comes out of the launch that stores y, on every form.
+SPX_EXPORT int spx_proxval_l1_b2(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
+                                 double lambda, double sigma, double delta, double chi_lambda, double q_scale, double* value) {
+  return run_b2<true>(ctx, y, q, xk, sj, n, lambda, sigma, delta, chi_lambda, q_scale, value);
 }

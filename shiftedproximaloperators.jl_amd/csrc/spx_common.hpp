@@ -322,7 +322,8 @@ struct SpxSyncHeader {
   long long grp_deferred[2];  // count words of the Binf group operators' deferred list: a call uses [set] and clears [set ^ 1] (spx_group.hip)
   unsigned int fin_top;       // the objective kernels' "last workgroup" tickets (spx_fin_ticket below); zero between launches
   int fin_flag;               // ... and their infeasibility bits; zero between launches
-  int pad[22];
+  double b2_value;            // spx_proxval_l1_b2 without a device value target: the launch stores h here, the host reads it back
+  int pad[20];
   unsigned int fin_class[kSpxBarSplit * 32];  // first-level tickets, one 128-byte line each
 };
 static_assert(sizeof(SpxSyncHeader) == 2 * kSpxBarSplit * 32 * 4 + 128 + kSpxBarSplit * 32 * 4, "SpxSyncHeader layout");

@@ -757,15 +757,18 @@ def prox_value_bang(y, ψ, q, σ, q_scale=1.0):
     (unless inside `device_values`).  The separable operators (ShiftedNormL1 / NormL0 / RootNormLhalf and their Box
     forms) and, on Float64 vectors with contiguous groups, ShiftedGroupNormL2 / ShiftedGroupNormL2Binf: one pass over the
     vectors for groups of at most 512 elements (uniform, or ragged with that bound), the prox followed by ψ's reduction
-    inside the same library call beyond.  The Box and Binf forms return the h part of ψ(y): the prox lies inside the box /
+    inside the same library call beyond.  ShiftedNormL1B2 on device Float64 vectors: the value comes out of the one launch
+    that stores y, at every size.  The Box, Binf and B2 forms return the h part of ψ(y): the prox lies inside the box /
     trust region by construction.  q_scale: the prox is taken at q_scale * q, formed on the fly (R2:
     `prox_value(ψ, ∇f, ν, q_scale=-ν)` instead of materialising -ν∇f).  Float32 group operators, host ψ, index-set
-    (gather) layouts and the remaining operators raise TypeError."""
+    (gather) layouts and the remaining operators (top-r: their h is 0 at any prox result) raise TypeError."""
     if isinstance(ψ, (ShiftedGroupNormL2, ShiftedGroupNormL2Binf)):
         return _group_prox_value_bang(y, ψ, q, σ, q_scale)
+    if isinstance(ψ, ShiftedNormL1B2):
+        return _b2_prox_value_bang(y, ψ, q, σ, q_scale)
     if not isinstance(ψ, (_Unboxed, _Boxed)) or ψ.host:
-        raise TypeError("prox_value is available for the separable operators and the contiguous Float64 group operators "
-                        "on device vectors")
+        raise TypeError("prox_value is available for the separable operators, the contiguous Float64 group operators and "
+                        "ShiftedNormL1B2 on device vectors")
     n = _n(ψ.xk)
     _vec(q, "q", n, like=ψ.xk)
     _vec(y, "y", n, like=ψ.xk)
@@ -800,6 +803,20 @@ def _group_prox_value_bang(y, ψ, q, σ, q_scale):
         _lib.check(L.spx_proxval_group_l2_binf(*head, ψ.Δ, float(q_scale), ctypes.byref(out)))
     else:
         _lib.check(L.spx_proxval_group_l2(*head, float(q_scale), ctypes.byref(out)))
+    return y, out.value
+
+
+def _b2_prox_value_bang(y, ψ, q, σ, q_scale):
+    if _is_host(ψ.xk) or ψ.xk.dtype != torch.float64:
+        raise TypeError("prox_value on ShiftedNormL1B2 needs device Float64 vectors")
+    n = _n(ψ.xk)
+    _vec(q, "q", n, like=ψ.xk)
+    _vec(y, "y", n, like=ψ.xk)
+    ψ._refresh()
+    L, ctx = _lib.load(), _ctx(_dev(y))
+    out = ctypes.c_double(0.0)
+    _lib.check(L.spx_proxval_l1_b2(ctx, _ptr(y), _ptr(q), _ptr(ψ.xk), _ptr(ψ.sj), n, ψ.h.lam, float(σ), ψ.Δ, ψ.χ.lam,
+                                   float(q_scale), ctypes.byref(out)))
     return y, out.value
 
 
