@@ -6,6 +6,10 @@ loop in miniature, using only the mirrored API:
     s, hkn = prox_value(psi, grad, nu, q_scale=-nu)   # mnu_grad = -nu grad; prox!(s, psi, mnu_grad, nu); psi(s): one pass
     shift_bang(psi, xk)                        # after an accepted step
 
+`fused_step=True` (GPU backend) takes s, h(xk + s), grad' s and xk + s from ONE prox_step call per iteration instead:
+
+    s, hkn, gts, _ = prox_step(psi, grad, nu, q_scale=-nu, xkn=xkn)     # no torch.dot(grad, s), no xk + s
+
 Everything stays in device memory; torch supplies the smooth part (A x, A' r).  `backend="oracle"` runs the same loop on
 the CPU with the reference restatement (test infrastructure) -- tests/test_gpu_r2_loop.py compares the two trajectories.
 """
@@ -17,7 +21,9 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))  # repository root: spx_amd, oracle
 
 
-def r2_lasso(A, b, lam, x0, backend, max_iter=200, tol=1e-6, eta1=1e-4, eta2=0.9, gamma=3.0, nu0=None):
+def r2_lasso(A, b, lam, x0, backend, max_iter=200, tol=1e-6, eta1=1e-4, eta2=0.9, gamma=3.0, nu0=None, fused_step=False):
+    if fused_step and backend != "gpu":
+        raise ValueError("fused_step needs backend='gpu'")
     if backend == "gpu":
         import torch
         import spx_amd as spx
@@ -27,6 +33,11 @@ def r2_lasso(A, b, lam, x0, backend, max_iter=200, tol=1e-6, eta1=1e-4, eta2=0.9
         psi = spx.shifted(spx.NormL1(lam), xk)
         prox_val = lambda grad, nu: spx.prox_value(psi, grad, nu, q_scale=-nu)   # q = -nu grad formed on the fly
         hval = lambda: psi(torch.zeros_like(xk))
+        xkn_buf = torch.empty_like(xk) if fused_step else None
+
+        def prox_step(grad, nu):   # s, h(xk + s), grad' s (qy is taken with the unscaled q = grad) and xk + s: one pass
+            s, hkn, gts, _ = spx.prox_step(psi, grad, nu, q_scale=-nu, xkn=xkn_buf)
+            return s, hkn, gts, xkn_buf
     else:
         from oracle import oracle
         dot = lambda u, v: float(np.dot(u, v))
@@ -45,12 +56,17 @@ def r2_lasso(A, b, lam, x0, backend, max_iter=200, tol=1e-6, eta1=1e-4, eta2=0.9
     nu = nu0 if nu0 is not None else 1.0
     hist = []
     for it in range(max_iter):
-        s, hkn = prox_val(grad, nu)
-        xi = hk - (dot(grad, s) + hkn)                      # model decrease
+        if fused_step:
+            s, hkn, gts, xkn = prox_step(grad, nu)
+        else:
+            s, hkn = prox_val(grad, nu)
+            gts, xkn = dot(grad, s), None
+        xi = hk - (gts + hkn)                               # model decrease
         if xi < 0 or np.sqrt(max(xi, 0.0) / nu) < tol:
             hist.append((it, fk + hk, nu, None))
             break
-        xkn = xk + s
+        if xkn is None:
+            xkn = xk + s
         resn = A @ xkn - b
         fkn = 0.5 * norm2(resn)
         rho = (fk + hk - fkn - hkn) / xi

@@ -280,6 +280,56 @@ int spx_proxval_lhalf_box(spx_ctx* ctx, double* y, const double* q, const double
                           double lambda, double sigma, const double* l_vec, const double* u_vec, double l_scalar,
                           double u_scalar, const uint8_t* sel_mask, double q_scale, double* value);
 
+/* ---- prox! fused with the step statistics of a solver iteration ------------------------------- */
+/* What an R2 / TR iteration does around the separable prox! -- `s = prox!(...)`, `h(xk + s)`, `dot(grad, s)`, `xk + s`,
+ * `norm(s)` -- in the ONE pass that stores y: 40 B/element (q, xk, sj in; y, xkn out) instead of 72-80 in separate passes,
+ * one launch instead of three or four.  The argument list of spx_proxval_X up to and including q_scale, then:
+ *   y        : bit-identical to spx_prox_X at q_scale * q, exactly the contract of spx_proxval_X.
+ *   xkn      : device pointer to n doubles, or NULL.  xkn[i] = (xk[i] + sj[i]) + y[i], in that association -- the point at
+ *              which h is evaluated, i.e. xk + s for a once-shifted psi with sj = 0.  Written for EVERY i, selected or
+ *              not.  It must not overlap y, q, xk, sj, l_vec, u_vec or the mask: a pointer EQUAL to one of them returns
+ *              SPX_ERR_INVALID_ARG, nothing else about overlap is checked.  Any 8-byte alignment (when it differs from the
+ *              other vectors' the call takes the element-wise kernel, as for any vectors of mixed alignment).
+ *   three sums, {[0], [1], [2]}:
+ *     [0] = the value spx_proxval_X returns: lambda * sum over the SELECTED indices of Term((xk + sj) + y) (Box forms: the
+ *           h part only, as spx_proxval_X);
+ *     [1] = sum over ALL i of q[i] * y[i], with q AS PASSED, not q_scale * q (R2 passes q = grad f and q_scale = -nu and
+ *           gets grad f' s directly);
+ *     [2] = sum over ALL i of y[i]^2.
+ *   stats    : host double[3], or NULL.  stats_dev: DEVICE double[3], or NULL.  At least one must be non-NULL
+ *              (SPX_ERR_INVALID_ARG otherwise).  With stats == NULL the call only enqueues -- no read-back, no
+ *              synchronisation -- and is capturable under the rules stated above for the value entry points (device
+ *              pointers, the same call made once before on the context).  With stats != NULL the call copies the three
+ *              doubles back and synchronises like spx_proxval_X, and is refused under a capture (SPX_ERR_INVALID_ARG,
+ *              nothing launched).  Both given: the same bits in both.
+ *   spx_ctx_set_value_target does not affect these calls.
+ *   y == q returns SPX_ERR_INVALID_ARG (<q, y> of an overwritten q serves nobody).
+ *   n == 0: three zeros on the host, and three zeros stored to stats_dev by a kernel (no memset node).
+ * The sums are added in a fixed order: reproducible run to run, and the same bits with tuning key 17 at 0 and at 1 -- one
+ * ticket per workgroup publishes its three partial sums, and the last workgroup (or the separate launch) adds each of the
+ * three in the order the single sum of spx_proxval_X is added.  [0] has the bits of spx_proxval_X's value whenever both
+ * calls take the same kernel form (same tuning keys, xkn aligned like the other vectors).
+ * Float64 and device pointers only: there is no Float32 form, no host-pointer twin (spx_host_*), and no group / top-r /
+ * ShiftedNormL1B2 form -- their fused-value kernels have different exits. */
+int spx_proxstep_l1(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
+                    double lambda, double sigma, double q_scale, double* xkn, double* stats, double* stats_dev);
+int spx_proxstep_l0(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
+                    double lambda, double sigma, double q_scale, double* xkn, double* stats, double* stats_dev);
+int spx_proxstep_lhalf(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
+                       double lambda, double sigma, double q_scale, double* xkn, double* stats, double* stats_dev);
+int spx_proxstep_l1_box(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
+                        double lambda, double sigma, const double* l_vec, const double* u_vec, double l_scalar,
+                        double u_scalar, const uint8_t* sel_mask, double q_scale, double* xkn, double* stats,
+                        double* stats_dev);
+int spx_proxstep_l0_box(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
+                        double lambda, double sigma, const double* l_vec, const double* u_vec, double l_scalar,
+                        double u_scalar, const uint8_t* sel_mask, double q_scale, double* xkn, double* stats,
+                        double* stats_dev);
+int spx_proxstep_lhalf_box(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
+                           double lambda, double sigma, const double* l_vec, const double* u_vec, double l_scalar,
+                           double u_scalar, const uint8_t* sel_mask, double q_scale, double* xkn, double* stats,
+                           double* stats_dev);
+
 /* ---- iprox!: argmin 1/2 y'Dy + g'y + psi(y), D = diag(d)  (src/ShiftedProximalOperators.jl:154-180) ------ */
 /* Separable; reads g, d, xk, sj (40 B/element).  y may alias g.
  * Unboxed forms: the reference asserts d[i] > 0.  check_d != 0: the call synchronises and returns SPX_ERR_ASSERT

@@ -215,6 +215,45 @@ function prox_value!(y::DVec, ψ::ShiftedNormL1Box{Float64, <:DVec, <:DVec, <:DV
 end
 
 # ---------------------------------------------------------------------------------------------
+# prox! fused with the step statistics of an iteration (spx_proxstep_*; no counterpart in the reference: what R2 / TR do
+# around the prox -- `ψ(s)`, `dot(∇fk, s)`, `xk + s`, `norm(s)` -- in the pass that stores s).  Returns (y, h, qy, yy):
+#   h  = λ Σ over the selected indices of Term((xk + sj) + y)      (the value prox_value! returns)
+#   qy = Σ over all i of q[i] y[i], with the q that was passed, not q_scale .* q       yy = Σ over all i of y[i]^2
+# xkn (a device vector that is none of y, q, ψ.xk, ψ.sj, l, u; or nothing) receives (xk + sj) + y.
+# `out` = a ROCVector{Float64} of at least 3 elements: the three sums stay on the device, nothing is read back and the
+# call does not synchronise; returns (y, out).  y must not be q.  Float64 device vectors, separable operators only.
+# Headline operator and the unboxed ℓ1 norm shown; spx_proxstep_l0 / lhalf / l0_box / lhalf_box follow the same pattern.
+# ---------------------------------------------------------------------------------------------
+function prox_step!(y::DVec, ψ::ShiftedNormL1Box{Float64, <:DVec, <:DVec, <:DVec}, q::DVec, σ::Float64;
+                    q_scale::Float64 = 1.0, xkn::Union{Nothing, DVec} = nothing, out::Union{Nothing, DVec} = nothing)
+  n = length(ψ.xk)
+  (length(y) == n && length(q) == n && (xkn === nothing || length(xkn) == n)) || throw(BoundsError())
+  (out === nothing || length(out) >= 3) || throw(ArgumentError("out needs at least 3 elements"))
+  m = mask_for(ψ)
+  stats = zeros(Cdouble, 3)
+  check(ccall((:spx_proxstep_l1_box, libspx), Cint,
+              (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int64, Cdouble, Cdouble,
+               Ptr{Cdouble}, Ptr{Cdouble}, Cdouble, Cdouble, Ptr{UInt8}, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+              ctx(), dptr(y), dptr(q), dptr(ψ.xk), dptr(ψ.sj), n, ψ.λ, σ,
+              dptr(vec_or_nothing(ψ.l)), dptr(vec_or_nothing(ψ.u)), scal(ψ.l), scal(ψ.u),
+              mptr(m), q_scale, dptr(xkn), out === nothing ? pointer(stats) : Ptr{Cdouble}(C_NULL), dptr(out)))
+  return out === nothing ? (y, stats[1], stats[2], stats[3]) : (y, out)
+end
+function prox_step!(y::DVec, ψ::ShiftedNormL1{Float64, <:DVec, <:DVec, <:DVec}, q::DVec, σ::Float64;
+                    q_scale::Float64 = 1.0, xkn::Union{Nothing, DVec} = nothing, out::Union{Nothing, DVec} = nothing)
+  n = length(ψ.xk)
+  (length(y) == n && length(q) == n && (xkn === nothing || length(xkn) == n)) || throw(BoundsError())
+  (out === nothing || length(out) >= 3) || throw(ArgumentError("out needs at least 3 elements"))
+  stats = zeros(Cdouble, 3)
+  check(ccall((:spx_proxstep_l1, libspx), Cint,
+              (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int64, Cdouble, Cdouble, Cdouble,
+               Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+              ctx(), dptr(y), dptr(q), dptr(ψ.xk), dptr(ψ.sj), n, ψ.λ, σ, q_scale,
+              dptr(xkn), out === nothing ? pointer(stats) : Ptr{Cdouble}(C_NULL), dptr(out)))
+  return out === nothing ? (y, stats[1], stats[2], stats[3]) : (y, out)
+end
+
+# ---------------------------------------------------------------------------------------------
 # l1 norm + l2-ball trust region      src/shiftedNormL1B2.jl:50-67   (χ = NormL2(χ.lambda))
 # ---------------------------------------------------------------------------------------------
 function prox!(y::DVec, ψ::ShiftedProximalOperators.ShiftedNormL1B2{Float64, <:DVec, <:DVec, <:DVec}, q::DVec, σ::Float64)

@@ -423,6 +423,23 @@ struct WithValue : Base {
     return sel ? Term{}((x + s) + y) : 0.0;
   }
 };
+// prox! fused with the step statistics of a solver iteration (spx_proxstep_*): besides the h terms the lane that computes
+// y[i] adds q[i] * y[i] (q as passed, not qscale * q) and y[i]^2 over ALL i, and stores (xk[i] + sj[i]) + y[i] -- the point
+// at which h is evaluated -- to xkn when that is not NULL.  Three partial sums per slot, in three planes `plane` doubles
+// apart (partials[slot], partials[plane + slot], partials[2 plane + slot]), each added in the order the single sum is.
+template <class Base, class Term>
+struct WithStep : WithValue<Base, Term> {
+  static constexpr bool kStep = true;
+  double* xkn = nullptr;  // NULL: no store
+  int64_t plane = 0;      // doubles between the planes of `partials`
+};
+template <class Op, class = void>
+struct StepMode { static constexpr bool value = false; };
+template <class Op>
+struct StepMode<Op, decltype((void)Op::kStep)> { static constexpr bool value = Op::kStep; };
+template <class Op>
+constexpr bool kStepOf = StepMode<Op>::value;
+
 __device__ __forceinline__ double block_sum4(double v, double* lds4) {  // 256-lane workgroup
   v = wave_sum(v);
   __syncthreads();
@@ -477,6 +494,75 @@ __device__ __forceinline__ void value_publish(const Op& op, int64_t slot, double
   }
 }
 
+// value_reduce_small<true> on the three planes of a WithStep call at once: the 24 loads of a lane are in flight together and
+// the wavefronts' sums cross one pair of barriers -- one memory round trip at the end of the launch instead of three -- while
+// every plane is added with the statements, hence in the order and to the bits, of value_reduce_small.
+__device__ __forceinline__ void value_reduce_small3(const double* partials, int64_t plane, int count, double (&out)[3]) {
+  __shared__ double vr3_lds[3][4];
+  const int t = threadIdx.x;
+  double v8[3][8];
+#pragma unroll
+  for (int p = 0; p < 3; ++p) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int i = t + k * 256;
+      const bool in = t < 256 && i < count;
+      v8[p][k] = in ? spx_atomic_load_f64(partials + p * plane + i) : 0.0;
+    }
+  }
+  double acc[3];
+#pragma unroll
+  for (int p = 0; p < 3; ++p) {
+    acc[p] = ((v8[p][0] + v8[p][1]) + (v8[p][2] + v8[p][3])) + ((v8[p][4] + v8[p][5]) + (v8[p][6] + v8[p][7]));
+    acc[p] = wave_sum(acc[p]);
+  }
+  __syncthreads();
+  if ((t & 63) == 0 && t < 256) {
+#pragma unroll
+    for (int p = 0; p < 3; ++p) vr3_lds[p][t >> 6] = acc[p];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int p = 0; p < 3; ++p) out[p] = (vr3_lds[p][0] + vr3_lds[p][1]) + (vr3_lds[p][2] + vr3_lds[p][3]);
+}
+// The three-sum form (WithStep): the workgroup's triple (valid in thread 0) goes to its slot of the three planes; ONE ticket
+// per workgroup publishes all three, and the workgroup that takes the last one adds the three planes, each in the order of
+// the single sum (value_reduce_small3).  Stores {fin_scale * h, <q, y>, <y, y>} to the library's result slots and to fin_target (stats_dev) if set.
+template <class Op>
+__device__ __forceinline__ void value_publish3(const Op& op, int64_t slot, double t0, double t1, double t2) {
+  if (op.fin_hdr == nullptr) {
+    if (threadIdx.x == 0) {
+      op.partials[slot] = t0;
+      op.partials[op.plane + slot] = t1;
+      op.partials[2 * op.plane + slot] = t2;
+    }
+    return;
+  }
+  __shared__ int vp3_last;
+  if (threadIdx.x == 0) {
+    spx_atomic_store_f64(op.partials + slot, t0);
+    spx_atomic_store_f64(op.partials + op.plane + slot, t1);
+    spx_atomic_store_f64(op.partials + 2 * op.plane + slot, t2);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    vp3_last = spx_fin_ticket(op.fin_hdr) ? 1 : 0;
+  }
+  __syncthreads();
+  if (!vp3_last) return;
+  double s3[3];
+  value_reduce_small3(op.partials, op.plane, (int)gridDim.x, s3);
+  if (threadIdx.x == 0) {
+    const double h = op.fin_scale * s3[0];
+    op.fin_result[0] = h;
+    op.fin_result[1] = s3[1];
+    op.fin_result[2] = s3[2];
+    if (op.fin_target) {
+      op.fin_target[0] = h;
+      op.fin_target[1] = s3[1];
+      op.fin_target[2] = s3[2];
+    }
+  }
+}
+
 // partials[0..count) -> *out, fixed order: reproducible run to run
 // target != NULL: also *target = scale * sum (the caller's device double, spx_ctx_set_value_target)
 __global__ __launch_bounds__(1024) void k_value_reduce(const double* partials, int64_t count, double* out, double scale,
@@ -511,6 +597,43 @@ __global__ __launch_bounds__(1024) void k_value_reduce(const double* partials, i
     for (int w = 0; w < 16; ++w) t += lds[w];
     *out = t;
     if (target) *target = scale * t;
+  }
+}
+// The three-sum form: workgroup b adds plane b of the partials -- the statements of k_value_reduce above, in its order (that
+// kernel is left as it is: its code object is part of every spx_proxval_* call) -- and stores out[b] (and target[b] when
+// target != NULL): {scale * h, <q, y>, <y, y>}.  Grid: 3 workgroups.
+__global__ __launch_bounds__(1024) void k_value_reduce3(const double* partials_, int64_t plane, int64_t count, double* out,
+                                                         double scale, double* target) {
+  __shared__ double lds[16];
+  const int b = blockIdx.x;
+  const double* partials = partials_ + (int64_t)b * plane;
+  double t = 0.0;
+  if (count <= kValueFuseMax) {  // (the order of the one-launch form)
+    t = value_reduce_small<false>(partials, (int)count);
+  } else {
+    double a8[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int64_t i0 = threadIdx.x; i0 < count; i0 += 8 * 1024) {
+      double v8[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const int64_t i = i0 + (int64_t)k * 1024;
+        v8[k] = (i < count) ? partials[i < count ? i : 0] : 0.0;
+      }
+#pragma unroll
+      for (int k = 0; k < 8; ++k) a8[k] += v8[k];
+    }
+    double acc = ((a8[0] + a8[1]) + (a8[2] + a8[3])) + ((a8[4] + a8[5]) + (a8[6] + a8[7]));
+    acc = wave_sum(acc);
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      for (int w = 0; w < 16; ++w) t += lds[w];
+    }
+  }
+  if (threadIdx.x == 0) {
+    const double v = (b == 0) ? scale * t : t;
+    out[b] = v;
+    if (target) target[b] = v;
   }
 }
 
@@ -551,6 +674,9 @@ __global__ __launch_bounds__(256) void k_sep_vec(double* y_, const double* q_, c
   const uint16_t* mk = reinterpret_cast<const uint16_t*>(mask_);
   const int64_t ntiles = (n2 + TILE - 1) / TILE;
   double hacc = 0.0;
+  double qacc = 0.0, yacc = 0.0;  // (WithStep) <q, y> and <y, y>
+  f64x2* xn = nullptr;
+  if constexpr (kStepOf<Op>) xn = reinterpret_cast<f64x2*>(op.xkn);
   for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const int64_t base = tile * TILE + threadIdx.x;
     f64x2 vq[UNROLL], vx[UNROLL], vs[UNROLL], vl[UNROLL], vu[UNROLL], vd[UNROLL];
@@ -580,6 +706,11 @@ __global__ __launch_bounds__(256) void k_sep_vec(double* y_, const double* q_, c
         r.x = apply_op(op, vq[k].x, vd[k].x, vx[k].x, vs[k].x, l0, u0, s0);
         r.y = apply_op(op, vq[k].y, vd[k].y, vx[k].y, vs[k].y, l1, u1, s1);
         if constexpr (Op::kObj) hacc += op.hterm(vx[k].x, vs[k].x, r.x, s0) + op.hterm(vx[k].y, vs[k].y, r.y, s1);
+        if constexpr (kStepOf<Op>) {
+          qacc += vq[k].x * r.x + vq[k].y * r.y;
+          yacc += r.x * r.x + r.y * r.y;
+          if (xn) st2<NT>(xn + i, f64x2{(vx[k].x + vs[k].x) + r.x, (vx[k].y + vs[k].y) + r.y});
+        }
         st2<NT>(y + i, r);
       }
     } else {  // last, partial tile
@@ -601,12 +732,23 @@ __global__ __launch_bounds__(256) void k_sep_vec(double* y_, const double* q_, c
           r.x = apply_op(op, a.x, dd.x, b.x, c.x, l0, u0, s0);
           r.y = apply_op(op, a.y, dd.y, b.y, c.y, l1, u1, s1);
           if constexpr (Op::kObj) hacc += op.hterm(b.x, c.x, r.x, s0) + op.hterm(b.y, c.y, r.y, s1);
+          if constexpr (kStepOf<Op>) {
+            qacc += a.x * r.x + a.y * r.y;
+            yacc += r.x * r.x + r.y * r.y;
+            if (xn) xn[i] = f64x2{(b.x + c.x) + r.x, (b.y + c.y) + r.y};
+          }
           y[i] = r;
         }
       }
     }
   }
-  if constexpr (Op::kObj) {
+  if constexpr (kStepOf<Op>) {
+    __shared__ double lds4[4];
+    const double t0 = block_sum4(hacc, lds4);
+    const double t1 = block_sum4(qacc, lds4);
+    const double t2 = block_sum4(yacc, lds4);
+    value_publish3(op, blockIdx.x, t0, t1, t2);
+  } else if constexpr (Op::kObj) {
     __shared__ double lds4[4];
     const double t = block_sum4(hacc, lds4);
     value_publish(op, blockIdx.x, t);
@@ -657,11 +799,17 @@ __global__ __launch_bounds__(256) void k_sep_lds(double* y_, const double* q_, c
       if constexpr (Op::kObj) {
         if (threadIdx.x == 0) op.partials[bid] = 0.0;  // (a slot of its own: every slot the host counts is written)
       }
+      if constexpr (kStepOf<Op>) {
+        if (threadIdx.x == 0) { op.partials[op.plane + bid] = 0.0; op.partials[2 * op.plane + bid] = 0.0; }
+      }
       return;
     }
   }
   const int64_t base = (bid * 4 + wave) * (64 * UNROLL) + lane;  // this lane's first pair
   double hacc = 0.0;
+  double qacc = 0.0, yacc = 0.0;  // (WithStep) <q, y> and <y, y>
+  f64x2* xn = nullptr;
+  if constexpr (kStepOf<Op>) xn = reinterpret_cast<f64x2*>(op.xkn);
   uint16_t vm[UNROLL];
 #pragma unroll
   for (int k = 0; k < UNROLL; ++k) {
@@ -699,9 +847,34 @@ __global__ __launch_bounds__(256) void k_sep_lds(double* y_, const double* q_, c
     if constexpr (Op::kObj) {
       if (i < n2) hacc += op.hterm(b.x, c.x, r.x, s0) + op.hterm(b.y, c.y, r.y, s1);
     }
+    if constexpr (kStepOf<Op>) {
+      if (i < n2) {
+        qacc += a.x * r.x + a.y * r.y;
+        yacc += r.x * r.x + r.y * r.y;
+        // (out of registers: the extra store needs no LDS)
+        if (xn) __builtin_nontemporal_store(f64x2{(b.x + c.x) + r.x, (b.y + c.y) + r.y}, xn + i);
+      }
+    }
     if (i < n2) __builtin_nontemporal_store(r, y + i);
   }
-  if constexpr (Op::kObj) {
+  if constexpr (kStepOf<Op>) {
+    // as below, three doubles per wave: the first 24 bytes of the wave's (consumed) staging area
+    const double t0 = wave_sum(hacc), t1 = wave_sum(qacc), t2 = wave_sum(yacc);
+    if (lane == 0) {
+      double* w = reinterpret_cast<double*>(wl);
+      w[0] = t0; w[1] = t1; w[2] = t2;
+    }
+    __syncthreads();
+    double tb0 = 0.0, tb1 = 0.0, tb2 = 0.0;
+    if (threadIdx.x == 0) {
+      const double* w0 = reinterpret_cast<const double*>(lds);
+      constexpr int stride = NARR * UNROLL * 1024 / 8;
+      tb0 = (w0[0] + w0[stride]) + (w0[2 * stride] + w0[3 * stride]);
+      tb1 = (w0[1] + w0[stride + 1]) + (w0[2 * stride + 1] + w0[3 * stride + 1]);
+      tb2 = (w0[2] + w0[stride + 2]) + (w0[2 * stride + 2] + w0[3 * stride + 2]);
+    }
+    value_publish3(op, bid, tb0, tb1, tb2);
+  } else if constexpr (Op::kObj) {
     // one partial per WORKGROUP (round 3; round 2 wrote one per wavefront: 130 208 of them at n = 1e8, and the ordered
     // reduction behind the pass cost ~25 us of the fused call).  The wave's staging area has been consumed: its first 8 bytes
     // carry the wave's sum to lane 0 of the workgroup, which adds the four in a fixed order.
@@ -727,6 +900,7 @@ __global__ __launch_bounds__(256) void k_sep_scalar(double* y, const double* q, 
   int64_t i = begin + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   double hacc = 0.0;
+  double qacc = 0.0, yacc = 0.0;  // (WithStep) <q, y> and <y, y>
   for (; i < n; i += stride) {
     double li = l_ ? l_[i] : ls;
     double ui = u_ ? u_[i] : us;
@@ -736,9 +910,24 @@ __global__ __launch_bounds__(256) void k_sep_scalar(double* y, const double* q, 
     const double xi = xk[i], si = sj[i];
     const double yi = apply_op(op, q[i], di, xi, si, li, ui, sel);
     if constexpr (Op::kObj) hacc += op.hterm(xi, si, yi, sel);
+    if constexpr (kStepOf<Op>) {
+      qacc += q[i] * yi;
+      yacc += yi * yi;
+      if (op.xkn) op.xkn[i] = (xi + si) + yi;
+    }
     y[i] = yi;
   }
-  if constexpr (Op::kObj) {
+  if constexpr (kStepOf<Op>) {
+    __shared__ double lds4[4];
+    const double t0 = block_sum4(hacc, lds4);
+    const double t1 = block_sum4(qacc, lds4);
+    const double t2 = block_sum4(yacc, lds4);
+    if (threadIdx.x == 0) {
+      op.partials[blockIdx.x] = t0;
+      op.partials[op.plane + blockIdx.x] = t1;
+      op.partials[2 * op.plane + blockIdx.x] = t2;
+    }
+  } else if constexpr (Op::kObj) {
     __shared__ double lds4[4];
     const double t = block_sum4(hacc, lds4);
     if (threadIdx.x == 0) op.partials[blockIdx.x] = t;
@@ -804,17 +993,31 @@ template <class Op>
 static int run_separable(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
                          const double* l, const double* u, double ls, double us, const uint8_t* mask, Op op,
                          const double* d = nullptr, double* value = nullptr /* Op::kObj: sum of the h terms */,
-                         double value_scale = 1.0 /* device-resident value = value_scale * sum */) {
-  if constexpr (Op::kObj) *value = 0.0;
+                         double value_scale = 1.0 /* device-resident value = value_scale * sum */,
+                         double* xkn = nullptr /* WithStep: (xk + sj) + y, or NULL */,
+                         double* stats = nullptr /* WithStep: host double[3], or NULL: nothing is read back */,
+                         double* stats_dev = nullptr /* WithStep: device double[3], or NULL */) {
+  if constexpr (kStepOf<Op>) {
+    if (stats) stats[0] = stats[1] = stats[2] = 0.0;
+    if (n == 0) {
+      if (stats_dev == nullptr) return SPX_OK;
+      SPX_ON_DEVICE(ctx);
+      return spx_zero_async(ctx, stats_dev, 3 * sizeof(double));  // (a kernel, not a memset node)
+    }
+  } else if constexpr (Op::kObj) {
+    *value = 0.0;
+  }
   if (n == 0) return SPX_OK;
   SPX_ON_DEVICE(ctx);
-  double* partials = nullptr;  // ws: [result | pad to 256 B | partial slots]
+  double* partials = nullptr;  // ws: [result(s) | pad to 256 B | partial slots (WithStep: three planes of them)]
   int64_t used = 0;
   if constexpr (Op::kObj) {
     const int64_t maxslots = ((n / 2) / (256 * 3) + 2) * 4 + 2 * (int64_t)ctx->num_cu * 8 + 16;
-    int rcw = spx_ws_reserve(ctx, 256 + (size_t)maxslots * sizeof(double));
+    constexpr int planes = kStepOf<Op> ? 3 : 1;
+    int rcw = spx_ws_reserve(ctx, 256 + (size_t)planes * (size_t)maxslots * sizeof(double));
     if (rcw) return rcw;
     partials = reinterpret_cast<double*>(static_cast<char*>(ctx->ws) + 256);
+    if constexpr (kStepOf<Op>) op.plane = maxslots;
     if (ctx->tune_fewer_launches) {  // (the one-launch form keeps its tickets in the synchronisation state)
       rcw = spx_sync_ready(ctx);
       if (rcw) return rcw;
@@ -825,7 +1028,7 @@ static int run_separable(spx_ctx* ctx, double* y, const double* q, const double*
   // (e.g. view(x, 2:n) of aligned arrays) are peeled: element 0 through the scalar kernel, the rest aligned again.
   auto vec_ok_at = [&](int64_t h) {
     auto a16 = [&](const double* p) { return !p || spx_aligned16(p + h); };
-    return a16(y) && a16(q) && a16(xk) && a16(sj) && a16(d) && a16(l) && a16(u) &&
+    return a16(y) && a16(q) && a16(xk) && a16(sj) && a16(d) && a16(l) && a16(u) && a16(xkn) &&
            (!mask || ((reinterpret_cast<uintptr_t>(mask) + (uintptr_t)h) & 1u) == 0);
   };
   auto launch_scalar = [&](int64_t begin, int64_t end) -> int {
@@ -833,6 +1036,7 @@ static int run_separable(spx_ctx* ctx, double* y, const double* q, const double*
     const int64_t cap = (int64_t)ctx->num_cu * 8;
     if (blocks > cap) blocks = cap;
     if constexpr (Op::kObj) op.partials = partials + used;
+    if constexpr (kStepOf<Op>) op.xkn = xkn;  // (indexed from element 0)
     hipLaunchKernelGGL((k_sep_scalar<Op>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, y, q, d, xk, sj, l, u,
                        mask, ls, us, begin, end, op);
     SPX_LAUNCH_CHECK();
@@ -862,10 +1066,12 @@ static int run_separable(spx_ctx* ctx, double* y, const double* q, const double*
       if (ctx->tune_fewer_launches && head == 0 && 2 * n2 == n) {
         fh = spx_sync_header(ctx);
         op.fin_result = reinterpret_cast<double*>(ctx->ws);
-        op.fin_target = ctx->value_target;
+        if constexpr (kStepOf<Op>) op.fin_target = stats_dev;  // (the context's value target does not apply)
+        else op.fin_target = ctx->value_target;
         op.fin_scale = value_scale;
       }
     }
+    if constexpr (kStepOf<Op>) op.xkn = xkn ? xkn + head : nullptr;
     if constexpr (Op::kBox) {
       const bool vecb = (l || u);
       const bool msk = (mask != nullptr);
@@ -884,7 +1090,17 @@ static int run_separable(spx_ctx* ctx, double* y, const double* q, const double*
     int rct = launch_scalar(done, n);
     if (rct) return rct;
   }
-  if constexpr (Op::kObj) {
+  if constexpr (kStepOf<Op>) {
+    double* result = reinterpret_cast<double*>(ctx->ws);  // {value_scale * h, <q, y>, <y, y>}
+    if (!fused) {
+      hipLaunchKernelGGL(k_value_reduce3, dim3(3), dim3(1024), 0, ctx->stream, (const double*)partials, op.plane, used,
+                         result, value_scale, stats_dev);
+      SPX_LAUNCH_CHECK();
+    }
+    if (stats == nullptr) return SPX_OK;  // device results only: the call returns after enqueueing
+    SPX_HIP(hipMemcpyAsync(stats, result, 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    SPX_HIP(hipStreamSynchronize(ctx->stream));
+  } else if constexpr (Op::kObj) {
     double* result = reinterpret_cast<double*>(ctx->ws);
     if (!fused) {
       hipLaunchKernelGGL(k_value_reduce, dim3(1), dim3(1024), 0, ctx->stream, (const double*)partials, used, result,
@@ -1011,6 +1227,71 @@ SPX_EXPORT int spx_proxval_lhalf_box(spx_ctx* ctx, double* y, const double* q, c
                                      double l_scalar, double u_scalar, const uint8_t* sel_mask, double q_scale, double* value) {
   return run_proxval<OpLhalfBox, HTermLhalf>(ctx, y, q, xk, sj, n, l_vec, u_vec, l_scalar, u_scalar, sel_mask,
                                              OpLhalfBox{sigma * lambda / 4, lambda, 0.5 / sigma}, lambda, q_scale, value);
+}
+
+// ---------------------------------------------------------------------------------------------
+// prox! + step statistics in one pass (spx_proxstep_*): y, xkn = (xk + sj) + y, and {h, <q, y>, <y, y>} to a host double[3]
+// (synchronous) and / or a device double[3] (enqueue only).  Float64, device pointers, the six separable operators.
+// ---------------------------------------------------------------------------------------------
+template <class Base, class Term>
+static int run_proxstep(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
+                        const double* l, const double* u, double ls, double us, const uint8_t* mask, Base base,
+                        double lambda, double q_scale, double* xkn, double* stats, double* stats_dev) {
+  int rc = spx_check_common(ctx, y, q, xk, sj, n);
+  if (rc) return rc;
+  SPX_REQUIRE(stats != nullptr || stats_dev != nullptr, "stats and stats_dev are both NULL");
+  SPX_REQUIRE(y == nullptr || y != q, "y aliases q (<q, y> of an overwritten q)");
+  if (xkn != nullptr) {
+    const void* x = xkn;
+    SPX_REQUIRE(x != y && x != q && x != xk && x != sj && x != l && x != u && x != mask, "xkn is one of the other vectors");
+  }
+  // the host copy synchronises: refused under a capture before anything is enqueued
+  if (stats != nullptr) { rc = spx_require_not_capturing(ctx, "returning the step statistics to the host (pass stats = NULL)"); if (rc) return rc; }
+  WithStep<Base, Term> op{};
+  static_cast<Base&>(op) = base;
+  op.qscale = q_scale;
+  return run_separable(ctx, y, q, xk, sj, n, l, u, ls, us, mask, op, nullptr, nullptr, lambda, xkn, stats, stats_dev);
+}
+
+SPX_EXPORT int spx_proxstep_l1(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
+                               double lambda, double sigma, double q_scale, double* xkn, double* stats, double* stats_dev) {
+  return run_proxstep<OpL1, HTermL1>(ctx, y, q, xk, sj, n, nullptr, nullptr, 0.0, 0.0, nullptr, OpL1{lambda * sigma},
+                                     lambda, q_scale, xkn, stats, stats_dev);
+}
+SPX_EXPORT int spx_proxstep_l0(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
+                               double lambda, double sigma, double q_scale, double* xkn, double* stats, double* stats_dev) {
+  return run_proxstep<OpL0, HTermL0>(ctx, y, q, xk, sj, n, nullptr, nullptr, 0.0, 0.0, nullptr,
+                                     OpL0{std::sqrt(2 * lambda * sigma)}, lambda, q_scale, xkn, stats, stats_dev);
+}
+SPX_EXPORT int spx_proxstep_lhalf(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
+                                  double lambda, double sigma, double q_scale, double* xkn, double* stats,
+                                  double* stats_dev) {
+  const double nl = sigma * lambda;
+  const double p = std::pow(54.0, 1.0 / 3.0) * std::pow(2 * nl, 2.0 / 3.0) / 4;
+  return run_proxstep<OpLhalf, HTermLhalf>(ctx, y, q, xk, sj, n, nullptr, nullptr, 0.0, 0.0, nullptr, OpLhalf{nl / 4, p},
+                                           lambda, q_scale, xkn, stats, stats_dev);
+}
+SPX_EXPORT int spx_proxstep_l1_box(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
+                                   double lambda, double sigma, const double* l_vec, const double* u_vec, double l_scalar,
+                                   double u_scalar, const uint8_t* sel_mask, double q_scale, double* xkn, double* stats,
+                                   double* stats_dev) {
+  return run_proxstep<OpL1Box, HTermL1>(ctx, y, q, xk, sj, n, l_vec, u_vec, l_scalar, u_scalar, sel_mask,
+                                        OpL1Box{sigma * lambda}, lambda, q_scale, xkn, stats, stats_dev);
+}
+SPX_EXPORT int spx_proxstep_l0_box(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
+                                   double lambda, double sigma, const double* l_vec, const double* u_vec, double l_scalar,
+                                   double u_scalar, const uint8_t* sel_mask, double q_scale, double* xkn, double* stats,
+                                   double* stats_dev) {
+  return run_proxstep<OpL0Box, HTermL0>(ctx, y, q, xk, sj, n, l_vec, u_vec, l_scalar, u_scalar, sel_mask,
+                                        OpL0Box{2 * lambda * sigma}, lambda, q_scale, xkn, stats, stats_dev);
+}
+SPX_EXPORT int spx_proxstep_lhalf_box(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj,
+                                      int64_t n, double lambda, double sigma, const double* l_vec, const double* u_vec,
+                                      double l_scalar, double u_scalar, const uint8_t* sel_mask, double q_scale,
+                                      double* xkn, double* stats, double* stats_dev) {
+  return run_proxstep<OpLhalfBox, HTermLhalf>(ctx, y, q, xk, sj, n, l_vec, u_vec, l_scalar, u_scalar, sel_mask,
+                                              OpLhalfBox{sigma * lambda / 4, lambda, 0.5 / sigma}, lambda, q_scale, xkn,
+                                              stats, stats_dev);
 }
 
 // ---------------------------------------------------------------------------------------------

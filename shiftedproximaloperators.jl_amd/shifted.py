@@ -825,6 +825,57 @@ def prox_value(ψ, q, σ, q_scale=1.0):
     return prox_value_bang(ψ.sol, ψ, q, σ, q_scale)
 
 
+def prox_step_bang(y, ψ, q, σ, q_scale=1.0, xkn=None, out=None):
+    """prox!(y, ψ, q_scale .* q, σ) and the step statistics of a solver iteration in ONE pass over the vectors (what R2 / TR
+    do around the prox: `h(xk + s)`, `dot(∇f, s)`, `xk + s`, `‖s‖`):
+
+        h  = λ · Σ over the SELECTED indices of Term((xk + sj) + y)   -- the value prox_value returns (Box forms: h part only)
+        qy = Σ over ALL i of q[i] · y[i]   -- with the UNSCALED q as passed, not q_scale · q (R2: q = ∇f, q_scale = -ν gives ∇fᵀs)
+        yy = Σ over ALL i of y[i]²
+        xkn[i] = (xk[i] + sj[i]) + y[i] for every i, selected or not (a device vector like ψ.xk that is none of y, q, ψ.xk,
+                 ψ.sj, l, u; None: not stored)
+
+    out=None: returns (y, h, qy, yy) as Python floats (synchronises).  out = a float64 device tensor with at least 3
+    elements: out[0:3] = (h, qy, yy), nothing is read back and the stream is not synchronised; returns (y, out) -- this form
+    can be captured into a graph once the same call has run before.  `device_values` does not apply.  y must not be q.
+    Supported: ShiftedNormL1 / NormL0 / RootNormLhalf and their Box forms on device Float64 vectors; host ψ, Float32, the
+    group, top-r and ShiftedNormL1B2 operators raise TypeError."""
+    if not isinstance(ψ, (_Unboxed, _Boxed)) or ψ.host or ψ.f32:
+        raise TypeError("prox_step is available for ShiftedNormL1 / ShiftedNormL0 / ShiftedRootNormLhalf and their Box forms "
+                        "on device Float64 vectors (no host ψ, Float32, group, top-r or ShiftedNormL1B2 form)")
+    n = _n(ψ.xk)
+    _vec(q, "q", n, like=ψ.xk)
+    _vec(y, "y", n, like=ψ.xk)
+    if xkn is not None:
+        _vec(xkn, "xkn", n, like=ψ.xk)
+    if y is q:
+        raise TypeError("prox_step: y must not be q (qy is taken with the q that was passed)")
+    if out is not None and not (type(out) is _Tensor and out.is_cuda and out.dtype == torch.float64 and out.dim() == 1
+                                and out.numel() >= 3 and out.stride(0) == 1 and out.device == ψ.xk.device):
+        raise TypeError("out must be a contiguous float64 device tensor with at least 3 elements on ψ.xk's device")
+    ψ._refresh()
+    L, ctx = _lib.load(), _ctx(_dev(y))
+    host = (ctypes.c_double * 3)() if out is None else None
+    tail = (float(q_scale), _ptr(xkn), host, ctypes.c_void_p(out.data_ptr()) if out is not None else _NULL)
+    fn = getattr(L, ψ._fn.replace("spx_prox_", "spx_proxstep_"))
+    if isinstance(ψ, _Boxed):
+        lv = None if _is_real(ψ.l) else _vec(ψ.l, "l", n, like=y)
+        uv = None if _is_real(ψ.u) else _vec(ψ.u, "u", n, like=y)
+        _lib.check(fn(ctx, _ptr(y), _ptr(q), _ptr(ψ.xk), _ptr(ψ.sj), n, ψ.h.lam, float(σ), _ptr(lv), _ptr(uv),
+                      float(ψ.l) if lv is None else 0.0, float(ψ.u) if uv is None else 0.0,
+                      _ptr(ψ._mask[0]) if ψ._mask is not None else ctypes.c_void_p(0), *tail))
+    else:
+        _lib.check(fn(ctx, _ptr(y), _ptr(q), _ptr(ψ.xk), _ptr(ψ.sj), n, ψ.h.lam, float(σ), *tail))
+    if out is not None:
+        return y, out
+    return y, host[0], host[1], host[2]
+
+
+def prox_step(ψ, q, σ, q_scale=1.0, xkn=None, out=None):
+    """prox_step_bang(ψ.sol, ψ, q, σ, ...): (ψ.sol, h, qy, yy), or (ψ.sol, out) with a device `out`; see prox_step_bang"""
+    return prox_step_bang(ψ.sol, ψ, q, σ, q_scale, xkn, out)
+
+
 def iprox_bang(y, ψ, g, d, check=True):
     """iprox!(y, ψ, g, d): y <- argmin_t ½ tᵀDt + gᵀt + ψ(t), D = diag(d); returns y.  Defined for ShiftedNormL1/L0 and
     their Box forms (as in the reference).  The unboxed forms assert d .> 0 like the reference (`check=True`
