@@ -309,8 +309,9 @@ int spx_proxval_lhalf_box(spx_ctx* ctx, double* y, const double* q, const double
  * ticket per workgroup publishes its three partial sums, and the last workgroup (or the separate launch) adds each of the
  * three in the order the single sum of spx_proxval_X is added.  [0] has the bits of spx_proxval_X's value whenever both
  * calls take the same kernel form (same tuning keys, xkn aligned like the other vectors).
- * Float64 and device pointers only: there is no Float32 form, no host-pointer twin (spx_host_*), and no group / top-r /
- * ShiftedNormL1B2 form -- their fused-value kernels have different exits. */
+ * Float64 and device pointers only: there is no Float32 form, no host-pointer twin (spx_host_*), and no top-r /
+ * ShiftedNormL1B2 form -- their fused-value kernels have different exits.  The group operators have a form of their own:
+ * spx_proxstep_group_l2[_binf], below. */
 int spx_proxstep_l1(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
                     double lambda, double sigma, double q_scale, double* xkn, double* stats, double* stats_dev);
 int spx_proxstep_l0(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
@@ -509,6 +510,34 @@ int spx_proxval_group_l2(spx_ctx* ctx, double* y, const double* q, const double*
 int spx_proxval_group_l2_binf(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
                               const int64_t* group_offsets, int64_t group_size, int64_t ngroups, const double* lambda_vec,
                               double sigma, double delta, double q_scale, double* value);
+
+/* prox! fused with the step statistics of a solver iteration, group forms -- the contract of spx_proxstep_* (above) on the
+ * group operators.  The argument list of spx_proxval_group_l2[_binf] up to and including q_scale, then the tail of spx_proxstep_*:
+ *   y        : bit-identical to spx_prox_group_l2[_binf] at q_scale * q, on every layout and route, with tuning key 9 at 0 or 1.
+ *   xkn      : device pointer to n doubles, or NULL.  xkn[i] = (xk[i] + sj[i]) + y[i] for EVERY i in [0, n), from whatever y
+ *              holds after the call -- on CSR layouts also at the indices no group contains.  It must not overlap y, q, xk or
+ *              sj: a pointer EQUAL to one of them returns SPX_ERR_INVALID_ARG, nothing is launched.  Any 8-byte alignment.
+ *   [0]      : the value spx_proxval_group_l2[_binf] returns for the same call -- the same bits on the same layout and route
+ *              (xkn aligned like the other vectors).
+ *   [1]      : sum over ALL i of q[i] * y[i], q AS PASSED (not q_scale * q); any q_scale, 0 and non-finite ones included.
+ *   [2]      : sum over ALL i of y[i]^2.  (Indices no group contains count in [1] and [2] with the y the operator leaves there.)
+ *   stats / stats_dev, capture, spx_ctx_set_value_target (no effect), y == q (refused): as spx_proxstep_*.  The sums are added
+ *              in a fixed order: two runs on the same inputs give the same bits.
+ *   n == 0 or ngroups == 0: three zeros, stored to stats_dev by a kernel; y as the plain operator leaves it.
+ * FUSED route -- uniform groups of at most 512 elements (group_offsets == NULL, the register-tile kernels): y, xkn and the
+ * three sums come out of the launches that store y; 40 B/element + one more read of q that is served on chip (the kernel
+ * keeps no copy of q across the group's reductions).  One launch (plain), two (Binf).
+ * COMPOSED routes -- every other layout (uniform groups above 512, one group over the whole vector / teams of workgroups,
+ * every CSR layout with or without a size bound): inside the same call and on the same stream, spx_proxval_group_l2[_binf]'s
+ * launches unchanged (y and [0]), then ONE streaming launch that reads q, y, xk, sj, stores xkn and adds [1] and [2].  Same
+ * contract, correct but not fast: 40 B/element more than spx_proxval_group_*.
+ * Float64 and device pointers only; no spx_host_* twin, no gather-index form. */
+int spx_proxstep_group_l2(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
+                          const int64_t* group_offsets, int64_t group_size, int64_t ngroups, const double* lambda_vec,
+                          double sigma, double q_scale, double* xkn, double* stats, double* stats_dev);
+int spx_proxstep_group_l2_binf(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
+                               const int64_t* group_offsets, int64_t group_size, int64_t ngroups, const double* lambda_vec,
+                               double sigma, double delta, double q_scale, double* xkn, double* stats, double* stats_dev);
 
 /* ShiftedGroupNormL2.prox! on Float32 vectors (round 3; the method is generic in R, src/shiftedGroupNormL2.jl:52-79): every
  * elementwise operation in Float32; the group norm is accumulated in Float64 and rounded once (the reference's `norm` is

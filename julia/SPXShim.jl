@@ -221,7 +221,8 @@ end
 #   qy = Σ over all i of q[i] y[i], with the q that was passed, not q_scale .* q       yy = Σ over all i of y[i]^2
 # xkn (a device vector that is none of y, q, ψ.xk, ψ.sj, l, u; or nothing) receives (xk + sj) + y.
 # `out` = a ROCVector{Float64} of at least 3 elements: the three sums stay on the device, nothing is read back and the
-# call does not synchronise; returns (y, out).  y must not be q.  Float64 device vectors, separable operators only.
+# call does not synchronise; returns (y, out).  y must not be q.  Float64 device vectors; the group operators' methods
+# (spx_proxstep_group_l2[_binf]) sit with their layout helpers further down.
 # Headline operator and the unboxed ℓ1 norm shown; spx_proxstep_l0 / lhalf / l0_box / lhalf_box follow the same pattern.
 # ---------------------------------------------------------------------------------------------
 function prox_step!(y::DVec, ψ::ShiftedNormL1Box{Float64, <:DVec, <:DVec, <:DVec}, q::DVec, σ::Float64;
@@ -374,6 +375,45 @@ end
 function prox_value!(y::DVec, ψ::ShiftedGroupNormL2Binf{Float64, RR, I, <:DVec, <:DVec, <:DVec}, q::DVec, σ::Float64;
                      q_scale::Float64 = 1.0) where {RR, I}
   group_value_call(y, ψ, q, σ, q_scale, ψ.Δ)   # the h part of ψ(y): the prox lies inside the trust region
+end
+
+# prox! fused with the step statistics, group forms (spx_proxstep_group_l2[_binf]; prox_step! above for the separable operators):
+# (y, h, qy, yy) with h = Σ_g λ_g ‖((xk + sj) + y)[g]‖ as prox_value! returns it, qy and yy over ALL i with the q that was passed;
+# xkn receives (xk + sj) + y at every index.  `out`: the three sums stay on the device, returns (y, out).  Contiguous groups only.
+# One pass over the vectors for uniform groups of at most 512 elements; prox_value!'s launches plus one streaming launch beyond.
+function group_step_call(y, ψ, q, σ, q_scale, xkn, out, extra...)   # extra = (Δ,) for the Binf form
+  n = length(ψ.xk)
+  (length(y) == n && length(q) == n && (xkn === nothing || length(xkn) == n)) || throw(BoundsError())
+  (out === nothing || length(out) >= 3) || throw(ArgumentError("out needs at least 3 elements"))
+  L = layout_for(ψ.h, n)
+  L.gather && throw(ArgumentError("prox_step! needs contiguous groups"))
+  offp = L.offsets === nothing ? Ptr{Int64}(C_NULL) : Ptr{Int64}(UInt(pointer(L.offsets)))
+  stats = zeros(Cdouble, 3)
+  sp = out === nothing ? pointer(stats) : Ptr{Cdouble}(C_NULL)
+  if isempty(extra)
+    check(ccall((:spx_proxstep_group_l2, libspx), Cint,
+                (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int64, Ptr{Int64}, Int64, Int64,
+                 Ptr{Cdouble}, Cdouble, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                ctx(), dptr(y), dptr(q), dptr(ψ.xk), dptr(ψ.sj), n, offp, L.gsize, L.ngroups, dptr(L.lambda), σ, q_scale,
+                dptr(xkn), sp, dptr(out)))
+  else
+    check(ccall((:spx_proxstep_group_l2_binf, libspx), Cint,
+                (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int64, Ptr{Int64}, Int64, Int64,
+                 Ptr{Cdouble}, Cdouble, Cdouble, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                ctx(), dptr(y), dptr(q), dptr(ψ.xk), dptr(ψ.sj), n, offp, L.gsize, L.ngroups, dptr(L.lambda), σ,
+                extra[1], q_scale, dptr(xkn), sp, dptr(out)))
+  end
+  return out === nothing ? (y, stats[1], stats[2], stats[3]) : (y, out)
+end
+
+function prox_step!(y::DVec, ψ::ShiftedGroupNormL2{Float64, RR, I, <:DVec, <:DVec, <:DVec}, q::DVec, σ::Float64;
+                    q_scale::Float64 = 1.0, xkn::Union{Nothing, DVec} = nothing, out::Union{Nothing, DVec} = nothing) where {RR, I}
+  group_step_call(y, ψ, q, σ, q_scale, xkn, out)
+end
+
+function prox_step!(y::DVec, ψ::ShiftedGroupNormL2Binf{Float64, RR, I, <:DVec, <:DVec, <:DVec}, q::DVec, σ::Float64;
+                    q_scale::Float64 = 1.0, xkn::Union{Nothing, DVec} = nothing, out::Union{Nothing, DVec} = nothing) where {RR, I}
+  group_step_call(y, ψ, q, σ, q_scale, xkn, out, ψ.Δ)
 end
 
 # prox! fused with h at the result, ShiftedNormL1B2 (spx_proxval_l1_b2): the one launch of prox! with λ‖xk + sj + y‖₁ formed

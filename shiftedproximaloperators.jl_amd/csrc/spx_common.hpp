@@ -323,7 +323,8 @@ struct SpxSyncHeader {
   unsigned int fin_top;       // the objective kernels' "last workgroup" tickets (spx_fin_ticket below); zero between launches
   int fin_flag;               // ... and their infeasibility bits; zero between launches
   double b2_value;            // spx_proxval_l1_b2 without a device value target: the launch stores h here, the host reads it back
-  int pad[20];
+  double grp_step_h;          // spx_proxstep_group_*, composed routes: h of the value call, picked up by the tail launch (spx_group.hip)
+  int pad[18];
   unsigned int fin_class[kSpxBarSplit * 32];  // first-level tickets, one 128-byte line each
 };
 static_assert(sizeof(SpxSyncHeader) == 2 * kSpxBarSplit * 32 * 4 + 128 + kSpxBarSplit * 32 * 4, "SpxSyncHeader layout");

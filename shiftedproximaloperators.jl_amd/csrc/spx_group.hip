@@ -71,45 +71,83 @@ struct GroupVal {
   double* dterm;              // [group]
   int lpg_main;               // lanes per group of the main launch's tile (bit -> group)
 };
+// The step form (spx_proxstep_group_l2[_binf]): three sums where GroupVal has one -- [0] the h terms as above, [1] q[i] * y[i]
+// (q as passed, not qs * q), [2] y[i]^2 -- and xkn = (xk + sj) + y stored next to y.  Three planes of everything that carries a sum:
+// the partials `nmain` doubles apart in `part` (the flags behind the third), the class sums in GroupStepWs, the terms of the
+// handed-on groups `dplane` doubles apart in `dterm`.  ONE ticket per workgroup publishes its three partials, and every plane is
+// added with the statements, hence in the order and to the bits, of the single sum.
+struct GroupStepWs {
+  double result[3];    // read back by the host
+  double cpart[3][8];  // class sums of the three planes of partials
+  double cany[8];      // ... and of the flags
+  double pad[29];      // (the partials start on a 256-byte boundary)
+};
+struct GroupStep : GroupVal {
+  double* xkn;        // (xk + sj) + y, or NULL
+  double* stats_dev;  // the caller's device double[3], or NULL
+  GroupStepWs* sws;   // (takes the place of `ws`)
+  int64_t dplane;     // doubles between the planes of `dterm`
+};
+static_assert(sizeof(GroupValWs) == 256 && sizeof(GroupStepWs) == 512, "the partials start on a 256-byte boundary");
+template <class GV>
+constexpr int kGroupSums = std::is_same<GV, GroupStep>::value ? 3 : 1;
 // x[i0], x[i0 + step], ... (cnt of them) added by the workgroup: lane t takes the elements t, t + 256, ..., eight loads in flight
-template <bool ATOMIC>
-__device__ __forceinline__ double gval_strided_sum(const double* x, int64_t i0, int64_t step, int64_t cnt) {
-  double a = 0.0;
-  for (int64_t k0 = threadIdx.x; k0 < cnt; k0 += 256 * 8) {
-    double v[8];
+// -- of each of the NS planes `plane` doubles apart, all of them issued before the first is added
+template <bool ATOMIC, int NS>
+__device__ __forceinline__ void gval_strided_sum(const double* x, int64_t plane, int64_t i0, int64_t step, int64_t cnt, double (&a)[NS]) {
 #pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const int64_t k = k0 + 256 * u;
-      const double* p = x + i0 + step * (k < cnt ? k : 0);
-      const double w = ATOMIC ? spx_atomic_load_f64(p) : *p;
-      v[u] = k < cnt ? w : 0.0;
+  for (int p = 0; p < NS; ++p) a[p] = 0.0;
+  for (int64_t k0 = threadIdx.x; k0 < cnt; k0 += 256 * 8) {
+    double v[NS][8];
+#pragma unroll
+    for (int p = 0; p < NS; ++p) {
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int64_t k = k0 + 256 * u;
+        const double* q = x + p * plane + i0 + step * (k < cnt ? k : 0);
+        const double w = ATOMIC ? spx_atomic_load_f64(q) : *q;
+        v[p][u] = k < cnt ? w : 0.0;
+      }
     }
 #pragma unroll
-    for (int u = 0; u < 8; ++u) a += v[u];
+    for (int p = 0; p < NS; ++p) {
+#pragma unroll
+      for (int u = 0; u < 8; ++u) a[p] += v[p][u];
+    }
   }
-  return a;
 }
-// `acc`: the lane's sum (non-zero in one lane per group); `handed`: this lane handed a group on.  Every lane of the (256-lane)
-// workgroup must call it.
-__device__ __forceinline__ void gval_finish(double acc, bool handed, const GroupVal& gv) {
-  __shared__ double gv_lds[4];
+// `acc`: the lane's sums (GroupVal: one, non-zero in one lane per group; GroupStep: three); `handed`: this lane handed a group on.
+// Every lane of the (256-lane) workgroup must call it.
+template <class GV>
+__device__ __forceinline__ void gval_finish(double (&acc)[kGroupSums<GV>], bool handed, const GV& gv) {
+  constexpr int NS = kGroupSums<GV>;
+  __shared__ double gv_lds[NS][4];
   __shared__ int gv_flag;
-  auto block_sum = [&](double v) {
-    v = wave_sum(v);
+  auto block_sum = [&](auto& v) {  // (every plane crosses the one pair of barriers)
+    constexpr int M = sizeof(v) / sizeof(double);
+#pragma unroll
+    for (int p = 0; p < M; ++p) v[p] = wave_sum(v[p]);
     __syncthreads();
-    if ((threadIdx.x & 63) == 0) gv_lds[threadIdx.x >> 6] = v;
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+      for (int p = 0; p < M; ++p) gv_lds[p][threadIdx.x >> 6] = v[p];
+    }
     __syncthreads();
-    return (gv_lds[0] + gv_lds[1]) + (gv_lds[2] + gv_lds[3]);
+#pragma unroll
+    for (int p = 0; p < M; ++p) v[p] = (gv_lds[p][0] + gv_lds[p][1]) + (gv_lds[p][2] + gv_lds[p][3]);
   };
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (this wavefront's dterm stores have left before its workgroup takes a ticket)
   if (!gv.behind) {
-    acc = block_sum(acc);
+    block_sum(acc);
     if (gv.any != nullptr) {
       const int any = __syncthreads_or(handed ? 1 : 0);
       if (threadIdx.x == 0) gv.any[blockIdx.x] = any ? 1.0 : 0.0;
     }
     if (gv.hdr == nullptr) {
-      if (threadIdx.x == 0) gv.part[blockIdx.x] = acc;
+      if (threadIdx.x == 0) {
+#pragma unroll
+        for (int p = 0; p < NS; ++p) gv.part[(int64_t)p * gv.nmain + blockIdx.x] = acc[p];
+      }
       return;
     }
   }
@@ -117,7 +155,10 @@ __device__ __forceinline__ void gval_finish(double acc, bool handed, const Group
   const unsigned int classes = grid < (unsigned)kSpxBarSplit ? grid : (unsigned)kSpxBarSplit;
   __syncthreads();
   if (threadIdx.x == 0) {
-    if (!gv.behind) spx_atomic_store_f64(&gv.part[blockIdx.x], acc);
+    if (!gv.behind) {
+#pragma unroll
+      for (int p = 0; p < NS; ++p) spx_atomic_store_f64(&gv.part[(int64_t)p * gv.nmain + blockIdx.x], acc[p]);
+    }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     const unsigned int want = (grid - j + (unsigned)kSpxBarSplit - 1u) / (unsigned)kSpxBarSplit;  // workgroups j, j + 8, ...
     const unsigned int c = __hip_atomic_fetch_add(&gv.hdr->fin_class[32u * j], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -127,15 +168,23 @@ __device__ __forceinline__ void gval_finish(double acc, bool handed, const Group
   __syncthreads();
   if (!gv_flag) return;
   // the last workgroup of class j: the partials j, j + classes, ... (and how many of their workgroups handed a group on)
+  double* const cpart = [&] { if constexpr (NS == 1) return &gv.ws->cpart[0]; else return &gv.sws->cpart[0][0]; }();
+  double* const cany = [&] { if constexpr (NS == 1) return &gv.ws->cany[0]; else return &gv.sws->cany[0]; }();
   const int64_t cnt = (int64_t)j < gv.nmain ? ((int64_t)gv.nmain - j + classes - 1) / classes : 0;
-  double a = gv.behind ? gval_strided_sum<false>(gv.part, j, classes, cnt) : gval_strided_sum<true>(gv.part, j, classes, cnt);
-  a = block_sum(a);
-  double f = 0.0;
-  if (gv.any != nullptr && gv.behind) f = block_sum(gval_strided_sum<false>(gv.any, j, classes, cnt));
+  double a[NS];
+  if (gv.behind) gval_strided_sum<false>(gv.part, gv.nmain, j, classes, cnt, a);
+  else gval_strided_sum<true>(gv.part, gv.nmain, j, classes, cnt, a);
+  block_sum(a);
+  double f[1] = {0.0};
+  if (gv.any != nullptr && gv.behind) {
+    gval_strided_sum<false>(gv.any, 0, j, classes, cnt, f);
+    block_sum(f);
+  }
   __syncthreads();
   if (threadIdx.x == 0) {
-    spx_atomic_store_f64(&gv.ws->cpart[j], a);
-    spx_atomic_store_f64(&gv.ws->cany[j], f);
+#pragma unroll
+    for (int p = 0; p < NS; ++p) spx_atomic_store_f64(&cpart[8 * p + j], a[p]);
+    spx_atomic_store_f64(&cany[j], f[0]);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     const unsigned int t = __hip_atomic_fetch_add(&gv.hdr->fin_top, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     gv_flag = (t + 1u == classes) ? 1 : 0;
@@ -144,20 +193,30 @@ __device__ __forceinline__ void gval_finish(double acc, bool handed, const Group
   __syncthreads();
   if (!gv_flag) return;
   // the last workgroup of the launch: the class sums in class order, then the handed-on groups (usually none)
-  __shared__ double gv_total[2];
+  __shared__ double gv_total[NS + 1];
   if (threadIdx.x == 0) {
-    double v = 0.0, n = 0.0;
+    double v[NS], n = 0.0;
+#pragma unroll
+    for (int p = 0; p < NS; ++p) v[p] = 0.0;
     for (unsigned int c = 0; c < classes; ++c) {
-      v += spx_atomic_load_f64(&gv.ws->cpart[c]);
-      n += spx_atomic_load_f64(&gv.ws->cany[c]);
+#pragma unroll
+      for (int p = 0; p < NS; ++p) v[p] += spx_atomic_load_f64(&cpart[8 * p + c]);
+      n += spx_atomic_load_f64(&cany[c]);
     }
-    gv_total[0] = v;
-    gv_total[1] = n;
+#pragma unroll
+    for (int p = 0; p < NS; ++p) gv_total[p] = v[p];
+    gv_total[NS] = n;
   }
   __syncthreads();
-  double total = gv_total[0];
-  if (gv_total[1] != 0.0) {  // (the same in every lane)
-    double d = 0.0;
+  double total[NS];
+#pragma unroll
+  for (int p = 0; p < NS; ++p) total[p] = gv_total[p];
+  if (gv_total[NS] != 0.0) {  // (the same in every lane)
+    double d[NS];
+#pragma unroll
+    for (int p = 0; p < NS; ++p) d[p] = 0.0;
+    int64_t dplane = 0;
+    if constexpr (NS == 3) dplane = gv.dplane;
     const int gpw = 64 / gv.lpg_main;
     for (int64_t b = threadIdx.x; b < gv.nmain; b += 256) {
       if (gv.any[b] == 0.0) continue;
@@ -166,18 +225,28 @@ __device__ __forceinline__ void gval_finish(double acc, bool handed, const Group
         while (m) {
           const int bit = __ffsll((long long)m) - 1;
           m &= m - 1;
-          d += spx_atomic_load_f64(&gv.dterm[(4 * b + w) * gpw + bit / gv.lpg_main]);
+#pragma unroll
+          for (int p = 0; p < NS; ++p) d[p] += spx_atomic_load_f64(&gv.dterm[p * dplane + (4 * b + w) * gpw + bit / gv.lpg_main]);
         }
       }
     }
-    total += block_sum(d);
+    block_sum(d);
+#pragma unroll
+    for (int p = 0; p < NS; ++p) total[p] += d[p];
   }
   if (threadIdx.x == 0) {
-    gv.ws->result = total;
-    if (gv.target) *gv.target = total;
+    if constexpr (NS == 1) {
+      gv.ws->result = total[0];
+      if (gv.target) *gv.target = total[0];
+    } else {
+#pragma unroll
+      for (int p = 0; p < NS; ++p) {
+        gv.sws->result[p] = total[p];
+        if (gv.stats_dev) gv.stats_dev[p] = total[p];
+      }
+    }
   }
 }
-__device__ __forceinline__ void gval_finish(double, bool, const GroupNoVal&) {}
 
 // ---------------------------------------------------------------------------------------------
 // fast path kernel: uniform groups of LPG*EPL elements; LPG lanes own a group, 64/LPG groups per wave;
@@ -207,7 +276,12 @@ __device__ __forceinline__ void gval_finish(double, bool, const GroupNoVal&) {}
 // association of k_obj_group MODE 0 -- into a per-lane sum that gval_finish turns into one partial per workgroup (GroupVal
 // above).  A group this launch does not store (deferred to the LIT launch / the list kernel) is counted by the launch that does.
 // VALUE = false: `gv` is an empty struct and none of this is compiled.
-template <int LPG, int EPL, bool BINF, bool PAIRS, bool LIT = false, bool FULL = false, bool VALUE = false>
+// STEP (spx_proxstep_group_l2[_binf], with VALUE; `gv` is a GroupStep): that lane also stores v = (xk + sj) + y to gv.xkn the way it
+// stores y, and adds q * y and y * y of its elements into two more sums.  q is wanted AS PASSED and the kernel keeps neither q
+// nor qs * q (only S = (qs * q + xk) + sj): it is read again once y is stored -- from the wavefront's staging buffer where the tile
+// came in through LDS (kDma, kPre: the buffer is not reused before the next tile), else from memory, where the lines this
+// wavefront fetched a few microseconds ago are still on chip -- which costs no register across the root find.
+template <int LPG, int EPL, bool BINF, bool PAIRS, bool LIT = false, bool FULL = false, bool VALUE = false, bool STEP = false>
 __global__ __launch_bounds__(256, (BINF && EPL >= 16) ? 2 : SPX_GROUP_WAVES) void k_group_reg(double* y_, const double* q_, const double* xk_, const double* sj_,
                                                     int64_t ngroups, int gsize, const double* __restrict__ lambda,
                                                     double sigma, double delta,
@@ -216,8 +290,9 @@ __global__ __launch_bounds__(256, (BINF && EPL >= 16) ? 2 : SPX_GROUP_WAVES) voi
                                                     int* status /* spx_ctx::status_dev */, int pole_lit /* tuning key 9 */,
                                                     unsigned long long* dcount /* the list's count word: deferred[0], or one of SpxSyncHeader::grp_deferred */,
                                                     unsigned long long* dclear /* LIT: the count word the NEXT call uses, zeroed here (or NULL) */,
-                                                    typename std::conditional<VALUE, GroupVal, GroupNoVal>::type gv) {
+                                                    typename std::conditional<STEP, GroupStep, typename std::conditional<VALUE, GroupVal, GroupNoVal>::type>::type gv) {
   static_assert((EPL % 2) == 0, "EPL must be even (16-byte pairs)");
+  static_assert(VALUE || !STEP, "the step form extends the value form");
   const int64_t GS = gsize;  // <= LPG * EPL
   constexpr int GPW = 64 / LPG;  // groups per wave
   const int lane = threadIdx.x & 63;
@@ -306,6 +381,7 @@ __global__ __launch_bounds__(256, (BINF && EPL >= 16) ? 2 : SPX_GROUP_WAVES) voi
   };
   bool handed_on = false;  // (VALUE) this lane put its group on the deferred list
   double hsum = 0.0;  // (VALUE) lane 0 of each group's lanes: sum of lambda_g * ||((xk + sj) + y)[g]|| over the groups stored here
+  double qsum = 0.0, ysum = 0.0;  // (STEP) every lane: q[i] * y[i] and y[i]^2 over the elements it stored
   for (int64_t g0 = wave * GPW; g0 < ntodo; g0 += nwaves * GPW) {  // wave-uniform trip count
     bool valid = (g0 + slot) < ntodo;
     const int64_t gi = valid ? (g0 + slot) : (ntodo - 1);  // idle slots shadow the last group, no store
@@ -474,6 +550,63 @@ __global__ __launch_bounds__(256, (BINF && EPL >= 16) ? 2 : SPX_GROUP_WAVES) voi
           if (k * LPG + j < gs) y_[base + k * LPG + j] = out[k];
       }
     }
+    if constexpr (STEP) {
+      if (valid && gv.xkn != nullptr) {  // v as the h term formed it, stored the way y is
+        if constexpr (PAIRS) {
+          f64x2* v2 = reinterpret_cast<f64x2*>(gv.xkn + base);
+#pragma unroll
+          for (int k = 0; k < EPL / 2; ++k)
+            if (FULL || k * LPG + j < npairs) {
+              const f64x2 v = f64x2{grp.XS[2 * k] + out[2 * k], grp.XS[2 * k + 1] + out[2 * k + 1]};
+              if constexpr (LPG <= 2 || kPaddedCached) v2[k * LPG + j] = v;
+              else __builtin_nontemporal_store(v, v2 + k * LPG + j);
+            }
+        } else {
+#pragma unroll
+          for (int k = 0; k < EPL; ++k)
+            if (k * LPG + j < gs) gv.xkn[base + k * LPG + j] = grp.XS[k] + out[k];
+        }
+      }
+      asm volatile("" ::: "memory");  // (q is read AGAIN below: the values loaded above are not kept alive across the root find)
+      double qy = 0.0, yy = 0.0;
+      if constexpr (PAIRS) {
+        const f64x2* q2 = reinterpret_cast<const f64x2*>(q_ + base);
+        [[maybe_unused]] const int slot_e = ((g0 + slot) < ntodo) ? slot : (int)(ntodo - g0 - 1);  // (kPre: as tile_regs)
+#pragma unroll
+        for (int k = 0; k < EPL / 2; ++k) {
+          const bool in = FULL || (k * LPG + j) < npairs;
+          const int p = in ? (k * LPG + j) : 0;
+          f64x2 a;
+          if constexpr (kPre) a = *reinterpret_cast<const f64x2*>(wl + (slot_e * npairs + p) * 16);
+          else if constexpr (kDma) a = *reinterpret_cast<const f64x2*>(wl + k * 1024 + lane * 16);
+          else if constexpr (LPG <= 2 || kPaddedCached) a = q2[p];
+          else a = __builtin_nontemporal_load(q2 + p);
+          qy += in ? a.x * out[2 * k] : 0.0;
+          qy += in ? a.y * out[2 * k + 1] : 0.0;
+          yy += in ? out[2 * k] * out[2 * k] : 0.0;
+          yy += in ? out[2 * k + 1] * out[2 * k + 1] : 0.0;
+        }
+      } else {
+#pragma unroll
+        for (int k = 0; k < EPL; ++k) {
+          const bool in = (k * LPG + j) < gs;
+          const double a = q_[base + (in ? k * LPG + j : 0)];
+          qy += in ? a * out[k] : 0.0;
+          yy += in ? out[k] * out[k] : 0.0;
+        }
+      }
+      if constexpr (LIT) {  // (a handed-on group: two more slots of its own)
+        qy = lanes_sum<LPG>(qy);
+        yy = lanes_sum<LPG>(yy);
+        if (valid && j == 0) {
+          spx_atomic_store_f64(&gv.dterm[gv.dplane + g], qy);
+          spx_atomic_store_f64(&gv.dterm[2 * gv.dplane + g], yy);
+        }
+      } else if (valid) {
+        qsum += qy;
+        ysum += yy;
+      }
+    }
   }
   if constexpr (VALUE) {
     if constexpr (!LIT) {  // (the host gives every wavefront one tile in these launches: tile = wavefront)
@@ -482,7 +615,13 @@ __global__ __launch_bounds__(256, (BINF && EPL >= 16) ? 2 : SPX_GROUP_WAVES) voi
         if (lane == 0) gv.dmask[wave] = m;
       }
     }
-    gval_finish(hsum, handed_on, gv);
+    if constexpr (STEP) {
+      double acc[3] = {hsum, qsum, ysum};
+      gval_finish(acc, handed_on, gv);
+    } else {
+      double acc[1] = {hsum};
+      gval_finish(acc, handed_on, gv);
+    }
   }
 }
 
@@ -628,7 +767,8 @@ __global__ __launch_bounds__(256) void k_group_list_val(double* y, const double*
     vv = lanes_sum<TEAM>(vv);
     if (lane == 0) spx_atomic_store_f64(&gv.dterm[g], lambda[g] * sqrt(vv));  // (its own slot: GroupVal)
   }
-  gval_finish(0.0, false, gv);
+  double none[1] = {0.0};
+  gval_finish(none, false, gv);
 }
 // y = c * q, elementwise (the composed routes of spx_proxval_group_* with q_scale != 1: the prox then runs at q := y)
 // CSR layouts: only over [offsets[0], offsets[ngroups]) -- the indices no group contains keep the caller's y for the operator.
@@ -837,14 +977,15 @@ struct GroupRegArgs {
   bool pairs;  // 16-byte loads: uniform groups of even size in 16-byte aligned vectors; otherwise 8-byte loads
 };
 // One k_group_reg launch.  PAIRS by the loads; FULL (main launches only) when the groups fill the tile; `gv` is passed on by VALUE.
-// dclear: the LIT launch's, NULL for a main launch.
-template <int LPG, int EPL, bool BINF, bool LIT, bool VALUE>
-static void launch_group_reg(const GroupRegArgs& a, dim3 grid, unsigned long long* dclear, const GroupVal& gv) {
+// (a GroupStep: the step form).  dclear: the LIT launch's, NULL for a main launch.
+template <int LPG, int EPL, bool BINF, bool LIT, bool VALUE, class GV>
+static void launch_group_reg(const GroupRegArgs& a, dim3 grid, unsigned long long* dclear, const GV& gv) {
   const GroupCall& c = a.c;
-  typename std::conditional<VALUE, GroupVal, GroupNoVal>::type v{};
+  constexpr bool STEP = VALUE && std::is_same<GV, GroupStep>::value;
+  typename std::conditional<VALUE, GV, GroupNoVal>::type v{};
   if constexpr (VALUE) v = gv;
   auto launch = [&](auto pairs, auto full) {
-    hipLaunchKernelGGL((k_group_reg<LPG, EPL, BINF, decltype(pairs)::value, LIT, decltype(full)::value, VALUE>), grid, dim3(256), 0,
+    hipLaunchKernelGGL((k_group_reg<LPG, EPL, BINF, decltype(pairs)::value, LIT, decltype(full)::value, VALUE, STEP>), grid, dim3(256), 0,
                        c.ctx->stream, c.y, c.q, c.xk, c.sj, c.ngroups, (int)c.gsize, c.lambda, c.sigma, c.delta, a.deferred,
                        c.offsets, c.ctx->status_dev, c.ctx->tune_binf_literal, a.dcount, dclear, v);
   };
@@ -906,8 +1047,16 @@ static int group_classify(const GroupCall& c, GroupRoute* route) {
 // Register tiles.  Ragged groups (CSR offsets + an upper bound on the sizes in group_size) use the same tiles through the 8-byte
 // loads; a group that exceeds the bound after all is handed to the general kernel.
 // VALUE (run_group_val below): the launches also form h at the result, see GroupVal.
-template <bool BINF, bool VALUE>
-static int group_route_reg(const GroupCall& c, double q_scale = 1.0, double* value = nullptr) {
+// STEP (run_group_step below, uniform groups only): ... and xkn and the two other sums, see GroupStep; `value` is then the host
+// double[3] or NULL (nothing read back, the call only enqueues).
+struct GroupStepOut {
+  double *xkn, *stats_dev;
+};
+template <bool BINF, bool VALUE, bool STEP = false>
+static int group_route_reg(const GroupCall& c, double q_scale = 1.0, double* value = nullptr, GroupStepOut so = {nullptr, nullptr}) {
+  static_assert(VALUE || !STEP, "the step form extends the value form");
+  using GV = typename std::conditional<STEP, GroupStep, GroupVal>::type;
+  constexpr int NS = STEP ? 3 : 1;  // sums per workgroup / handed-on group
   using Tiles = typename std::conditional<BINF, GroupTilesBinf, GroupTilesPlain>::type;
   spx_ctx* ctx = c.ctx;
   const int64_t ngroups = c.ngroups;
@@ -922,24 +1071,32 @@ static int group_route_reg(const GroupCall& c, double q_scale = 1.0, double* val
   long long* deferred = nullptr;
   unsigned long long *dcount = nullptr, *dclear = nullptr;
   // VALUE: one reservation -- [deferred list | GroupValWs | partials and flags of the main launch | tile masks | dterm]
-  GroupVal gv_main{}, gv_last{};
-  [[maybe_unused]] GroupValWs* vws = nullptr;
+  GV gv_main{}, gv_last{};
+  [[maybe_unused]] GroupValWs* vws = nullptr;  // (STEP: a GroupStepWs)
   if constexpr (VALUE) {
     const size_t list_bytes = (BINF || ragged) ? (((size_t)(ngroups + 1) * sizeof(long long) + 256 + 255) & ~(size_t)255) : 0;
     // (a wavefront per tile: the masks of the handed-on groups are indexed by wavefront)
     SPX_REQUIRE(blocks * 4 * gpw >= ngroups, "too many groups for the fused value form");
-    const size_t part_bytes = ((size_t)blocks * 2 * sizeof(double) + 255) & ~(size_t)255;  // partials | flags
+    const size_t head_bytes = STEP ? sizeof(GroupStepWs) : sizeof(GroupValWs);
+    const size_t part_bytes = ((size_t)blocks * (NS + 1) * sizeof(double) + 255) & ~(size_t)255;  // partials (NS planes) | flags
     const size_t mask_bytes = list_bytes ? (size_t)blocks * 4 * sizeof(unsigned long long) : 0;
-    rc = spx_ws_reserve(ctx, list_bytes + sizeof(GroupValWs) + part_bytes + mask_bytes + (list_bytes ? (size_t)ngroups * sizeof(double) : 0) + 256);
+    rc = spx_ws_reserve(ctx, list_bytes + head_bytes + part_bytes + mask_bytes + (list_bytes ? (size_t)ngroups * NS * sizeof(double) : 0) + 256);
     if (rc) return rc;
     rc = spx_sync_ready(ctx);
     if (rc) return rc;
     vws = reinterpret_cast<GroupValWs*>(static_cast<char*>(ctx->ws) + list_bytes);
-    double* part = reinterpret_cast<double*>(vws + 1);
+    double* part = reinterpret_cast<double*>(reinterpret_cast<char*>(vws) + head_bytes);
     const bool one = !(BINF || ragged);  // the main launch is the call's last one
     unsigned long long* dmask = one ? nullptr : reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(part) + part_bytes);
     double* dterm = one ? nullptr : reinterpret_cast<double*>(reinterpret_cast<char*>(part) + part_bytes + mask_bytes);
-    gv_main = GroupVal{q_scale, part, one ? nullptr : part + blocks, (int)blocks, false, one ? spx_sync_header(ctx) : nullptr, vws, ctx->value_target, dmask, dterm, lpg};
+    static_cast<GroupVal&>(gv_main) = GroupVal{q_scale, part, one ? nullptr : part + NS * blocks, (int)blocks, false, one ? spx_sync_header(ctx) : nullptr, vws,
+                                               STEP ? nullptr : ctx->value_target, dmask, dterm, lpg};
+    if constexpr (STEP) {  // (the context's value target does not apply)
+      gv_main.xkn = so.xkn;
+      gv_main.stats_dev = so.stats_dev;
+      gv_main.sws = reinterpret_cast<GroupStepWs*>(vws);
+      gv_main.dplane = ngroups;
+    }
     gv_last = gv_main;
     gv_last.behind = true;
     gv_last.hdr = spx_sync_header(ctx);
@@ -968,7 +1125,7 @@ static int group_route_reg(const GroupCall& c, double q_scale = 1.0, double* val
       rc = spx_zero_async(ctx, deferred, sizeof(long long)); if (rc) return rc;
     }
   }
-  const bool aligned = spx_aligned16(c.y) && spx_aligned16(c.q) && spx_aligned16(c.xk) && spx_aligned16(c.sj);
+  const bool aligned = spx_aligned16(c.y) && spx_aligned16(c.q) && spx_aligned16(c.xk) && spx_aligned16(c.sj) && spx_aligned16(so.xkn);
   const GroupRegArgs args{c, deferred, dcount, !ragged && (c.gsize & 1) == 0 && aligned};
   group_uncovered<BINF>(c);
   Tiles::select(c.gsize, [&](auto row) {
@@ -994,7 +1151,14 @@ static int group_route_reg(const GroupCall& c, double q_scale = 1.0, double* val
                          ctx->status_dev, ctx->tune_binf_literal, (const int*)nullptr, (int64_t)0);
   }
   SPX_LAUNCH_CHECK();
-  if constexpr (VALUE) return group_val_return(ctx, vws, value);
+  if constexpr (STEP) {
+    if (value == nullptr) return SPX_OK;  // device results only: the call returns after enqueueing
+    SPX_HIP(hipMemcpyAsync(value, reinterpret_cast<GroupStepWs*>(vws)->result, 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    SPX_HIP(hipStreamSynchronize(ctx->stream));
+    return SPX_OK;
+  } else if constexpr (VALUE) {
+    return group_val_return(ctx, vws, value);
+  }
   return SPX_OK;
 }
 
@@ -1148,6 +1312,120 @@ SPX_EXPORT int spx_proxval_group_l2_binf(spx_ctx* ctx, double* y, const double* 
                                          const double* lambda_vec, double sigma, double delta, double q_scale,
                                          double* value) {
   return run_group_val<true>({ctx, y, q, xk, sj, n, group_offsets, group_size, ngroups, lambda_vec, sigma, delta}, q_scale, value);
+}
+
+// ---------------------------------------------------------------------------------------------
+// prox! fused with the step statistics (include/spx.h, "group forms" of spx_proxstep_*).  Uniform groups on the register tiles:
+// everything comes out of the launches that store y (k_group_reg, STEP).  Every other layout is composed in this call: the
+// unchanged run_group_val -- y and h, h kept on the device in SpxSyncHeader::grp_step_h -- then ONE streaming launch for xkn and
+// the two sums, which also hands h on to the result slots.
+// ---------------------------------------------------------------------------------------------
+// xkn = (xk + sj) + y, <q, y>, <y, y> over [0, n): a grid-stride loop, VEC: 16-byte accesses (every vector 16-byte aligned; the
+// odd last element is taken by one lane).  The finish is gval_finish's on three planes; plane 0 carries nothing but *h, added
+// by workgroup 0 to zeros, so that the last workgroup stores the triple {h, <q, y>, <y, y>}.
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_group_step_tail(const double* q, const double* y, const double* xk, const double* sj,
+                                                          double* xkn, int64_t n, const double* h, GroupStep gv) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
+  double qy = 0.0, yy = 0.0;
+  if constexpr (VEC) {
+    const int64_t n2 = n >> 1;
+    for (int64_t i = t; i < n2; i += stride) {
+      const f64x2 a = __builtin_nontemporal_load(reinterpret_cast<const f64x2*>(q) + i);
+      const f64x2 b = __builtin_nontemporal_load(reinterpret_cast<const f64x2*>(y) + i);
+      if (xkn != nullptr) {
+        const f64x2 x = __builtin_nontemporal_load(reinterpret_cast<const f64x2*>(xk) + i);
+        const f64x2 s = __builtin_nontemporal_load(reinterpret_cast<const f64x2*>(sj) + i);
+        __builtin_nontemporal_store(f64x2{(x.x + s.x) + b.x, (x.y + s.y) + b.y}, reinterpret_cast<f64x2*>(xkn) + i);
+      }
+      qy += a.x * b.x;
+      qy += a.y * b.y;
+      yy += b.x * b.x;
+      yy += b.y * b.y;
+    }
+    if ((n & 1) && t == 0) {
+      const int64_t i = n - 1;
+      if (xkn != nullptr) xkn[i] = (xk[i] + sj[i]) + y[i];
+      qy += q[i] * y[i];
+      yy += y[i] * y[i];
+    }
+  } else {
+    for (int64_t i = t; i < n; i += stride) {
+      const double b = y[i];
+      if (xkn != nullptr) xkn[i] = (xk[i] + sj[i]) + b;
+      qy += q[i] * b;
+      yy += b * b;
+    }
+  }
+  double acc[3] = {t == 0 ? *h : 0.0, qy, yy};
+  gval_finish(acc, false, gv);
+}
+
+template <bool BINF>
+static int run_group_step(const GroupCall& c, double q_scale, double* xkn, double* stats, double* stats_dev) {
+  GroupRoute route;
+  int rc = group_classify<BINF>(c, &route);
+  if (rc) return rc;
+  spx_ctx* ctx = c.ctx;
+  SPX_REQUIRE(stats != nullptr || stats_dev != nullptr, "stats and stats_dev are both NULL");
+  SPX_REQUIRE(c.y == nullptr || c.y != c.q, "y aliases q (<q, y> of an overwritten q)");
+  if (xkn != nullptr) SPX_REQUIRE(xkn != c.y && xkn != c.q && xkn != c.xk && xkn != c.sj, "xkn is one of the other vectors");
+  // the host copy synchronises: refused under a capture before anything is enqueued
+  if (stats != nullptr) { rc = spx_require_not_capturing(ctx, "returning the step statistics to the host (pass stats = NULL)"); if (rc) return rc; }
+  if (stats) stats[0] = stats[1] = stats[2] = 0.0;
+  if (route == GroupRoute::None) {  // no group at all: three zeros; y as the plain operator leaves it (it does not read q)
+    rc = group_run<BINF>(c, route);
+    if (rc || stats_dev == nullptr) return rc;
+    SPX_ON_DEVICE(ctx);
+    return spx_zero_async(ctx, stats_dev, 3 * sizeof(double));  // (a kernel, not a memset node)
+  }
+  if (route == GroupRoute::Reg && c.offsets == nullptr) return group_route_reg<BINF, true, true>(c, q_scale, stats, {xkn, stats_dev});
+  // composed: [GroupStepWs | three planes of partials] of the tail launch, reserved before anything is enqueued
+  const bool vec = spx_aligned16(c.y) && spx_aligned16(c.q) && spx_aligned16(c.xk) && spx_aligned16(c.sj) && spx_aligned16(xkn);
+  const int64_t work = vec ? (c.n + 1) / 2 : c.n;
+  int64_t blocks = (work + 255) / 256;
+  if (blocks > (int64_t)ctx->num_cu * 8) blocks = (int64_t)ctx->num_cu * 8;
+  rc = spx_ws_reserve(ctx, sizeof(GroupStepWs) + (size_t)blocks * 3 * sizeof(double) + 256);
+  if (rc) return rc;
+  rc = spx_sync_ready(ctx);
+  if (rc) return rc;
+  SpxSyncHeader* hdr = spx_sync_header(ctx);
+  double* const caller_target = ctx->value_target;  // (does not apply to this call: h goes to the library's own word)
+  ctx->value_target = &hdr->grp_step_h;
+  double unused;
+  rc = run_group_val<BINF>(c, q_scale, &unused);
+  ctx->value_target = caller_target;
+  if (rc) return rc;
+  SPX_ON_DEVICE(ctx);
+  GroupStep gv{};
+  GroupStepWs* sws = reinterpret_cast<GroupStepWs*>(ctx->ws);
+  static_cast<GroupVal&>(gv) = GroupVal{1.0, reinterpret_cast<double*>(sws + 1), nullptr, (int)blocks, false, hdr, nullptr, nullptr, nullptr, nullptr, 64};
+  gv.xkn = xkn;
+  gv.stats_dev = stats_dev;
+  gv.sws = sws;
+  if (vec) hipLaunchKernelGGL(k_group_step_tail<true>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, c.q, (const double*)c.y, c.xk, c.sj, xkn, c.n, (const double*)&hdr->grp_step_h, gv);
+  else hipLaunchKernelGGL(k_group_step_tail<false>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, c.q, (const double*)c.y, c.xk, c.sj, xkn, c.n, (const double*)&hdr->grp_step_h, gv);
+  SPX_LAUNCH_CHECK();
+  if (stats == nullptr) return SPX_OK;  // device results only: the call returns after enqueueing
+  SPX_HIP(hipMemcpyAsync(stats, sws->result, 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  SPX_HIP(hipStreamSynchronize(ctx->stream));
+  return SPX_OK;
+}
+
+SPX_EXPORT int spx_proxstep_group_l2(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
+                                     const int64_t* group_offsets, int64_t group_size, int64_t ngroups,
+                                     const double* lambda_vec, double sigma, double q_scale, double* xkn, double* stats,
+                                     double* stats_dev) {
+  return run_group_step<false>({ctx, y, q, xk, sj, n, group_offsets, group_size, ngroups, lambda_vec, sigma, 0.0}, q_scale, xkn, stats,
+                               stats_dev);
+}
+
+SPX_EXPORT int spx_proxstep_group_l2_binf(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj,
+                                          int64_t n, const int64_t* group_offsets, int64_t group_size, int64_t ngroups,
+                                          const double* lambda_vec, double sigma, double delta, double q_scale, double* xkn,
+                                          double* stats, double* stats_dev) {
+  return run_group_step<true>({ctx, y, q, xk, sj, n, group_offsets, group_size, ngroups, lambda_vec, sigma, delta}, q_scale, xkn, stats,
+                              stats_dev);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -839,7 +839,8 @@ def prox_step_bang(y, ψ, q, σ, q_scale=1.0, xkn=None, out=None):
     elements: out[0:3] = (h, qy, yy), nothing is read back and the stream is not synchronised; returns (y, out) -- this form
     can be captured into a graph once the same call has run before.  `device_values` does not apply.  y must not be q.
     Supported: ShiftedNormL1 / NormL0 / RootNormLhalf and their Box forms on device Float64 vectors; host ψ, Float32, the
-    group, top-r and ShiftedNormL1B2 operators raise TypeError."""
+    group, top-r and ShiftedNormL1B2 operators raise TypeError.  The group operators have a call of their own:
+    group_prox_step_bang."""
     if not isinstance(ψ, (_Unboxed, _Boxed)) or ψ.host or ψ.f32:
         raise TypeError("prox_step is available for ShiftedNormL1 / ShiftedNormL0 / ShiftedRootNormLhalf and their Box forms "
                         "on device Float64 vectors (no host ψ, Float32, group, top-r or ShiftedNormL1B2 form)")
@@ -874,6 +875,58 @@ def prox_step_bang(y, ψ, q, σ, q_scale=1.0, xkn=None, out=None):
 def prox_step(ψ, q, σ, q_scale=1.0, xkn=None, out=None):
     """prox_step_bang(ψ.sol, ψ, q, σ, ...): (ψ.sol, h, qy, yy), or (ψ.sol, out) with a device `out`; see prox_step_bang"""
     return prox_step_bang(ψ.sol, ψ, q, σ, q_scale, xkn, out)
+
+
+def group_prox_step_bang(y, ψ, q, σ, q_scale=1.0, xkn=None, out=None):
+    """prox_step_bang for the group operators, ShiftedGroupNormL2 and ShiftedGroupNormL2Binf (spx_proxstep_group_l2[_binf]):
+    prox!(y, ψ, q_scale .* q, σ) and the step statistics of a trust-region iteration in one library call,
+
+        h  = Σ over the groups of λ_g · ‖((xk + sj) + y)[g]‖   -- the value prox_value returns (Binf form: h part only)
+        qy = Σ over ALL i of q[i] · y[i]   -- with the UNSCALED q as passed, not q_scale · q
+        yy = Σ over ALL i of y[i]²
+        xkn[i] = (xk[i] + sj[i]) + y[i] for every i, inside a group or not (a device vector like ψ.xk that is none of y, q,
+                 ψ.xk, ψ.sj; None: not stored)
+
+    Uniform groups of at most 512 elements: everything comes out of the pass that stores y.  Every other contiguous layout
+    (larger groups, one group over the vector, ragged groups): prox_value's launches followed by one streaming launch inside
+    the same call -- the same results, not the same speed.  Arguments, `out` and the return shapes are prox_step_bang's:
+    (y, h, qy, yy) as Python floats, or (y, out) with a float64 device tensor `out` of at least 3 elements (nothing read back,
+    capturable into a graph once the same call has run before).  `device_values` does not apply.  y must not be q.
+    Device Float64 vectors and contiguous groups only: host ψ, Float32, index-set (gather) layouts and every non-group ψ raise
+    TypeError."""
+    if not isinstance(ψ, (ShiftedGroupNormL2, ShiftedGroupNormL2Binf)):
+        raise TypeError("group_prox_step is available for ShiftedGroupNormL2 and ShiftedGroupNormL2Binf (the separable "
+                        "operators: prox_step)")
+    g = ψ._layout
+    if _is_host(ψ.xk) or ψ.xk.dtype != torch.float64 or g.index is not None:
+        raise TypeError("group_prox_step needs device Float64 vectors and contiguous groups")
+    n = _n(ψ.xk)
+    _vec(q, "q", n, like=ψ.xk)
+    _vec(y, "y", n, like=ψ.xk)
+    if xkn is not None:
+        _vec(xkn, "xkn", n, like=ψ.xk)
+    if y is q:
+        raise TypeError("group_prox_step: y must not be q (qy is taken with the q that was passed)")
+    if out is not None and not (type(out) is _Tensor and out.is_cuda and out.dtype == torch.float64 and out.dim() == 1
+                                and out.numel() >= 3 and out.stride(0) == 1 and out.device == ψ.xk.device):
+        raise TypeError("out must be a contiguous float64 device tensor with at least 3 elements on ψ.xk's device")
+    ψ._refresh()
+    L, ctx = _lib.load(), _ctx(_dev(y))
+    host = (ctypes.c_double * 3)() if out is None else None
+    head = (ctx, _ptr(y), _ptr(q), _ptr(ψ.xk), _ptr(ψ.sj), n, _ptr(g.offsets), g.group_size, g.ngroups, _ptr(g.lam), float(σ))
+    tail = (float(q_scale), _ptr(xkn), host, ctypes.c_void_p(out.data_ptr()) if out is not None else _NULL)
+    if isinstance(ψ, ShiftedGroupNormL2Binf):
+        _lib.check(L.spx_proxstep_group_l2_binf(*head, ψ.Δ, *tail))
+    else:
+        _lib.check(L.spx_proxstep_group_l2(*head, *tail))
+    if out is not None:
+        return y, out
+    return y, host[0], host[1], host[2]
+
+
+def group_prox_step(ψ, q, σ, q_scale=1.0, xkn=None, out=None):
+    """group_prox_step_bang(ψ.sol, ψ, q, σ, ...): (ψ.sol, h, qy, yy), or (ψ.sol, out) with a device `out`"""
+    return group_prox_step_bang(ψ.sol, ψ, q, σ, q_scale, xkn, out)
 
 
 def iprox_bang(y, ψ, g, d, check=True):
