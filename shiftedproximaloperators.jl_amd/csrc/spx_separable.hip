@@ -93,12 +93,12 @@ struct ProxL0Box {  // src/shiftedNormL0Box.jl:96-128
   }
 };
 // The Float64 operators of the kernels below; kLdsKiB: KiB per wave and input vector in the LDS-staged skeleton (0: the
-// register-staged one), kObj: WithValue adds the value of h
-struct OpL1 : ProxL1<double> { static constexpr int kLdsKiB = 6; static constexpr bool kObj = false; };
-struct OpL1Aliased : ProxL1Aliased<double> { static constexpr int kLdsKiB = 6; static constexpr bool kObj = false; };
-struct OpL0 : ProxL0<double> { static constexpr int kLdsKiB = 6; static constexpr bool kObj = false; };
-struct OpL1Box : ProxL1Box<double> { static constexpr int kLdsKiB = 6; static constexpr bool kObj = false; };
-struct OpL0Box : ProxL0Box<double> { static constexpr int kLdsKiB = 6; static constexpr bool kObj = false; };
+// register-staged one).  WithValue / WithStep below wrap them with the sums a call adds (kSumsOf)
+struct OpL1 : ProxL1<double> { static constexpr int kLdsKiB = 6; };
+struct OpL1Aliased : ProxL1Aliased<double> { static constexpr int kLdsKiB = 6; };
+struct OpL0 : ProxL0<double> { static constexpr int kLdsKiB = 6; };
+struct OpL1Box : ProxL1Box<double> { static constexpr int kLdsKiB = 6; };
+struct OpL0Box : ProxL0Box<double> { static constexpr int kLdsKiB = 6; };
 
 // ---------------------------------------------------------------------------------------------
 // RootNormLhalf closed form.  Reference (src/shiftedRootNormLhalf.jl:48,57; shiftedRootNormLhalfBox.jl:92,106):
@@ -170,7 +170,7 @@ struct OpLhalf {  // src/shiftedRootNormLhalf.jl:47-60
   static constexpr bool kBox = false;
   static constexpr int kLdsKiB = 6;  // KiB per wave and input vector in the LDS-staged skeleton
   static constexpr int kNIn = 3;
-  static constexpr bool kObj = false;     // input vectors besides bounds: q, xk, sj
+      // input vectors besides bounds: q, xk, sj
   __device__ __forceinline__ double operator()(double q, double x, double s, double, double, bool) const {
     double xs = x + s;
     double sol = q + xs;  // :50
@@ -189,7 +189,7 @@ struct OpLhalfBox {  // src/shiftedRootNormLhalfBox.jl:92-117
   static constexpr bool kBox = true;
   static constexpr int kLdsKiB = 0;  // 0: register-staged skeleton (VALU-heavy: needs the occupancy; 5.97 vs 5.68 TB/s)
   static constexpr int kNIn = 3;
-  static constexpr bool kObj = false;
+ 
   // RNorm(tt) = (tt - q)^2 / 2 / sigma + lambda sqrt|tt + xs|   (:95); used only to pick the argmin
   __device__ __forceinline__ double rnorm(double tt, double q, double xs) const {
     double d = tt - q;
@@ -390,11 +390,11 @@ struct IproxL0Box {  // src/shiftedNormL0Box.jl:137-231
     return sel ? yi : iprox_zero(d, g, left, right);  // :227
   }
 };
-struct OpIproxL1 : IproxL1<double> { static constexpr int kLdsKiB = 4; static constexpr bool kObj = false; };
-struct OpIproxL0 : IproxL0<double> { static constexpr int kLdsKiB = 4; static constexpr bool kObj = false; };
+struct OpIproxL1 : IproxL1<double> { static constexpr int kLdsKiB = 4; };
+struct OpIproxL0 : IproxL0<double> { static constexpr int kLdsKiB = 4; };
 // register-staged: five fp64 divisions per element want the occupancy (6.10 vs 5.70 TB/s)
-struct OpIproxL1Box : IproxL1Box<double> { static constexpr int kLdsKiB = 0; static constexpr bool kObj = false; };
-struct OpIproxL0Box : IproxL0Box<double> { static constexpr int kLdsKiB = 4; static constexpr bool kObj = false; };
+struct OpIproxL1Box : IproxL1Box<double> { static constexpr int kLdsKiB = 0; };
+struct OpIproxL0Box : IproxL0Box<double> { static constexpr int kLdsKiB = 4; };
 
 // ---------------------------------------------------------------------------------------------
 // prox! fused with the value of h at the result ("fused with prox where possible"): the kernels
@@ -407,210 +407,171 @@ struct HTermL0 : TermL0 {};
 struct HTermLhalf : TermLhalf {};
 template <class Base, class Term>
 struct WithValue : Base {
-  static constexpr bool kObj = true;
-  double* partials;  // one slot per wavefront (LDS skeleton) / workgroup (register skeleton, scalar kernel)
+  static constexpr int kSums = 1;
+  double* partials;  // one slot per workgroup
   double qscale;     // the prox is taken at qscale * q (R2: q = -nu * grad f, formed on the fly; 1.0 = q itself)
-  // Round 4 (value_publish below): when the call is ONE launch of at most kValueFuseMax workgroups, the workgroup that
-  // finishes last adds the partials itself and the k_value_reduce launch is not queued (fin_hdr != NULL)
+  // (value_publish below) when the call is ONE launch of at most kValueFuseMax workgroups, the workgroup that finishes last
+  // adds the partials itself and the k_value_reduce launch is not queued (fin_hdr != NULL)
   SpxSyncHeader* fin_hdr = nullptr;
-  double* fin_result = nullptr;  // the library's result slot (read back by the host form)
-  double* fin_target = nullptr;  // spx_ctx::value_target (may be NULL)
-  double fin_scale = 1.0;
+  double* fin_result = nullptr;  // the library's result slots (read back by the host forms)
+  double* fin_target = nullptr;  // the caller's device slots: spx_ctx::value_target / stats_dev (may be NULL)
+  double fin_scale = 1.0;        // both receive fin_scale * (sum of the h terms)
   __device__ __forceinline__ double operator()(double q, double x, double s, double l, double u, bool sel) const {
     return Base::operator()(qscale * q, x, s, l, u, sel);
   }
-  __device__ __forceinline__ double hterm(double x, double s, double y, bool sel) const {
+  __device__ __forceinline__ double hterm(double x, double s, double y, bool sel, bool = false) const {
     return sel ? Term{}((x + s) + y) : 0.0;
+  }
+  __device__ __forceinline__ double hterm(f64x2 x, f64x2 s, f64x2 y, bool s0, bool s1) const {  // a 16-byte pair
+    return hterm(x.x, s.x, y.x, s0) + hterm(x.y, s.y, y.y, s1);
   }
 };
 // prox! fused with the step statistics of a solver iteration (spx_proxstep_*): besides the h terms the lane that computes
 // y[i] adds q[i] * y[i] (q as passed, not qscale * q) and y[i]^2 over ALL i, and stores (xk[i] + sj[i]) + y[i] -- the point
 // at which h is evaluated -- to xkn when that is not NULL.  Three partial sums per slot, in three planes `plane` doubles
-// apart (partials[slot], partials[plane + slot], partials[2 plane + slot]), each added in the order the single sum is.
+// apart (partials[slot], partials[plane + slot], partials[2 plane + slot]).
 template <class Base, class Term>
 struct WithStep : WithValue<Base, Term> {
-  static constexpr bool kStep = true;
+  static constexpr int kSums = 3;
   double* xkn = nullptr;  // NULL: no store
   int64_t plane = 0;      // doubles between the planes of `partials`
 };
+// kSumsOf<Op>: the sums a call adds besides y -- 0 (plain prox! / iprox!), 1 (WithValue: h), 3 (WithStep: h, <q, y>, <y, y>).
+// Everything below is written once over that count: plane p of a list of partials is added with the same statements, hence
+// in the same order and to the same bits, whether it is the only plane or one of three.
 template <class Op, class = void>
-struct StepMode { static constexpr bool value = false; };
+struct SumsOf { static constexpr int value = 0; };
 template <class Op>
-struct StepMode<Op, decltype((void)Op::kStep)> { static constexpr bool value = Op::kStep; };
+struct SumsOf<Op, decltype((void)Op::kSums)> { static constexpr int value = Op::kSums; };
 template <class Op>
-constexpr bool kStepOf = StepMode<Op>::value;
+constexpr int kSumsOf = SumsOf<Op>::value;
+// A lane's (then a workgroup's) sums.  Handed to the functions below and returned BY VALUE: an accumulator that a kernel
+// passes by reference, or indexes by a loop variable, stays in memory until inlining and unrolling are done, and the element
+// loops then compile to other code than with the statements written out at their sites (k_sep_vec<WithStep<OpL1, ...>>: 90
+// VGPRs and five waves per SIMD instead of 80 and six; by value every kernel keeps its registers: profiles/sep_finish_kres.txt).
+template <int NS>
+struct SepSums { double v[NS]; };
+template <class Op>
+using SumsFor = SepSums<(kSumsOf<Op> > 0 ? kSumsOf<Op> : 1)>;  // (no array of length 0)
+template <class Op>
+__device__ __forceinline__ int64_t plane_of(const Op& op) {
+  if constexpr (kSumsOf<Op> > 1) return op.plane;
+  else return 0;
+}
 
-__device__ __forceinline__ double block_sum4(double v, double* lds4) {  // 256-lane workgroup
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) lds4[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (lds4[0] + lds4[1]) + (lds4[2] + lds4[3]);
-}
-// partials[0..count), count <= kValueFuseMax, added by the first 256 lanes of a workgroup in a fixed order (eight loads in
-// flight per lane, a fixed tree, wavefront butterflies, the four wavefronts in order): the order of BOTH the one-launch form
-// (ATOMIC: the slots were written by other workgroups of the same launch) and k_value_reduce on short lists, so that the two
-// forms of a call give the same bits.  Every lane of the workgroup must call it.
-constexpr int kValueFuseMax = 2048;
-template <bool ATOMIC>
-__device__ __forceinline__ double value_reduce_small(const double* partials, int count) {
-  __shared__ double vr_lds4[4];
+// a.v[p] summed over the first 256 lanes of a workgroup, for NS planes across one pair of barriers: wavefront butterflies,
+// then the four wavefronts in order.  Every lane of the workgroup must call it; the result is valid in all of them.
+template <int NS>
+__device__ __forceinline__ SepSums<NS> block_sum4(SepSums<NS> a) {
+  __shared__ double bs_lds[NS][4];
   const int t = threadIdx.x;
-  double v8[8];
 #pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const int i = t + k * 256;
-    const bool in = t < 256 && i < count;
-    if constexpr (ATOMIC) v8[k] = in ? spx_atomic_load_f64(partials + i) : 0.0;
-    else v8[k] = in ? partials[i] : 0.0;
+  for (int p = 0; p < NS; ++p) a.v[p] = wave_sum(a.v[p]);
+  __syncthreads();
+  if ((t & 63) == 0 && t < 256) {
+#pragma unroll
+    for (int p = 0; p < NS; ++p) bs_lds[p][t >> 6] = a.v[p];
   }
-  double acc = ((v8[0] + v8[1]) + (v8[2] + v8[3])) + ((v8[4] + v8[5]) + (v8[6] + v8[7]));
-  acc = wave_sum(acc);
   __syncthreads();
-  if ((t & 63) == 0 && t < 256) vr_lds4[t >> 6] = acc;
-  __syncthreads();
-  return (vr_lds4[0] + vr_lds4[1]) + (vr_lds4[2] + vr_lds4[3]);
+#pragma unroll
+  for (int p = 0; p < NS; ++p) a.v[p] = (bs_lds[p][0] + bs_lds[p][1]) + (bs_lds[p][2] + bs_lds[p][3]);
+  return a;
 }
-// The partial sum `t` of this workgroup (valid in thread 0) goes to its slot; in the one-launch form the workgroup that takes
-// the last ticket (spx_fin_ticket) then adds all of them and stores the value.  Every lane of the workgroup must call it.
-template <class Op>
-__device__ __forceinline__ void value_publish(const Op& op, int64_t slot, double t) {
-  if (op.fin_hdr == nullptr) {
-    if (threadIdx.x == 0) op.partials[slot] = t;
-    return;
+// The same sum for k_sep_lds, valid in thread 0 only, across ONE barrier and without LDS of its own: the wave's staging area
+// `wl` (of `wave_bytes`, the first of them at `lds`) has been consumed, its first 8 NS bytes carry the wave's sums to thread 0.
+template <int NS>
+__device__ __forceinline__ SepSums<NS> block_sum4_staged(SepSums<NS> a, char* wl, const char* lds, int wave_bytes) {
+#pragma unroll
+  for (int p = 0; p < NS; ++p) a.v[p] = wave_sum(a.v[p]);
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int p = 0; p < NS; ++p) reinterpret_cast<double*>(wl)[p] = a.v[p];
   }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const double* w0 = reinterpret_cast<const double*>(lds);
+    const int stride = wave_bytes / 8;
+#pragma unroll
+    for (int p = 0; p < NS; ++p) a.v[p] = (w0[p] + w0[stride + p]) + (w0[2 * stride + p] + w0[3 * stride + p]);
+  }
+  return a;
+}
+// .v[p] = the sum of partials[p * plane + (0..count)), count <= kValueFuseMax, added by the first 256 lanes of a workgroup in
+// a fixed order (all 8 NS loads of a lane in flight before the first add -- one memory round trip, whatever NS is -- a fixed
+// tree, then block_sum4): the order of BOTH the one-launch form (ATOMIC: the slots were written by other workgroups of the
+// same launch) and k_value_reduce on short lists, so that the two forms of a call give the same bits.  Every lane of the
+// workgroup must call it.
+constexpr int kValueFuseMax = 2048;
+template <bool ATOMIC, int NS>
+__device__ __forceinline__ SepSums<NS> value_reduce_small(const double* partials, int64_t plane, int count) {
+  const int t = threadIdx.x;
+  double v8[NS][8];
+#pragma unroll
+  for (int p = 0; p < NS; ++p) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int i = t + k * 256;
+      const bool in = t < 256 && i < count;
+      if constexpr (ATOMIC) v8[p][k] = in ? spx_atomic_load_f64(partials + p * plane + i) : 0.0;
+      else v8[p][k] = in ? partials[p * plane + i] : 0.0;
+    }
+  }
+  SepSums<NS> a;
+#pragma unroll
+  for (int p = 0; p < NS; ++p)
+    a.v[p] = ((v8[p][0] + v8[p][1]) + (v8[p][2] + v8[p][3])) + ((v8[p][4] + v8[p][5]) + (v8[p][6] + v8[p][7]));
+  return block_sum4(a);
+}
+// The partial sums t.v[0..NS) of this workgroup (valid in thread 0) go to its slot of the NS planes.  value_store: a later
+// launch adds them -- all there is to do in a launch that can never be the only one of its call.  value_publish: in the
+// one-launch form ONE ticket per workgroup (spx_fin_ticket) publishes all NS of them, and the workgroup that takes the last
+// one adds the planes and stores {fin_scale * h, <q, y>, <y, y>} (NS = 1: the first of them) to the library's result slots and
+// to fin_target if set.  Every lane of the workgroup must call it.
+template <class Op, int NS>
+__device__ __forceinline__ void value_store(const Op& op, int64_t slot, SepSums<NS> t) {
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int p = 0; p < NS; ++p) op.partials[p * plane_of(op) + slot] = t.v[p];
+  }
+}
+template <class Op, int NS>
+__device__ __forceinline__ void value_publish(const Op& op, int64_t slot, SepSums<NS> t) {
+  if (op.fin_hdr == nullptr) return value_store(op, slot, t);
+  const int64_t plane = plane_of(op);
   __shared__ int vp_last;
   if (threadIdx.x == 0) {
-    spx_atomic_store_f64(op.partials + slot, t);
+#pragma unroll
+    for (int p = 0; p < NS; ++p) spx_atomic_store_f64(op.partials + p * plane + slot, t.v[p]);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     vp_last = spx_fin_ticket(op.fin_hdr) ? 1 : 0;
   }
   __syncthreads();
   if (!vp_last) return;
-  const double sum = value_reduce_small<true>(op.partials, (int)gridDim.x);
+  SepSums<NS> sum = value_reduce_small<true, NS>(op.partials, plane, (int)gridDim.x);
   if (threadIdx.x == 0) {
-    *op.fin_result = sum;
-    if (op.fin_target) *op.fin_target = op.fin_scale * sum;
-  }
-}
-
-// value_reduce_small<true> on the three planes of a WithStep call at once: the 24 loads of a lane are in flight together and
-// the wavefronts' sums cross one pair of barriers -- one memory round trip at the end of the launch instead of three -- while
-// every plane is added with the statements, hence in the order and to the bits, of value_reduce_small.
-__device__ __forceinline__ void value_reduce_small3(const double* partials, int64_t plane, int count, double (&out)[3]) {
-  __shared__ double vr3_lds[3][4];
-  const int t = threadIdx.x;
-  double v8[3][8];
+    sum.v[0] = op.fin_scale * sum.v[0];
 #pragma unroll
-  for (int p = 0; p < 3; ++p) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const int i = t + k * 256;
-      const bool in = t < 256 && i < count;
-      v8[p][k] = in ? spx_atomic_load_f64(partials + p * plane + i) : 0.0;
-    }
-  }
-  double acc[3];
-#pragma unroll
-  for (int p = 0; p < 3; ++p) {
-    acc[p] = ((v8[p][0] + v8[p][1]) + (v8[p][2] + v8[p][3])) + ((v8[p][4] + v8[p][5]) + (v8[p][6] + v8[p][7]));
-    acc[p] = wave_sum(acc[p]);
-  }
-  __syncthreads();
-  if ((t & 63) == 0 && t < 256) {
-#pragma unroll
-    for (int p = 0; p < 3; ++p) vr3_lds[p][t >> 6] = acc[p];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int p = 0; p < 3; ++p) out[p] = (vr3_lds[p][0] + vr3_lds[p][1]) + (vr3_lds[p][2] + vr3_lds[p][3]);
-}
-// The three-sum form (WithStep): the workgroup's triple (valid in thread 0) goes to its slot of the three planes; ONE ticket
-// per workgroup publishes all three, and the workgroup that takes the last one adds the three planes, each in the order of
-// the single sum (value_reduce_small3).  Stores {fin_scale * h, <q, y>, <y, y>} to the library's result slots and to fin_target (stats_dev) if set.
-template <class Op>
-__device__ __forceinline__ void value_publish3(const Op& op, int64_t slot, double t0, double t1, double t2) {
-  if (op.fin_hdr == nullptr) {
-    if (threadIdx.x == 0) {
-      op.partials[slot] = t0;
-      op.partials[op.plane + slot] = t1;
-      op.partials[2 * op.plane + slot] = t2;
-    }
-    return;
-  }
-  __shared__ int vp3_last;
-  if (threadIdx.x == 0) {
-    spx_atomic_store_f64(op.partials + slot, t0);
-    spx_atomic_store_f64(op.partials + op.plane + slot, t1);
-    spx_atomic_store_f64(op.partials + 2 * op.plane + slot, t2);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    vp3_last = spx_fin_ticket(op.fin_hdr) ? 1 : 0;
-  }
-  __syncthreads();
-  if (!vp3_last) return;
-  double s3[3];
-  value_reduce_small3(op.partials, op.plane, (int)gridDim.x, s3);
-  if (threadIdx.x == 0) {
-    const double h = op.fin_scale * s3[0];
-    op.fin_result[0] = h;
-    op.fin_result[1] = s3[1];
-    op.fin_result[2] = s3[2];
-    if (op.fin_target) {
-      op.fin_target[0] = h;
-      op.fin_target[1] = s3[1];
-      op.fin_target[2] = s3[2];
+    for (int p = 0; p < NS; ++p) {
+      op.fin_result[p] = sum.v[p];
+      if (op.fin_target) op.fin_target[p] = sum.v[p];
     }
   }
 }
 
-// partials[0..count) -> *out, fixed order: reproducible run to run
-// target != NULL: also *target = scale * sum (the caller's device double, spx_ctx_set_value_target)
-__global__ __launch_bounds__(1024) void k_value_reduce(const double* partials, int64_t count, double* out, double scale,
-                                                        double* target) {
+// Workgroup b adds plane b of the partials, partials[b * plane + (0..count)), in a fixed order (reproducible run to run) and
+// stores out[b], and target[b] when target != NULL (the caller's device slots): {scale * h, <q, y>, <y, y>}.
+// Grid: NS workgroups.
+template <int NS>
+__global__ __launch_bounds__(1024) void k_value_reduce(const double* partials, int64_t plane, int64_t count, double* out,
+                                                        double scale, double* target) {
   __shared__ double lds[16];
-  if (count <= kValueFuseMax) {  // (the order of the one-launch form)
-    const double t = value_reduce_small<false>(partials, (int)count);
-    if (threadIdx.x == 0) {
-      *out = t;
-      if (target) *target = scale * t;
-    }
-    return;
-  }
-  // eight independent loads in flight per lane, added in a fixed order (reproducible run to run)
-  double a8[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  for (int64_t i0 = threadIdx.x; i0 < count; i0 += 8 * 1024) {
-    double v8[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const int64_t i = i0 + (int64_t)k * 1024;
-      v8[k] = (i < count) ? partials[i < count ? i : 0] : 0.0;
-    }
-#pragma unroll
-    for (int k = 0; k < 8; ++k) a8[k] += v8[k];
-  }
-  double acc = ((a8[0] + a8[1]) + (a8[2] + a8[3])) + ((a8[4] + a8[5]) + (a8[6] + a8[7]));
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t = 0.0;
-    for (int w = 0; w < 16; ++w) t += lds[w];
-    *out = t;
-    if (target) *target = scale * t;
-  }
-}
-// The three-sum form: workgroup b adds plane b of the partials -- the statements of k_value_reduce above, in its order (that
-// kernel is left as it is: its code object is part of every spx_proxval_* call) -- and stores out[b] (and target[b] when
-// target != NULL): {scale * h, <q, y>, <y, y>}.  Grid: 3 workgroups.
-__global__ __launch_bounds__(1024) void k_value_reduce3(const double* partials_, int64_t plane, int64_t count, double* out,
-                                                         double scale, double* target) {
-  __shared__ double lds[16];
-  const int b = blockIdx.x;
-  const double* partials = partials_ + (int64_t)b * plane;
+  const int b = (NS == 1) ? 0 : (int)blockIdx.x;
+  partials += (int64_t)b * plane;
   double t = 0.0;
   if (count <= kValueFuseMax) {  // (the order of the one-launch form)
-    t = value_reduce_small<false>(partials, (int)count);
+    t = value_reduce_small<false, 1>(partials, 0, (int)count).v[0];
   } else {
+    // eight independent loads in flight per lane
     double a8[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     for (int64_t i0 = threadIdx.x; i0 < count; i0 += 8 * 1024) {
       double v8[8];
@@ -652,10 +613,36 @@ __device__ __forceinline__ f64x2 ld2(const f64x2* p) {
   if constexpr (NT) return __builtin_nontemporal_load(p);
   else return *p;
 }
-template <bool NT>
-__device__ __forceinline__ void st2(f64x2* p, f64x2 v) {
+template <bool NT, class V>
+__device__ __forceinline__ void st2(V* p, V v) {
   if constexpr (NT) __builtin_nontemporal_store(v, p);
   else *p = v;
+}
+// (xk + sj) + y, the point at which h is evaluated: element by element, the expression of hterm, whose value the compiler reuses
+__device__ __forceinline__ double at_point(double x, double s, double y) { return (x + s) + y; }
+__device__ __forceinline__ f64x2 at_point(f64x2 x, f64x2 s, f64x2 y) { return f64x2{(x.x + s.x) + y.x, (x.y + s.y) + y.y}; }
+__device__ __forceinline__ double sum_prod(double a, double b) { return a * b; }
+__device__ __forceinline__ double sum_prod(f64x2 a, f64x2 b) { return a.x * b.x + a.y * b.y; }
+// The sums and the xkn store of one element site, written once for the three kernels: V = f64x2 is the 16-byte pair `i` of
+// the vector skeletons (s0, s1: its selection bits), V = double element `i` of the scalar kernel (s0).  q, x, s: the loaded
+// q (as passed, unscaled), xk, sj; r: the result(s).  NT: the store to xn (NULL: none) is non-temporal.  Returns acc with the
+// site's terms added (by value: see SepSums).
+template <bool NT, class Op, class V>
+__device__ __forceinline__ SumsFor<Op> sep_accumulate(const Op& op, SumsFor<Op> acc, V q, V x, V s, V r, bool s0, bool s1,
+                                                      V* xn, int64_t i) {
+  if constexpr (kSumsOf<Op> >= 1) acc.v[0] += op.hterm(x, s, r, s0, s1);
+  if constexpr (kSumsOf<Op> == 3) {
+    acc.v[1] += sum_prod(q, r);
+    acc.v[2] += sum_prod(r, r);
+    if (xn) st2<NT>(xn + i, at_point(x, s, r));
+  }
+  return acc;
+}
+// (WithStep) where xkn goes, as pairs or elements; NULL: no store
+template <class V, class Op>
+__device__ __forceinline__ V* xkn_of(const Op& op) {
+  if constexpr (kSumsOf<Op> == 3) return reinterpret_cast<V*>(op.xkn);
+  else return nullptr;
 }
 
 // n2 = number of 16-byte pairs.  VECB: l/u are vectors.  MASK: sel mask present.
@@ -673,10 +660,8 @@ __global__ __launch_bounds__(256) void k_sep_vec(double* y_, const double* q_, c
   const f64x2* uv = reinterpret_cast<const f64x2*>(u_);
   const uint16_t* mk = reinterpret_cast<const uint16_t*>(mask_);
   const int64_t ntiles = (n2 + TILE - 1) / TILE;
-  double hacc = 0.0;
-  double qacc = 0.0, yacc = 0.0;  // (WithStep) <q, y> and <y, y>
-  f64x2* xn = nullptr;
-  if constexpr (kStepOf<Op>) xn = reinterpret_cast<f64x2*>(op.xkn);
+  SumsFor<Op> acc = {};
+  f64x2* const xn = xkn_of<f64x2>(op);
   for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const int64_t base = tile * TILE + threadIdx.x;
     f64x2 vq[UNROLL], vx[UNROLL], vs[UNROLL], vl[UNROLL], vu[UNROLL], vd[UNROLL];
@@ -705,12 +690,7 @@ __global__ __launch_bounds__(256) void k_sep_vec(double* y_, const double* q_, c
         f64x2 r;
         r.x = apply_op(op, vq[k].x, vd[k].x, vx[k].x, vs[k].x, l0, u0, s0);
         r.y = apply_op(op, vq[k].y, vd[k].y, vx[k].y, vs[k].y, l1, u1, s1);
-        if constexpr (Op::kObj) hacc += op.hterm(vx[k].x, vs[k].x, r.x, s0) + op.hterm(vx[k].y, vs[k].y, r.y, s1);
-        if constexpr (kStepOf<Op>) {
-          qacc += vq[k].x * r.x + vq[k].y * r.y;
-          yacc += r.x * r.x + r.y * r.y;
-          if (xn) st2<NT>(xn + i, f64x2{(vx[k].x + vs[k].x) + r.x, (vx[k].y + vs[k].y) + r.y});
-        }
+        acc = sep_accumulate<NT>(op, acc, vq[k], vx[k], vs[k], r, s0, s1, xn, i);
         st2<NT>(y + i, r);
       }
     } else {  // last, partial tile
@@ -731,28 +711,13 @@ __global__ __launch_bounds__(256) void k_sep_vec(double* y_, const double* q_, c
           f64x2 r;
           r.x = apply_op(op, a.x, dd.x, b.x, c.x, l0, u0, s0);
           r.y = apply_op(op, a.y, dd.y, b.y, c.y, l1, u1, s1);
-          if constexpr (Op::kObj) hacc += op.hterm(b.x, c.x, r.x, s0) + op.hterm(b.y, c.y, r.y, s1);
-          if constexpr (kStepOf<Op>) {
-            qacc += a.x * r.x + a.y * r.y;
-            yacc += r.x * r.x + r.y * r.y;
-            if (xn) xn[i] = f64x2{(b.x + c.x) + r.x, (b.y + c.y) + r.y};
-          }
+          acc = sep_accumulate<false>(op, acc, a, b, c, r, s0, s1, xn, i);
           y[i] = r;
         }
       }
     }
   }
-  if constexpr (kStepOf<Op>) {
-    __shared__ double lds4[4];
-    const double t0 = block_sum4(hacc, lds4);
-    const double t1 = block_sum4(qacc, lds4);
-    const double t2 = block_sum4(yacc, lds4);
-    value_publish3(op, blockIdx.x, t0, t1, t2);
-  } else if constexpr (Op::kObj) {
-    __shared__ double lds4[4];
-    const double t = block_sum4(hacc, lds4);
-    value_publish(op, blockIdx.x, t);
-  }
+  if constexpr (kSumsOf<Op> > 0) value_publish(op, blockIdx.x, block_sum4(acc));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -796,20 +761,15 @@ __global__ __launch_bounds__(256) void k_sep_lds(double* y_, const double* q_, c
   if (xcd_chunk > 0) {
     bid = (int64_t)(blockIdx.x & 7) * xcd_chunk + (blockIdx.x >> 3);
     if (bid * (256 * UNROLL) >= n2) {
-      if constexpr (Op::kObj) {
-        if (threadIdx.x == 0) op.partials[bid] = 0.0;  // (a slot of its own: every slot the host counts is written)
-      }
-      if constexpr (kStepOf<Op>) {
-        if (threadIdx.x == 0) { op.partials[op.plane + bid] = 0.0; op.partials[2 * op.plane + bid] = 0.0; }
+      if constexpr (kSumsOf<Op> > 0) {
+        value_store(op, bid, SumsFor<Op>{});  // (a slot of its own: every slot the host counts is written; never the one-launch form)
       }
       return;
     }
   }
   const int64_t base = (bid * 4 + wave) * (64 * UNROLL) + lane;  // this lane's first pair
-  double hacc = 0.0;
-  double qacc = 0.0, yacc = 0.0;  // (WithStep) <q, y> and <y, y>
-  f64x2* xn = nullptr;
-  if constexpr (kStepOf<Op>) xn = reinterpret_cast<f64x2*>(op.xkn);
+  SumsFor<Op> acc = {};
+  f64x2* const xn = xkn_of<f64x2>(op);
   uint16_t vm[UNROLL];
 #pragma unroll
   for (int k = 0; k < UNROLL; ++k) {
@@ -844,51 +804,13 @@ __global__ __launch_bounds__(256) void k_sep_lds(double* y_, const double* q_, c
     f64x2 r;
     r.x = apply_op(op, a.x, dd.x, b.x, c.x, l0, u0, s0);
     r.y = apply_op(op, a.y, dd.y, b.y, c.y, l1, u1, s1);
-    if constexpr (Op::kObj) {
-      if (i < n2) hacc += op.hterm(b.x, c.x, r.x, s0) + op.hterm(b.y, c.y, r.y, s1);
-    }
-    if constexpr (kStepOf<Op>) {
-      if (i < n2) {
-        qacc += a.x * r.x + a.y * r.y;
-        yacc += r.x * r.x + r.y * r.y;
-        // (out of registers: the extra store needs no LDS)
-        if (xn) __builtin_nontemporal_store(f64x2{(b.x + c.x) + r.x, (b.y + c.y) + r.y}, xn + i);
-      }
+    if constexpr (kSumsOf<Op> > 0) {  // (the tail's lanes hold a copy of the last pair)
+      if (i < n2) acc = sep_accumulate<true>(op, acc, a, b, c, r, s0, s1, xn, i);  // (xkn out of registers: the extra store needs no LDS)
     }
     if (i < n2) __builtin_nontemporal_store(r, y + i);
   }
-  if constexpr (kStepOf<Op>) {
-    // as below, three doubles per wave: the first 24 bytes of the wave's (consumed) staging area
-    const double t0 = wave_sum(hacc), t1 = wave_sum(qacc), t2 = wave_sum(yacc);
-    if (lane == 0) {
-      double* w = reinterpret_cast<double*>(wl);
-      w[0] = t0; w[1] = t1; w[2] = t2;
-    }
-    __syncthreads();
-    double tb0 = 0.0, tb1 = 0.0, tb2 = 0.0;
-    if (threadIdx.x == 0) {
-      const double* w0 = reinterpret_cast<const double*>(lds);
-      constexpr int stride = NARR * UNROLL * 1024 / 8;
-      tb0 = (w0[0] + w0[stride]) + (w0[2 * stride] + w0[3 * stride]);
-      tb1 = (w0[1] + w0[stride + 1]) + (w0[2 * stride + 1] + w0[3 * stride + 1]);
-      tb2 = (w0[2] + w0[stride + 2]) + (w0[2 * stride + 2] + w0[3 * stride + 2]);
-    }
-    value_publish3(op, bid, tb0, tb1, tb2);
-  } else if constexpr (Op::kObj) {
-    // one partial per WORKGROUP (round 3; round 2 wrote one per wavefront: 130 208 of them at n = 1e8, and the ordered
-    // reduction behind the pass cost ~25 us of the fused call).  The wave's staging area has been consumed: its first 8 bytes
-    // carry the wave's sum to lane 0 of the workgroup, which adds the four in a fixed order.
-    const double t = wave_sum(hacc);
-    if (lane == 0) *reinterpret_cast<double*>(wl) = t;
-    __syncthreads();
-    double tb = 0.0;
-    if (threadIdx.x == 0) {
-      const double* w0 = reinterpret_cast<const double*>(lds);
-      constexpr int stride = NARR * UNROLL * 1024 / 8;
-      tb = (w0[0] + w0[stride]) + (w0[2 * stride] + w0[3 * stride]);
-    }
-    value_publish(op, bid, tb);
-  }
+  // one slot per WORKGROUP (one per wavefront meant 130 208 of them at n = 1e8, and ~25 us of ordered reduction behind the pass)
+  if constexpr (kSumsOf<Op> > 0) value_publish(op, bid, block_sum4_staged(acc, wl, lds, NARR * UNROLL * 1024));
 }
 
 // scalar path: unaligned vectors, and the odd last element of the vector path ([begin, n))
@@ -899,8 +821,8 @@ __global__ __launch_bounds__(256) void k_sep_scalar(double* y, const double* q, 
                                                      int64_t n, Op op) {
   int64_t i = begin + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  double hacc = 0.0;
-  double qacc = 0.0, yacc = 0.0;  // (WithStep) <q, y> and <y, y>
+  SumsFor<Op> acc = {};
+  double* const xn = xkn_of<double>(op);  // (indexed from element 0)
   for (; i < n; i += stride) {
     double li = l_ ? l_[i] : ls;
     double ui = u_ ? u_[i] : us;
@@ -908,30 +830,12 @@ __global__ __launch_bounds__(256) void k_sep_scalar(double* y, const double* q, 
     double di = 0.0;
     if constexpr (Op::kNIn == 4) di = d_[i];
     const double xi = xk[i], si = sj[i];
-    const double yi = apply_op(op, q[i], di, xi, si, li, ui, sel);
-    if constexpr (Op::kObj) hacc += op.hterm(xi, si, yi, sel);
-    if constexpr (kStepOf<Op>) {
-      qacc += q[i] * yi;
-      yacc += yi * yi;
-      if (op.xkn) op.xkn[i] = (xi + si) + yi;
-    }
+    const double qi = q[i];
+    const double yi = apply_op(op, qi, di, xi, si, li, ui, sel);
+    acc = sep_accumulate<false>(op, acc, qi, xi, si, yi, sel, false, xn, i);
     y[i] = yi;
   }
-  if constexpr (kStepOf<Op>) {
-    __shared__ double lds4[4];
-    const double t0 = block_sum4(hacc, lds4);
-    const double t1 = block_sum4(qacc, lds4);
-    const double t2 = block_sum4(yacc, lds4);
-    if (threadIdx.x == 0) {
-      op.partials[blockIdx.x] = t0;
-      op.partials[op.plane + blockIdx.x] = t1;
-      op.partials[2 * op.plane + blockIdx.x] = t2;
-    }
-  } else if constexpr (Op::kObj) {
-    __shared__ double lds4[4];
-    const double t = block_sum4(hacc, lds4);
-    if (threadIdx.x == 0) op.partials[blockIdx.x] = t;
-  }
+  if constexpr (kSumsOf<Op> > 0) value_store(op, blockIdx.x, block_sum4(acc));  // (never the only launch of a call)
 }
 
 // Tuning knobs (spx_ctx_set_tuning).  Defaults from tools/sweep_sep.py on MI355X, n = 1e8 (profiles/r01_sweep_sep.txt):
@@ -944,12 +848,12 @@ __global__ __launch_bounds__(256) void k_sep_scalar(double* y, const double* q, 
 template <class Op, bool VECB, bool MASK>
 static int launch_vec(spx_ctx* ctx, double* y, const double* q, const double* d, const double* xk, const double* sj,
                       const double* l, const double* u, const uint8_t* mask, double ls, double us, int64_t n2, Op op,
-                      int64_t* value_slots /* out: partial slots written (Op::kObj) */,
-                      const SpxSyncHeader* fuse_hdr = nullptr /* Op::kObj: this launch is the whole call -- it may finish the value itself */,
+                      int64_t* value_slots /* out: partial slots written (kSumsOf<Op> > 0) */,
+                      const SpxSyncHeader* fuse_hdr = nullptr /* kSumsOf<Op> > 0: this launch is the whole call -- it may finish the sums itself */,
                       bool* fused = nullptr) {
-  // (Op::kObj) the one-launch form: the grid is the list of slots, short enough for one workgroup to add
+  // (kSumsOf<Op> > 0) the one-launch form: the grid is the list of slots, short enough for one workgroup to add
   auto try_fuse = [&](int64_t blocks) {
-    if constexpr (Op::kObj) {
+    if constexpr (kSumsOf<Op> > 0) {
       if (fuse_hdr != nullptr && blocks <= kValueFuseMax && !ctx->tune_sep_xcd) {
         op.fin_hdr = const_cast<SpxSyncHeader*>(fuse_hdr);
         *fused = true;
@@ -989,35 +893,25 @@ static int launch_vec(spx_ctx* ctx, double* y, const double* q, const double* d,
   return SPX_OK;
 }
 
+// kSumsOf<Op> > 0: the sums {value_scale * h, <q, y>, <y, y>} (WithValue: the first of them) go to the library's result slots,
+// to result_dev (device doubles, or NULL) and, when result_host != NULL, back to the host -- that form synchronises and is
+// refused under a capture; those callers answer n == 0 themselves.
 template <class Op>
 static int run_separable(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
                          const double* l, const double* u, double ls, double us, const uint8_t* mask, Op op,
-                         const double* d = nullptr, double* value = nullptr /* Op::kObj: sum of the h terms */,
-                         double value_scale = 1.0 /* device-resident value = value_scale * sum */,
-                         double* xkn = nullptr /* WithStep: (xk + sj) + y, or NULL */,
-                         double* stats = nullptr /* WithStep: host double[3], or NULL: nothing is read back */,
-                         double* stats_dev = nullptr /* WithStep: device double[3], or NULL */) {
-  if constexpr (kStepOf<Op>) {
-    if (stats) stats[0] = stats[1] = stats[2] = 0.0;
-    if (n == 0) {
-      if (stats_dev == nullptr) return SPX_OK;
-      SPX_ON_DEVICE(ctx);
-      return spx_zero_async(ctx, stats_dev, 3 * sizeof(double));  // (a kernel, not a memset node)
-    }
-  } else if constexpr (Op::kObj) {
-    *value = 0.0;
-  }
+                         const double* d = nullptr, double* result_host = nullptr, double* result_dev = nullptr,
+                         double value_scale = 1.0, double* xkn = nullptr /* WithStep: (xk + sj) + y, or NULL */) {
+  constexpr int NS = kSumsOf<Op>;
   if (n == 0) return SPX_OK;
   SPX_ON_DEVICE(ctx);
-  double* partials = nullptr;  // ws: [result(s) | pad to 256 B | partial slots (WithStep: three planes of them)]
-  int64_t used = 0;
-  if constexpr (Op::kObj) {
-    const int64_t maxslots = ((n / 2) / (256 * 3) + 2) * 4 + 2 * (int64_t)ctx->num_cu * 8 + 16;
-    constexpr int planes = kStepOf<Op> ? 3 : 1;
-    int rcw = spx_ws_reserve(ctx, 256 + (size_t)planes * (size_t)maxslots * sizeof(double));
+  double* partials = nullptr;  // ws: [results | pad to 256 B | NS planes of partial slots]
+  int64_t used = 0, plane = 0;
+  if constexpr (NS > 0) {
+    plane = ((n / 2) / (256 * 3) + 2) * 4 + 2 * (int64_t)ctx->num_cu * 8 + 16;  // at least the slots of any route
+    int rcw = spx_ws_reserve(ctx, 256 + (size_t)NS * (size_t)plane * sizeof(double));
     if (rcw) return rcw;
     partials = reinterpret_cast<double*>(static_cast<char*>(ctx->ws) + 256);
-    if constexpr (kStepOf<Op>) op.plane = maxslots;
+    if constexpr (NS > 1) op.plane = plane;
     if (ctx->tune_fewer_launches) {  // (the one-launch form keeps its tickets in the synchronisation state)
       rcw = spx_sync_ready(ctx);
       if (rcw) return rcw;
@@ -1035,8 +929,8 @@ static int run_separable(spx_ctx* ctx, double* y, const double* q, const double*
     int64_t blocks = (end - begin + 255) / 256;
     const int64_t cap = (int64_t)ctx->num_cu * 8;
     if (blocks > cap) blocks = cap;
-    if constexpr (Op::kObj) op.partials = partials + used;
-    if constexpr (kStepOf<Op>) op.xkn = xkn;  // (indexed from element 0)
+    if constexpr (NS > 0) op.partials = partials + used;
+    if constexpr (NS == 3) op.xkn = xkn;  // (indexed from element 0)
     hipLaunchKernelGGL((k_sep_scalar<Op>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, y, q, d, xk, sj, l, u,
                        mask, ls, us, begin, end, op);
     SPX_LAUNCH_CHECK();
@@ -1060,18 +954,17 @@ static int run_separable(spx_ctx* ctx, double* y, const double* q, const double*
     int rc;
     int64_t slots = 0;
     const SpxSyncHeader* fh = nullptr;
-    if constexpr (Op::kObj) {
+    if constexpr (NS > 0) {
       op.partials = partials + used;
-      // one launch covers the whole vector (no peeled element in front, no odd element behind): it may finish the value
+      // one launch covers the whole vector (no peeled element in front, no odd element behind): it may finish the sums
       if (ctx->tune_fewer_launches && head == 0 && 2 * n2 == n) {
         fh = spx_sync_header(ctx);
         op.fin_result = reinterpret_cast<double*>(ctx->ws);
-        if constexpr (kStepOf<Op>) op.fin_target = stats_dev;  // (the context's value target does not apply)
-        else op.fin_target = ctx->value_target;
+        op.fin_target = result_dev;
         op.fin_scale = value_scale;
       }
     }
-    if constexpr (kStepOf<Op>) op.xkn = xkn ? xkn + head : nullptr;
+    if constexpr (NS == 3) op.xkn = xkn ? xkn + head : nullptr;
     if constexpr (Op::kBox) {
       const bool vecb = (l || u);
       const bool msk = (mask != nullptr);
@@ -1090,29 +983,20 @@ static int run_separable(spx_ctx* ctx, double* y, const double* q, const double*
     int rct = launch_scalar(done, n);
     if (rct) return rct;
   }
-  if constexpr (kStepOf<Op>) {
-    double* result = reinterpret_cast<double*>(ctx->ws);  // {value_scale * h, <q, y>, <y, y>}
-    if (!fused) {
-      hipLaunchKernelGGL(k_value_reduce3, dim3(3), dim3(1024), 0, ctx->stream, (const double*)partials, op.plane, used,
-                         result, value_scale, stats_dev);
-      SPX_LAUNCH_CHECK();
-    }
-    if (stats == nullptr) return SPX_OK;  // device results only: the call returns after enqueueing
-    SPX_HIP(hipMemcpyAsync(stats, result, 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    SPX_HIP(hipStreamSynchronize(ctx->stream));
-  } else if constexpr (Op::kObj) {
+  if constexpr (NS > 0) {
     double* result = reinterpret_cast<double*>(ctx->ws);
     if (!fused) {
-      hipLaunchKernelGGL(k_value_reduce, dim3(1), dim3(1024), 0, ctx->stream, (const double*)partials, used, result,
-                         value_scale, ctx->value_target);
+      hipLaunchKernelGGL(k_value_reduce<NS>, dim3(NS), dim3(1024), 0, ctx->stream, (const double*)partials, plane, used, result,
+                         value_scale, result_dev);
       SPX_LAUNCH_CHECK();
     }
-    if (ctx->value_target) {  // device-resident value: nothing is read back, the call returns after enqueueing
-      *value = std::numeric_limits<double>::quiet_NaN();
-      return SPX_OK;
+    if (result_host == nullptr) return SPX_OK;  // device results only: nothing is read back, the call returns after enqueueing
+    {
+      const int rcc = spx_require_not_capturing(ctx, NS == 1 ? "returning the value of prox_value to the host"
+                                                             : "returning the step statistics to the host (pass stats = NULL)");
+      if (rcc) return rcc;
     }
-    { const int rcc = spx_require_not_capturing(ctx, "returning the value of prox_value to the host"); if (rcc) return rcc; }
-    SPX_HIP(hipMemcpyAsync(value, result, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    SPX_HIP(hipMemcpyAsync(result_host, result, NS * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     SPX_HIP(hipStreamSynchronize(ctx->stream));
   }
   return SPX_OK;
@@ -1121,29 +1005,44 @@ static int run_separable(spx_ctx* ctx, double* y, const double* q, const double*
 // ---------------------------------------------------------------------------------------------
 // C entry points
 // ---------------------------------------------------------------------------------------------
+// The operators' constants from (lambda, sigma), stated once: y of spx_prox_X, spx_proxval_X and spx_proxstep_X has the
+// same bits because the three build the same functor.  Op: the Float64 or the Float32 struct of the operator.
+template <class Op, class T>
+static Op make_l1(T lambda, T sigma) { return Op{lambda * sigma}; }
+template <class Op, class T>
+static Op make_l0(T lambda, T sigma) { return Op{std::sqrt(2 * lambda * sigma)}; }
+template <class Op, class T>
+static Op make_l1_box(T lambda, T sigma) { return Op{sigma * lambda}; }
+template <class Op, class T>
+static Op make_l0_box(T lambda, T sigma) { return Op{2 * lambda * sigma}; }
+static OpLhalf make_lhalf(double lambda, double sigma) {
+  const double nl = sigma * lambda;
+  const double p = std::pow(54.0, 1.0 / 3.0) * std::pow(2 * nl, 2.0 / 3.0) / 4;  // shiftedRootNormLhalf.jl:49
+  return OpLhalf{nl / 4, p};
+}
+static OpLhalfBox make_lhalf_box(double lambda, double sigma) { return OpLhalfBox{sigma * lambda / 4, lambda, 0.5 / sigma}; }
+
 SPX_EXPORT int spx_prox_l1(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
                            double lambda, double sigma) {
   int rc = spx_check_common(ctx, y, q, xk, sj, n);
   if (rc) return rc;
   if (y == q && lambda * sigma >= 0.0)  // the reference's two-pass body with y === q (see OpL1Aliased)
     return run_separable(ctx, y, q, xk, sj, n, nullptr, nullptr, 0.0, 0.0, nullptr, OpL1Aliased{});
-  return run_separable(ctx, y, q, xk, sj, n, nullptr, nullptr, 0.0, 0.0, nullptr, OpL1{lambda * sigma});
+  return run_separable(ctx, y, q, xk, sj, n, nullptr, nullptr, 0.0, 0.0, nullptr, make_l1<OpL1>(lambda, sigma));
 }
 
 SPX_EXPORT int spx_prox_l0(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
                            double lambda, double sigma) {
   int rc = spx_check_common(ctx, y, q, xk, sj, n);
   if (rc) return rc;
-  return run_separable(ctx, y, q, xk, sj, n, nullptr, nullptr, 0.0, 0.0, nullptr, OpL0{std::sqrt(2 * lambda * sigma)});
+  return run_separable(ctx, y, q, xk, sj, n, nullptr, nullptr, 0.0, 0.0, nullptr, make_l0<OpL0>(lambda, sigma));
 }
 
 SPX_EXPORT int spx_prox_lhalf(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
                               double lambda, double sigma) {
   int rc = spx_check_common(ctx, y, q, xk, sj, n);
   if (rc) return rc;
-  const double nl = sigma * lambda;
-  const double p = std::pow(54.0, 1.0 / 3.0) * std::pow(2 * nl, 2.0 / 3.0) / 4;  // shiftedRootNormLhalf.jl:49
-  return run_separable(ctx, y, q, xk, sj, n, nullptr, nullptr, 0.0, 0.0, nullptr, OpLhalf{nl / 4, p});
+  return run_separable(ctx, y, q, xk, sj, n, nullptr, nullptr, 0.0, 0.0, nullptr, make_lhalf(lambda, sigma));
 }
 
 SPX_EXPORT int spx_prox_l1_box(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
@@ -1151,7 +1050,7 @@ SPX_EXPORT int spx_prox_l1_box(spx_ctx* ctx, double* y, const double* q, const d
                                double u_scalar, const uint8_t* sel_mask) {
   int rc = spx_check_common(ctx, y, q, xk, sj, n);
   if (rc) return rc;
-  return run_separable(ctx, y, q, xk, sj, n, l_vec, u_vec, l_scalar, u_scalar, sel_mask, OpL1Box{sigma * lambda});
+  return run_separable(ctx, y, q, xk, sj, n, l_vec, u_vec, l_scalar, u_scalar, sel_mask, make_l1_box<OpL1Box>(lambda, sigma));
 }
 
 SPX_EXPORT int spx_prox_l0_box(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
@@ -1159,7 +1058,7 @@ SPX_EXPORT int spx_prox_l0_box(spx_ctx* ctx, double* y, const double* q, const d
                                double u_scalar, const uint8_t* sel_mask) {
   int rc = spx_check_common(ctx, y, q, xk, sj, n);
   if (rc) return rc;
-  return run_separable(ctx, y, q, xk, sj, n, l_vec, u_vec, l_scalar, u_scalar, sel_mask, OpL0Box{2 * lambda * sigma});
+  return run_separable(ctx, y, q, xk, sj, n, l_vec, u_vec, l_scalar, u_scalar, sel_mask, make_l0_box<OpL0Box>(lambda, sigma));
 }
 
 SPX_EXPORT int spx_prox_lhalf_box(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj,
@@ -1168,7 +1067,7 @@ SPX_EXPORT int spx_prox_lhalf_box(spx_ctx* ctx, double* y, const double* q, cons
   int rc = spx_check_common(ctx, y, q, xk, sj, n);
   if (rc) return rc;
   return run_separable(ctx, y, q, xk, sj, n, l_vec, u_vec, l_scalar, u_scalar, sel_mask,
-                       OpLhalfBox{sigma * lambda / 4, lambda, 0.5 / sigma});
+                       make_lhalf_box(lambda, sigma));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1182,9 +1081,11 @@ static int run_proxval(spx_ctx* ctx, double* y, const double* q, const double* x
   if (rc) return rc;
   SPX_REQUIRE(value != nullptr, "value is NULL");
   WithValue<Base, Term> op{base, nullptr, q_scale};
-  double sum = 0.0;
-  rc = run_separable(ctx, y, q, xk, sj, n, l, u, ls, us, mask, op, nullptr, &sum, lambda);
-  *value = lambda * sum;  // (NaN when the value went to the context's device target)
+  double h = lambda * 0.0;  // (n == 0, or an error)
+  double* const target = ctx->value_target;  // device-resident value: nothing is read back, the call returns after enqueueing
+  rc = run_separable(ctx, y, q, xk, sj, n, l, u, ls, us, mask, op, nullptr, target ? nullptr : &h, target, lambda);
+  if (rc == SPX_OK && n > 0 && target) h = std::numeric_limits<double>::quiet_NaN();
+  *value = h;
   return rc;
 }
 
@@ -1195,38 +1096,36 @@ SPX_EXPORT int spx_proxval_l1(spx_ctx* ctx, double* y, const double* q, const do
     return run_proxval<OpL1Aliased, HTermL1>(ctx, y, q, xk, sj, n, nullptr, nullptr, 0.0, 0.0, nullptr, OpL1Aliased{},
                                              lambda, 1.0, value);
   }
-  return run_proxval<OpL1, HTermL1>(ctx, y, q, xk, sj, n, nullptr, nullptr, 0.0, 0.0, nullptr, OpL1{lambda * sigma},
-                                    lambda, q_scale, value);
+  return run_proxval<OpL1, HTermL1>(ctx, y, q, xk, sj, n, nullptr, nullptr, 0.0, 0.0, nullptr,
+                                    make_l1<OpL1>(lambda, sigma), lambda, q_scale, value);
 }
 SPX_EXPORT int spx_proxval_l0(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
                               double lambda, double sigma, double q_scale, double* value) {
   return run_proxval<OpL0, HTermL0>(ctx, y, q, xk, sj, n, nullptr, nullptr, 0.0, 0.0, nullptr,
-                                    OpL0{std::sqrt(2 * lambda * sigma)}, lambda, q_scale, value);
+                                    make_l0<OpL0>(lambda, sigma), lambda, q_scale, value);
 }
 SPX_EXPORT int spx_proxval_lhalf(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
                                  double lambda, double sigma, double q_scale, double* value) {
-  const double nl = sigma * lambda;
-  const double p = std::pow(54.0, 1.0 / 3.0) * std::pow(2 * nl, 2.0 / 3.0) / 4;
-  return run_proxval<OpLhalf, HTermLhalf>(ctx, y, q, xk, sj, n, nullptr, nullptr, 0.0, 0.0, nullptr, OpLhalf{nl / 4, p},
-                                          lambda, q_scale, value);
+  return run_proxval<OpLhalf, HTermLhalf>(ctx, y, q, xk, sj, n, nullptr, nullptr, 0.0, 0.0, nullptr,
+                                          make_lhalf(lambda, sigma), lambda, q_scale, value);
 }
 SPX_EXPORT int spx_proxval_l1_box(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
                                   double lambda, double sigma, const double* l_vec, const double* u_vec,
                                   double l_scalar, double u_scalar, const uint8_t* sel_mask, double q_scale, double* value) {
   return run_proxval<OpL1Box, HTermL1>(ctx, y, q, xk, sj, n, l_vec, u_vec, l_scalar, u_scalar, sel_mask,
-                                       OpL1Box{sigma * lambda}, lambda, q_scale, value);
+                                       make_l1_box<OpL1Box>(lambda, sigma), lambda, q_scale, value);
 }
 SPX_EXPORT int spx_proxval_l0_box(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
                                   double lambda, double sigma, const double* l_vec, const double* u_vec,
                                   double l_scalar, double u_scalar, const uint8_t* sel_mask, double q_scale, double* value) {
   return run_proxval<OpL0Box, HTermL0>(ctx, y, q, xk, sj, n, l_vec, u_vec, l_scalar, u_scalar, sel_mask,
-                                       OpL0Box{2 * lambda * sigma}, lambda, q_scale, value);
+                                       make_l0_box<OpL0Box>(lambda, sigma), lambda, q_scale, value);
 }
 SPX_EXPORT int spx_proxval_lhalf_box(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj,
                                      int64_t n, double lambda, double sigma, const double* l_vec, const double* u_vec,
                                      double l_scalar, double u_scalar, const uint8_t* sel_mask, double q_scale, double* value) {
   return run_proxval<OpLhalfBox, HTermLhalf>(ctx, y, q, xk, sj, n, l_vec, u_vec, l_scalar, u_scalar, sel_mask,
-                                             OpLhalfBox{sigma * lambda / 4, lambda, 0.5 / sigma}, lambda, q_scale, value);
+                                             make_lhalf_box(lambda, sigma), lambda, q_scale, value);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1247,51 +1146,55 @@ static int run_proxstep(spx_ctx* ctx, double* y, const double* q, const double* 
   }
   // the host copy synchronises: refused under a capture before anything is enqueued
   if (stats != nullptr) { rc = spx_require_not_capturing(ctx, "returning the step statistics to the host (pass stats = NULL)"); if (rc) return rc; }
+  if (stats) stats[0] = stats[1] = stats[2] = 0.0;
+  if (n == 0) {
+    if (stats_dev == nullptr) return SPX_OK;
+    SPX_ON_DEVICE(ctx);
+    return spx_zero_async(ctx, stats_dev, 3 * sizeof(double));  // (a kernel, not a memset node)
+  }
   WithStep<Base, Term> op{};
   static_cast<Base&>(op) = base;
   op.qscale = q_scale;
-  return run_separable(ctx, y, q, xk, sj, n, l, u, ls, us, mask, op, nullptr, nullptr, lambda, xkn, stats, stats_dev);
+  // (the context's value target applies to prox_value only)
+  return run_separable(ctx, y, q, xk, sj, n, l, u, ls, us, mask, op, nullptr, stats, stats_dev, lambda, xkn);
 }
 
 SPX_EXPORT int spx_proxstep_l1(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
                                double lambda, double sigma, double q_scale, double* xkn, double* stats, double* stats_dev) {
-  return run_proxstep<OpL1, HTermL1>(ctx, y, q, xk, sj, n, nullptr, nullptr, 0.0, 0.0, nullptr, OpL1{lambda * sigma},
-                                     lambda, q_scale, xkn, stats, stats_dev);
+  return run_proxstep<OpL1, HTermL1>(ctx, y, q, xk, sj, n, nullptr, nullptr, 0.0, 0.0, nullptr,
+                                     make_l1<OpL1>(lambda, sigma), lambda, q_scale, xkn, stats, stats_dev);
 }
 SPX_EXPORT int spx_proxstep_l0(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
                                double lambda, double sigma, double q_scale, double* xkn, double* stats, double* stats_dev) {
   return run_proxstep<OpL0, HTermL0>(ctx, y, q, xk, sj, n, nullptr, nullptr, 0.0, 0.0, nullptr,
-                                     OpL0{std::sqrt(2 * lambda * sigma)}, lambda, q_scale, xkn, stats, stats_dev);
+                                     make_l0<OpL0>(lambda, sigma), lambda, q_scale, xkn, stats, stats_dev);
 }
 SPX_EXPORT int spx_proxstep_lhalf(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
                                   double lambda, double sigma, double q_scale, double* xkn, double* stats,
                                   double* stats_dev) {
-  const double nl = sigma * lambda;
-  const double p = std::pow(54.0, 1.0 / 3.0) * std::pow(2 * nl, 2.0 / 3.0) / 4;
-  return run_proxstep<OpLhalf, HTermLhalf>(ctx, y, q, xk, sj, n, nullptr, nullptr, 0.0, 0.0, nullptr, OpLhalf{nl / 4, p},
-                                           lambda, q_scale, xkn, stats, stats_dev);
+  return run_proxstep<OpLhalf, HTermLhalf>(ctx, y, q, xk, sj, n, nullptr, nullptr, 0.0, 0.0, nullptr,
+                                           make_lhalf(lambda, sigma), lambda, q_scale, xkn, stats, stats_dev);
 }
 SPX_EXPORT int spx_proxstep_l1_box(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
                                    double lambda, double sigma, const double* l_vec, const double* u_vec, double l_scalar,
                                    double u_scalar, const uint8_t* sel_mask, double q_scale, double* xkn, double* stats,
                                    double* stats_dev) {
   return run_proxstep<OpL1Box, HTermL1>(ctx, y, q, xk, sj, n, l_vec, u_vec, l_scalar, u_scalar, sel_mask,
-                                        OpL1Box{sigma * lambda}, lambda, q_scale, xkn, stats, stats_dev);
+                                        make_l1_box<OpL1Box>(lambda, sigma), lambda, q_scale, xkn, stats, stats_dev);
 }
 SPX_EXPORT int spx_proxstep_l0_box(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
                                    double lambda, double sigma, const double* l_vec, const double* u_vec, double l_scalar,
                                    double u_scalar, const uint8_t* sel_mask, double q_scale, double* xkn, double* stats,
                                    double* stats_dev) {
   return run_proxstep<OpL0Box, HTermL0>(ctx, y, q, xk, sj, n, l_vec, u_vec, l_scalar, u_scalar, sel_mask,
-                                        OpL0Box{2 * lambda * sigma}, lambda, q_scale, xkn, stats, stats_dev);
+                                        make_l0_box<OpL0Box>(lambda, sigma), lambda, q_scale, xkn, stats, stats_dev);
 }
 SPX_EXPORT int spx_proxstep_lhalf_box(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj,
                                       int64_t n, double lambda, double sigma, const double* l_vec, const double* u_vec,
                                       double l_scalar, double u_scalar, const uint8_t* sel_mask, double q_scale,
                                       double* xkn, double* stats, double* stats_dev) {
   return run_proxstep<OpLhalfBox, HTermLhalf>(ctx, y, q, xk, sj, n, l_vec, u_vec, l_scalar, u_scalar, sel_mask,
-                                              OpLhalfBox{sigma * lambda / 4, lambda, 0.5 / sigma}, lambda, q_scale, xkn,
-                                              stats, stats_dev);
+                                              make_lhalf_box(lambda, sigma), lambda, q_scale, xkn, stats, stats_dev);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1456,24 +1359,24 @@ int run_f32(spx_ctx* ctx, float* y, const float* q, const float* xk, const float
 SPX_EXPORT int spx_prox_l1_f32(spx_ctx* ctx, float* y, const float* q, const float* xk, const float* sj, int64_t n,
                                float lambda, float sigma) {
   if (y == q && n > 0) return run_f32(ctx, y, q, xk, sj, n, nullptr, nullptr, 0.0f, 0.0f, nullptr, F32L1Aliased{});
-  return run_f32(ctx, y, q, xk, sj, n, nullptr, nullptr, 0.0f, 0.0f, nullptr, F32L1{lambda * sigma});
+  return run_f32(ctx, y, q, xk, sj, n, nullptr, nullptr, 0.0f, 0.0f, nullptr, make_l1<F32L1>(lambda, sigma));
 }
 
 SPX_EXPORT int spx_prox_l0_f32(spx_ctx* ctx, float* y, const float* q, const float* xk, const float* sj, int64_t n,
                                float lambda, float sigma) {
-  return run_f32(ctx, y, q, xk, sj, n, nullptr, nullptr, 0.0f, 0.0f, nullptr, F32L0{sqrtf(2 * lambda * sigma)});
+  return run_f32(ctx, y, q, xk, sj, n, nullptr, nullptr, 0.0f, 0.0f, nullptr, make_l0<F32L0>(lambda, sigma));
 }
 
 SPX_EXPORT int spx_prox_l1_box_f32(spx_ctx* ctx, float* y, const float* q, const float* xk, const float* sj, int64_t n,
                                    float lambda, float sigma, const float* l_vec, const float* u_vec, float l_scalar,
                                    float u_scalar, const uint8_t* sel_mask) {
-  return run_f32(ctx, y, q, xk, sj, n, l_vec, u_vec, l_scalar, u_scalar, sel_mask, F32L1Box{sigma * lambda});
+  return run_f32(ctx, y, q, xk, sj, n, l_vec, u_vec, l_scalar, u_scalar, sel_mask, make_l1_box<F32L1Box>(lambda, sigma));
 }
 
 SPX_EXPORT int spx_prox_l0_box_f32(spx_ctx* ctx, float* y, const float* q, const float* xk, const float* sj, int64_t n,
                                    float lambda, float sigma, const float* l_vec, const float* u_vec, float l_scalar,
                                    float u_scalar, const uint8_t* sel_mask) {
-  return run_f32(ctx, y, q, xk, sj, n, l_vec, u_vec, l_scalar, u_scalar, sel_mask, F32L0Box{2 * lambda * sigma});
+  return run_f32(ctx, y, q, xk, sj, n, l_vec, u_vec, l_scalar, u_scalar, sel_mask, make_l0_box<F32L0Box>(lambda, sigma));
 }
 
 

@@ -825,6 +825,28 @@ def prox_value(ψ, q, σ, q_scale=1.0):
     return prox_value_bang(ψ.sol, ψ, q, σ, q_scale)
 
 
+def _prox_step_call(name, y, ψ, q, q_scale, xkn, out, call):
+    """the argument checks and the two result forms that prox_step_bang and group_prox_step_bang share.  call(L, ctx, n, tail)
+    makes the library call and returns its status; tail = (q_scale, xkn, host double[3] or None, device double[3] or NULL)"""
+    n = _n(ψ.xk)
+    _vec(q, "q", n, like=ψ.xk)
+    _vec(y, "y", n, like=ψ.xk)
+    if xkn is not None:
+        _vec(xkn, "xkn", n, like=ψ.xk)
+    if y is q:
+        raise TypeError("%s: y must not be q (qy is taken with the q that was passed)" % name)
+    if out is not None and not (type(out) is _Tensor and out.is_cuda and out.dtype == torch.float64 and out.dim() == 1
+                                and out.numel() >= 3 and out.stride(0) == 1 and out.device == ψ.xk.device):
+        raise TypeError("out must be a contiguous float64 device tensor with at least 3 elements on ψ.xk's device")
+    ψ._refresh()
+    host = (ctypes.c_double * 3)() if out is None else None
+    tail = (float(q_scale), _ptr(xkn), host, ctypes.c_void_p(out.data_ptr()) if out is not None else _NULL)
+    _lib.check(call(_lib.load(), _ctx(_dev(y)), n, tail))
+    if out is not None:
+        return y, out
+    return y, host[0], host[1], host[2]
+
+
 def prox_step_bang(y, ψ, q, σ, q_scale=1.0, xkn=None, out=None):
     """prox!(y, ψ, q_scale .* q, σ) and the step statistics of a solver iteration in ONE pass over the vectors (what R2 / TR
     do around the prox: `h(xk + s)`, `dot(∇f, s)`, `xk + s`, `‖s‖`):
@@ -844,32 +866,18 @@ def prox_step_bang(y, ψ, q, σ, q_scale=1.0, xkn=None, out=None):
     if not isinstance(ψ, (_Unboxed, _Boxed)) or ψ.host or ψ.f32:
         raise TypeError("prox_step is available for ShiftedNormL1 / ShiftedNormL0 / ShiftedRootNormLhalf and their Box forms "
                         "on device Float64 vectors (no host ψ, Float32, group, top-r or ShiftedNormL1B2 form)")
-    n = _n(ψ.xk)
-    _vec(q, "q", n, like=ψ.xk)
-    _vec(y, "y", n, like=ψ.xk)
-    if xkn is not None:
-        _vec(xkn, "xkn", n, like=ψ.xk)
-    if y is q:
-        raise TypeError("prox_step: y must not be q (qy is taken with the q that was passed)")
-    if out is not None and not (type(out) is _Tensor and out.is_cuda and out.dtype == torch.float64 and out.dim() == 1
-                                and out.numel() >= 3 and out.stride(0) == 1 and out.device == ψ.xk.device):
-        raise TypeError("out must be a contiguous float64 device tensor with at least 3 elements on ψ.xk's device")
-    ψ._refresh()
-    L, ctx = _lib.load(), _ctx(_dev(y))
-    host = (ctypes.c_double * 3)() if out is None else None
-    tail = (float(q_scale), _ptr(xkn), host, ctypes.c_void_p(out.data_ptr()) if out is not None else _NULL)
-    fn = getattr(L, ψ._fn.replace("spx_prox_", "spx_proxstep_"))
-    if isinstance(ψ, _Boxed):
+
+    def call(L, ctx, n, tail):
+        fn = getattr(L, ψ._fn.replace("spx_prox_", "spx_proxstep_"))
+        if not isinstance(ψ, _Boxed):
+            return fn(ctx, _ptr(y), _ptr(q), _ptr(ψ.xk), _ptr(ψ.sj), n, ψ.h.lam, float(σ), *tail)
         lv = None if _is_real(ψ.l) else _vec(ψ.l, "l", n, like=y)
         uv = None if _is_real(ψ.u) else _vec(ψ.u, "u", n, like=y)
-        _lib.check(fn(ctx, _ptr(y), _ptr(q), _ptr(ψ.xk), _ptr(ψ.sj), n, ψ.h.lam, float(σ), _ptr(lv), _ptr(uv),
-                      float(ψ.l) if lv is None else 0.0, float(ψ.u) if uv is None else 0.0,
-                      _ptr(ψ._mask[0]) if ψ._mask is not None else ctypes.c_void_p(0), *tail))
-    else:
-        _lib.check(fn(ctx, _ptr(y), _ptr(q), _ptr(ψ.xk), _ptr(ψ.sj), n, ψ.h.lam, float(σ), *tail))
-    if out is not None:
-        return y, out
-    return y, host[0], host[1], host[2]
+        return fn(ctx, _ptr(y), _ptr(q), _ptr(ψ.xk), _ptr(ψ.sj), n, ψ.h.lam, float(σ), _ptr(lv), _ptr(uv),
+                  float(ψ.l) if lv is None else 0.0, float(ψ.u) if uv is None else 0.0,
+                  _ptr(ψ._mask[0]) if ψ._mask is not None else ctypes.c_void_p(0), *tail)
+
+    return _prox_step_call("prox_step", y, ψ, q, q_scale, xkn, out, call)
 
 
 def prox_step(ψ, q, σ, q_scale=1.0, xkn=None, out=None):
@@ -900,28 +908,14 @@ def group_prox_step_bang(y, ψ, q, σ, q_scale=1.0, xkn=None, out=None):
     g = ψ._layout
     if _is_host(ψ.xk) or ψ.xk.dtype != torch.float64 or g.index is not None:
         raise TypeError("group_prox_step needs device Float64 vectors and contiguous groups")
-    n = _n(ψ.xk)
-    _vec(q, "q", n, like=ψ.xk)
-    _vec(y, "y", n, like=ψ.xk)
-    if xkn is not None:
-        _vec(xkn, "xkn", n, like=ψ.xk)
-    if y is q:
-        raise TypeError("group_prox_step: y must not be q (qy is taken with the q that was passed)")
-    if out is not None and not (type(out) is _Tensor and out.is_cuda and out.dtype == torch.float64 and out.dim() == 1
-                                and out.numel() >= 3 and out.stride(0) == 1 and out.device == ψ.xk.device):
-        raise TypeError("out must be a contiguous float64 device tensor with at least 3 elements on ψ.xk's device")
-    ψ._refresh()
-    L, ctx = _lib.load(), _ctx(_dev(y))
-    host = (ctypes.c_double * 3)() if out is None else None
-    head = (ctx, _ptr(y), _ptr(q), _ptr(ψ.xk), _ptr(ψ.sj), n, _ptr(g.offsets), g.group_size, g.ngroups, _ptr(g.lam), float(σ))
-    tail = (float(q_scale), _ptr(xkn), host, ctypes.c_void_p(out.data_ptr()) if out is not None else _NULL)
-    if isinstance(ψ, ShiftedGroupNormL2Binf):
-        _lib.check(L.spx_proxstep_group_l2_binf(*head, ψ.Δ, *tail))
-    else:
-        _lib.check(L.spx_proxstep_group_l2(*head, *tail))
-    if out is not None:
-        return y, out
-    return y, host[0], host[1], host[2]
+
+    def call(L, ctx, n, tail):
+        head = (ctx, _ptr(y), _ptr(q), _ptr(ψ.xk), _ptr(ψ.sj), n, _ptr(g.offsets), g.group_size, g.ngroups, _ptr(g.lam), float(σ))
+        if isinstance(ψ, ShiftedGroupNormL2Binf):
+            return L.spx_proxstep_group_l2_binf(*head, ψ.Δ, *tail)
+        return L.spx_proxstep_group_l2(*head, *tail)
+
+    return _prox_step_call("group_prox_step", y, ψ, q, q_scale, xkn, out, call)
 
 
 def group_prox_step(ψ, q, σ, q_scale=1.0, xkn=None, out=None):

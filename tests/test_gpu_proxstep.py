@@ -224,6 +224,41 @@ def test_prox_step_kernel_forms(s, n):
         _set(s, 17, 1); _set(s, 3, 1); _set(s, 1, 1); _set(s, 0, 0)
 
 
+@pytest.mark.parametrize("n,vecb", [(6146, False), (30722, False), (3074, True)])
+def test_prox_value_and_step_xcd_contiguous_tiles(s, n, vecb):
+    """key 5 = 1 (XCD-contiguous tile ranges): the grid is rounded up to a multiple of 8 workgroups, the workgroup ids are
+    remapped, and the workgroups left without a tile store zero slots.  Scalar bounds, 3072 elements per workgroup: n = 6146 is
+    3 working workgroups of 8 launched, n = 30722 is 11 of 16 with remapped ids; vector bounds and a mask, 1536 per workgroup:
+    n = 3074 is 3 of 8; the last tile is one pair each time.  Against the key 5 = 0 call: y and xkn have equal bits, and so
+    have the value and the three sums -- the same tile lands in the same slot, and the extra slots add +0.0."""
+    import torch
+    x, sj, q, lo, up, selected = _data(n, 9550 + n)
+    xd, sd, qd, ld, ud = _dev((x, sj, q, lo, up))
+    if vecb:
+        psi = s.shifted(s.shifted(s.NormL1(0.7), xd, ld, ud, selected), sd)
+    else:
+        psi = s.shifted(s.shifted(s.NormL1(0.7), xd, 0.9, s.NormLinf(1.0)), sd)
+    got = {}
+    try:
+        for k5 in (0, 1):
+            _set(s, 5, k5)
+            y_pv, v = s.prox_value(psi, qd, 1.1)
+            y_pv = y_pv.clone()
+            xkn = _buf(n)
+            y, h, qy, yy = s.prox_step(psi, qd, 1.1, xkn=xkn)
+            got[k5] = (y_pv, y.clone(), xkn, [float(t).hex() for t in (v, h, qy, yy)])
+    finally:
+        _set(s, 5, 0)
+    what = "key 5 n=%d vecb=%s" % (n, vecb)
+    print(what, got[0][3], got[1][3])
+    for a, b in zip(got[0][:3], got[1][:3]):
+        assert torch.equal(a, b), what
+    assert got[0][3] == got[1][3], (what, got[0][3], got[1][3])
+    assert torch.equal(got[1][0], got[1][1]) and torch.equal(got[1][2], (xd + sd) + got[1][1]), what
+    _check_h("l1", float.fromhex(got[1][3][1]), psi(got[1][1]), what)
+    _check_sums(q, got[1][1].cpu().numpy(), float.fromhex(got[1][3][2]), float.fromhex(got[1][3][3]), what)
+
+
 def test_prox_step_xkn_alone_misaligned(s):
     """every other vector 16-byte aligned and xkn 8 bytes off, and the reverse: the call takes the element-wise route, stores
     every element and nothing else"""

@@ -8,7 +8,7 @@ cur=None; rows=[]
 for line in sys.stdin:
     m=re.search(r'Function Name: (\S+)',line)
     if m: cur={'name':m.group(1)}; rows.append(cur); continue
-    for key,pat in (('vgpr',r' VGPRs: (\d+)'),('sgpr',r' SGPRs: (\d+)'),('occ',r'Occupancy \[waves/SIMD\]: (\d+)'),('spill',r'VGPRs Spill: (\d+)'),('lds',r'LDS Size \[bytes/block\]: (\d+)'),('scratch',r'ScratchSize \[bytes/lane\]: (\d+)')):
+    for key,pat in (('vgpr',r' VGPRs: (\d+)'),('sgpr',r'SGPRs: (\d+)'),('occ',r'Occupancy \[waves/SIMD\]: (\d+)'),('spill',r'VGPRs Spill: (\d+)'),('lds',r'LDS Size \[bytes/block\]: (\d+)'),('scratch',r'ScratchSize \[bytes/lane\]: (\d+)')):
         m=re.search(pat,line)
         if m and cur is not None: cur[key]=m.group(1)
 flt=sys.argv[1] if len(sys.argv)>1 else ''

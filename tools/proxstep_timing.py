@@ -8,8 +8,9 @@
 Warm, HIP-event stopwatch on the context's stream, every result in device doubles (no read-back in any leg).  The legs of a
 shape alternate round by round; the figure is the median round, the spread (max - min) / median of the rounds of (a) is
 printed beside it.  With --parent-lib PATH (a libspx.so built from the parent commit) leg (a) is also timed on that build, in
-the same rounds: (a) must not have moved -- the difference is to be read against the spread of repeating (a) on one build,
-which is measured as a second, independent series of (a) in the same rounds.
+the same rounds, and so are (c) and (d) when that build has spx_proxstep_*: they must not have moved -- new / parent of each
+is to be read against the spread of repeating (a) on one build, which is measured as a second, independent series of (a) in
+the same rounds: the last column says whether every ratio lies within max(spread, |(a') / (a) - 1|) of 1.
 
     timeout -k 10 900 python tools/proxstep_timing.py [--out profiles/proxstep_timing.txt] [--quick] [--parent-lib PATH]
     timeout -k 10 300 rocprofv3 --kernel-trace --stats -d DIR -- python tools/proxstep_timing.py --one    # a profile of its own
@@ -28,7 +29,7 @@ import __graft_entry__ as ge
 ap = argparse.ArgumentParser()
 ap.add_argument("--out", default=None, help="also write the table to this file")
 ap.add_argument("--quick", action="store_true", help="n <= 1e6 only, fewer rounds (a rehearsal of the tool, not a measurement)")
-ap.add_argument("--parent-lib", default=None, help="libspx.so of the parent commit: leg (a) is timed on it too")
+ap.add_argument("--parent-lib", default=None, help="libspx.so of the parent commit: leg (a), and (c), (d) if it has them, are timed on it too")
 ap.add_argument("--one", action="store_true", help="only 20 calls of spx_proxstep_l1_box at n = 1e8 (for a profiler run)")
 args = ap.parse_args()
 
@@ -51,13 +52,14 @@ def check_rc(lib, rc):
 
 # the parent build, loaded beside this one: its own context on the same stream
 LP = ctxp = None
+parent_step = False
 if args.parent_lib:
     LP = ctypes.CDLL(os.path.abspath(args.parent_lib))
     for name, sig in s._lib.SIGNATURES.items():
         if hasattr(LP, name):
             getattr(LP, name).argtypes = sig
             getattr(LP, name).restype = ctypes.c_char_p if name == "spx_last_error" else ctypes.c_int
-    assert not hasattr(LP, "spx_proxstep_l1"), "--parent-lib has spx_proxstep_*: not a build of the parent commit"
+    parent_step = hasattr(LP, "spx_proxstep_l1")
     ctxp = ctypes.c_void_p()
     check_rc(LP, LP.spx_ctx_create_on_stream(0, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream), ctypes.byref(ctxp)))
 
@@ -70,10 +72,12 @@ if args.one:
 
 lines = ["# (a) spx_proxval_X  (b) proxval + dot(q, y) + add(xk, y, out=xkn) + dot(y, y)  (c) spx_proxstep_X with xkn  (d) without xkn",
          "# [ms per call, median of the rounds; spread = (max - min) / median of the rounds of (a)]",
-         "# (a') = a second, independent series of (a) on this build; (a-parent) = (a) on the parent commit's build, same rounds",
+         "# (a') = a second, independent series of (a) on this build; (x-parent) = (x) on the parent commit's build, same rounds",
+         "# a/par, c/par, d/par = this build over the parent's; within: every one of them within max(spread, |(a')/(a) - 1|) of 1",
          "# device: %s" % torch.cuda.get_device_name(0),
          "%-18s %10s %9s %9s %9s %9s %7s %7s %7s | %9s %9s %8s %8s" % ("operator", "n", "(a)", "(b)", "(c)", "(d)", "(c)/(b)", "(c)/(a)",
-                                                                          "(d)/(a)", "(a')", "(a-parent)", "spread", "par/(a)")]
+                                                                          "(d)/(a)", "(a')", "(a-parent)", "spread", "par/(a)")
+         + (" | %10s %10s %7s %7s %7s %6s" % ("(c-parent)", "(d-parent)", "a/par", "c/par", "d/par", "within") if parent_step else "")]
 print("\n".join(lines), flush=True)
 target = torch.zeros(1, dtype=torch.float64, device=dev)
 stats = torch.zeros(3, dtype=torch.float64, device=dev)
@@ -109,15 +113,17 @@ try:
                 torch.add(xk, y, out=xkn)
                 torch.dot(y, y, out=dots[1])
 
-            def leg_c():
-                check_rc(L, getattr(L, "spx_proxstep_" + sym)(ctx, *vec, *box, qs, ptr(xkn), None, ptr(stats)))
+            def leg_c(lib=L, c=ctx):
+                check_rc(lib, getattr(lib, "spx_proxstep_" + sym)(c, *vec, *box, qs, ptr(xkn), None, ptr(stats)))
 
-            def leg_d():
-                check_rc(L, getattr(L, "spx_proxstep_" + sym)(ctx, *vec, *box, qs, None, None, ptr(stats)))
+            def leg_d(lib=L, c=ctx):
+                check_rc(lib, getattr(lib, "spx_proxstep_" + sym)(c, *vec, *box, qs, None, None, ptr(stats)))
 
             legs = [leg_a, leg_b, leg_c, leg_d, leg_a]
             if LP is not None:
                 legs.append(lambda: leg_a(LP, ctxp))
+            if parent_step:
+                legs += [lambda: leg_c(LP, ctxp), lambda: leg_d(LP, ctxp)]
             if args.one:
                 for _ in range(20):
                     leg_c()
@@ -150,6 +156,11 @@ try:
             par = med[5] if LP is not None else float("nan")
             line = "%-18s %10d %9.4f %9.4f %9.4f %9.4f %7.3f %7.3f %7.3f | %9.4f %9.4f %7.1f%% %8.3f" % (
                 op, n, a, b, c, d, c / b, c / a, d / a, a2, par, 100.0 * spread, par / a)
+            if parent_step:
+                cp, dp = med[6], med[7]
+                tol = max(spread, abs(a2 / a - 1.0))
+                ok = all(abs(r - 1.0) <= tol for r in (a / par, c / cp, d / dp))
+                line += " | %10.4f %10.4f %7.3f %7.3f %7.3f %6s" % (cp, dp, a / par, c / cp, d / dp, "yes" if ok else "NO")
             lines.append(line)
             print(line, flush=True)
         del xk, sj, q, y, xkn, lo, up, mask
