@@ -147,6 +147,8 @@ int spx_timer_stop(spx_ctx* ctx, float* elapsed_ms); /* records stop, waits, ret
  * last adds the partial sums, in the order the separate final launch did -- and ShiftedGroupNormL2Binf on uniform groups
  * runs without the zero-fill launch of its deferred list (two count words that alternate between calls; under a stream
  * capture the zero-fill node stays); 0 = three launches each, as in rounds 1-3.  Same bits either way.
+ * Key 18 = spx_proxstep_l1_b2 takes its composed route on every form (1; 0, default: the fused route where the form has
+ * one).  For A/B runs and the tests: y, xkn and [0] keep their bits, [1] and [2] are added in another order.
  * Key 9 DOES change results, within the stated tolerance: ShiftedGroupNormL2Binf, 0 (default) = the closed form at the root
  * (within ~1e-15 of the exact value of the reference's formula everywhere), 1 = groups whose root sits next to the pole of
  * step(n) (u < n / 1000) are evaluated literally, operation by operation as src/shiftedGroupNormL2Binf.jl:87-113 with
@@ -309,9 +311,9 @@ int spx_proxval_lhalf_box(spx_ctx* ctx, double* y, const double* q, const double
  * ticket per workgroup publishes its three partial sums, and the last workgroup (or the separate launch) adds each of the
  * three in the order the single sum of spx_proxval_X is added.  [0] has the bits of spx_proxval_X's value whenever both
  * calls take the same kernel form (same tuning keys, xkn aligned like the other vectors).
- * Float64 and device pointers only: there is no Float32 form, no host-pointer twin (spx_host_*), and no top-r /
- * ShiftedNormL1B2 form -- their fused-value kernels have different exits.  The group operators have a form of their own:
- * spx_proxstep_group_l2[_binf], below. */
+ * Float64 and device pointers only: there is no Float32 form, no host-pointer twin (spx_host_*), and no top-r form (its h is
+ * 0 at any prox result).  The group operators and ShiftedNormL1B2 have forms of their own: spx_proxstep_group_l2[_binf] and
+ * spx_proxstep_l1_b2, below. */
 int spx_proxstep_l1(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
                     double lambda, double sigma, double q_scale, double* xkn, double* stats, double* stats_dev);
 int spx_proxstep_l0(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
@@ -448,6 +450,41 @@ int spx_obj_l1_b2(spx_ctx* ctx, const double* y, const double* xk, const double*
  * that form should compose instead is decided by tools/b2_proxval_timing.py on vectors of mixed alignment.) */
 int spx_proxval_l1_b2(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
                       double lambda, double sigma, double delta, double chi_lambda, double q_scale, double* value);
+/* prox! fused with the step statistics of a trust-region iteration -- the contract of spx_proxstep_* (above) on
+ * ShiftedNormL1B2: `s = prox!(...)`, `h(xk + s)`, `dot(grad f, s)`, `xk + s`, `norm(s)` in one call.  The argument list of
+ * spx_proxval_l1_b2 up to and including q_scale, then the tail of spx_proxstep_*:
+ *   y        : bit-identical to spx_prox_l1_b2 at q_scale * q -- on every form (register-resident, xk in LDS, streaming with
+ *              16-byte accesses, streaming with 8-byte accesses), with the trust region active or inactive, whichever of the
+ *              five store sites ends up standing.  The form and the grid are chosen from y, q, xk, sj and the plain kernels'
+ *              residency alone: xkn takes no part in that choice (nor in whether stores may be speculative).
+ *   xkn      : device pointer to n doubles, or NULL.  xkn[i] = (xk[i] + sj[i]) + y[i], in that association, for EVERY i, from
+ *              the y that stands.  A pointer EQUAL to y, q, xk or sj returns SPX_ERR_INVALID_ARG, nothing is launched; no
+ *              other overlap is checked.  Any 8-byte alignment: an alignment that differs from the other vectors' does NOT
+ *              change the form -- the xkn store alone drops to 8-byte stores, y keeps the bits of the plain call.
+ *   [0]      : the value spx_proxval_l1_b2 returns for the same call; the same bits when both calls follow the same sequence
+ *              of calls on their contexts (the previous call's "trust region active" bit selects the speculative paths).
+ *   [1]      : sum over ALL i of q[i] * y[i], q AS PASSED (not q_scale * q); any q_scale, 0 and non-finite ones included.
+ *   [2]      : sum over ALL i of y[i]^2.
+ *   stats / stats_dev: host double[3] / DEVICE double[3], at least one non-NULL (SPX_ERR_INVALID_ARG otherwise).  stats == NULL:
+ *              the call only enqueues and is capturable exactly where spx_proxval_l1_b2 is (device pointers, one warm call,
+ *              vectors of one alignment).  stats != NULL: three doubles are read back, the call synchronises and is refused
+ *              under a capture (nothing launched).  Both given: the same bits in both.
+ *   spx_ctx_set_value_target has no effect on this call.  y == q returns SPX_ERR_INVALID_ARG.
+ *   n == 0: three zeros on the host, and three zeros stored to stats_dev by a kernel (no memset node).
+ *   Every sum is formed in a fixed order (static partition in every storing pass, partial sums exchanged in workgroup order): a
+ *   repeat gives the same bits, independent of which workgroup took which tile.  After an expired wait y is NaN as in
+ *   spx_prox_l1_b2 and the three sums are NaN.
+ * FUSED route -- the register-resident form, the LDS form and the 16-byte streaming form: y, xkn and the three sums come out
+ * of the ONE launch that stores y (streaming: 64 B/element, 40 with the trust region inactive; the register and LDS forms read
+ * q a second time at the store, they keep only sj + q_scale * q across the root find).
+ * COMPOSED route -- the 8-byte streaming form, whose fused kernel would spill more than its spx_proxval_l1_b2 twin (36 against
+ * 20 B per lane, profiles/b2_proxstep_kres.txt), and every form under tuning key 18 = 1: inside the same call and on
+ * the same stream, spx_proxval_l1_b2's launch unchanged (y and [0]), then the ONE streaming launch of the group operators'
+ * composed routes, which reads q, y, xk, sj, stores xkn and adds [1] and [2].  Same contract; y, xkn and [0] keep their bits.
+ * Float64 and device pointers only; no spx_host_* twin. */
+int spx_proxstep_l1_b2(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
+                       double lambda, double sigma, double delta, double chi_lambda, double q_scale, double* xkn,
+                       double* stats, double* stats_dev);
 
 /* ---- group operators -------------------------------------------------------------------- */
 /* Groups are contiguous index ranges (the reference's `idx` entries as UnitRanges / [:]):

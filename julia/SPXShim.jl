@@ -431,8 +431,26 @@ function prox_value!(y::DVec, ψ::ShiftedProximalOperators.ShiftedNormL1B2{Float
   return y, out[]
 end
 
+# prox! fused with the step statistics, ShiftedNormL1B2 (spx_proxstep_l1_b2): (y, h, qy, yy) with h as prox_value! returns it, qy
+# and yy over ALL i with the q that was passed; xkn receives (xk + sj) + y at every index.  `out`: the three sums stay on the
+# device, returns (y, out).  One launch on the register, LDS and 16-byte streaming forms; prox_value!'s launch plus one streaming
+# launch on vectors of mixed alignment.
+function prox_step!(y::DVec, ψ::ShiftedProximalOperators.ShiftedNormL1B2{Float64, <:DVec, <:DVec, <:DVec}, q::DVec, σ::Float64;
+                    q_scale::Float64 = 1.0, xkn::Union{Nothing, DVec} = nothing, out::Union{Nothing, DVec} = nothing)
+  n = length(ψ.xk)
+  (length(y) == n && length(q) == n && (xkn === nothing || length(xkn) == n)) || throw(BoundsError())
+  (out === nothing || length(out) >= 3) || throw(ArgumentError("out needs at least 3 elements"))
+  stats = zeros(Cdouble, 3)
+  sp = out === nothing ? pointer(stats) : Ptr{Cdouble}(C_NULL)
+  check(ccall((:spx_proxstep_l1_b2, libspx), Cint,
+              (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int64, Cdouble, Cdouble, Cdouble, Cdouble,
+               Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+              ctx(), dptr(y), dptr(q), dptr(ψ.xk), dptr(ψ.sj), n, ψ.λ, σ, ψ.Δ, ψ.χ.lambda, q_scale, dptr(xkn), sp, dptr(out)))
+  return out === nothing ? (y, stats[1], stats[2], stats[3]) : (y, out)
+end
+
 # ---------------------------------------------------------------------------------------------
-# ψ(y)                        src/ShiftedProximalOperators.jl:51-54, shiftedNormL1Box.jl:70-82 (idem L0Box, L½Box),
+# ψ(y)                      src/ShiftedProximalOperators.jl:51-54, shiftedNormL1Box.jl:70-82 (idem L0Box, L½Box),
 #                             shiftedIndBallL0BInf.jl:44-49, shiftedGroupNormL2Binf.jl:34-39
 # ---------------------------------------------------------------------------------------------
 # (ccall needs a literal symbol and a literal argument-type tuple: every entry point is spelled out)

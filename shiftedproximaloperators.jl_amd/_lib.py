@@ -57,6 +57,7 @@ SIGNATURES = {
     "spx_proxstep_group_l2": [_p, _p, _p, _p, _p, _i64, _p, _i64, _i64, _p, _d, _d, _p, ctypes.POINTER(_d), _p],
     "spx_proxstep_group_l2_binf": [_p, _p, _p, _p, _p, _i64, _p, _i64, _i64, _p, _d, _d, _d, _p, ctypes.POINTER(_d), _p],
     "spx_proxval_l1_b2": [_p, _p, _p, _p, _p, _i64, _d, _d, _d, _d, _d, ctypes.POINTER(_d)],
+    "spx_proxstep_l1_b2": [_p, _p, _p, _p, _p, _i64, _d, _d, _d, _d, _d, _p, ctypes.POINTER(_d), _p],
     "spx_iprox_l1": [_p, _p, _p, _p, _p, _p, _i64, _d, _int],
     "spx_iprox_l0": [_p, _p, _p, _p, _p, _p, _i64, _d, _int],
     "spx_iprox_l1_box": [_p, _p, _p, _p, _p, _p, _i64, _d, _p, _p, _d, _d, _p],

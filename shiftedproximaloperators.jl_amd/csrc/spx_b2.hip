@@ -17,6 +17,7 @@
 // lies inside are kept as candidates), the root is then found on aggregate + candidates, and the second pass stores y.
 // (Rounds 1-2: a host-driven loop and three streaming passes; both gone.)
 #include <cmath>
+#include <type_traits>
 
 #include "spx_common.hpp"
 
@@ -206,6 +207,23 @@ struct B2Val {
   double* out;    // device double that receives the value
 };
 __device__ __forceinline__ B2Val b2_val(B2Val v) { return v; }
+// STEP (spx_proxstep_l1_b2; only together with VALUE, and the pack then carries a B2Step): at every one of the five store sites the
+// lane that stores o to y[i] also stores v = (x + s) + o -- the v of the h term, the same bits -- to xkn[i] and adds q[i] * o (q AS
+// PASSED, not qs * q) and o * o to two more accumulators (hq, hy), reset wherever hv is.  The exit exchange then carries three
+// words (row 63, words 0..2 of every slot) and lane 0 of workgroup 0 stores {lambda * sum, <q, y>, <y, y>} to res_hdr
+// (SpxSyncHeader::b2_step, read back by the host) and / or res_dev (the caller's device double[3]).  The register-resident forms
+// keep only sj + qs * q: they read q AGAIN at the store site (behind a compiler barrier, so that the first load is not kept
+// alive in EPL more registers); the streaming visitors are handed the raw q pair next to the scaled one.
+struct B2Step : B2Val {
+  double* xkn;      // (xk + sj) + y, or NULL
+  double* res_hdr;  // SpxSyncHeader::b2_step, or NULL (device results only)
+  double* res_dev;  // the caller's device double[3], or NULL
+  int xvec;         // xkn is 16-byte aligned (VEC streaming form: else the xkn store alone drops to 8-byte stores)
+};
+__device__ __forceinline__ B2Val b2_val(B2Step v) { return static_cast<B2Val>(v); }
+template <class T>
+__device__ __forceinline__ B2Step b2_step(T) { return B2Step{}; }
+__device__ __forceinline__ B2Step b2_step(B2Step v) { return v; }
 // q as the prox reads it: qs * q, ONE rounded multiply (-ffp-contract=off: never contracted into the sum that follows); q itself
 // for the plain prox.  (The streaming forms and the tails.  The loads of the register-resident forms write the product out
 // under `if constexpr`: even an identity call there changes the code of the PLAIN kernel -- in the arm of the select it
@@ -215,18 +233,51 @@ __device__ __forceinline__ double b2_qs(double qs, double qv) { if constexpr (VA
 template <bool VALUE>
 __device__ __forceinline__ f64x2 b2_qs(double qs, f64x2 a) { if constexpr (VALUE) return f64x2{qs * a.x, qs * a.y}; else return a; }
 
-template <bool REG, int EPL, int THREADS, bool VEC, bool LDSX = false, bool VALUE = false, class... VA>
+template <bool REG, int EPL, int THREADS, bool VEC, bool LDSX = false, bool VALUE = false, bool STEP = false, class... VA>
 __global__ __launch_bounds__(THREADS) void k_b2_coop(double* y, const double* q, const double* xk, const double* sj, int64_t n,
                                                    double ls, double delta, double chil, unsigned long long* rows,
                                                    unsigned long long* clear_rows, int clear_g, SpxSyncHeader* hdr,
                                                    int can_spec, f64x2* cand, unsigned int cand_cap, VA... va) {
   static_assert(sizeof...(VA) == (VALUE ? 1 : 0), "VALUE: one B2Val behind the plain arguments");
+  static_assert(!STEP || VALUE, "STEP extends VALUE");
   double qsc = 1.0, vlam = 0.0, hv = 0.0;  // (VALUE) q_scale, lambda, this lane's sum of |(xk + sj) + y| over the pass that stores y
   double* vout = nullptr;
   if constexpr (VALUE) {
     const B2Val bv = b2_val(va...);
     qsc = bv.qs; vlam = bv.lambda; vout = bv.out;
   }
+  double hq = 0.0, hy = 0.0;  // (STEP) this lane's sums of q * y and y * y over the pass that stores y
+  double* sxkn = nullptr;
+  double* sres_hdr = nullptr;
+  double* sres_dev = nullptr;
+  bool sxvec = false;
+  if constexpr (STEP) {
+    const B2Step bs = b2_step(va...);
+    sxkn = bs.xkn; sres_hdr = bs.res_hdr; sres_dev = bs.res_dev; sxvec = bs.xvec != 0;
+  }
+  // (STEP) what goes with one stored element / pair: xkn and the two sums; qr = q as passed
+  auto step_one = [&](int64_t i, double qr, double x, double s, double o) {
+    if (sxkn != nullptr) sxkn[i] = (x + s) + o;
+    hq += qr * o;
+    hy += o * o;
+  };
+  auto step_pair = [&](int64_t p, f64x2 qr, f64x2 x, f64x2 s, f64x2 o) {
+    if (sxkn != nullptr) {
+      const f64x2 v{(x.x + s.x) + o.x, (x.y + s.y) + o.y};
+      if (VEC && sxvec) b2_st<true>(sxkn, p, v);
+      else b2_st<false>(sxkn, p, v);
+    }
+    hq += qr.x * o.x;
+    hq += qr.y * o.y;
+    hy += o.x * o.x;
+    hy += o.y * o.y;
+  };
+  // (STEP, register-resident forms) q[i] read again: the barrier keeps the compiler from holding on to the load that formed sj + qs * q
+  auto q_again = [&](int64_t i) -> double {
+    const double* qp = q;
+    asm volatile("" : "+s"(qp));
+    return qp[i];
+  };
   __shared__ double lds6[6][16];
   const int t = threadIdx.x;
   const int G = (int)gridDim.x;
@@ -254,7 +305,7 @@ __global__ __launch_bounds__(THREADS) void k_b2_coop(double* y, const double* q,
     else { x = X[k]; lo = LO[k]; hi = HI[k]; }
   };
   auto opaque = [](double v) -> double { if constexpr (LDSX) asm volatile("" : "+v"(v)); return v; };
-  auto opaque_i = [](int64_t v) -> int64_t { if constexpr (LDSX) asm volatile("" : "+v"(v)); return v; };
+  auto opaque_i = [](int64_t v) -> int64_t { if constexpr (LDSX || STEP) asm volatile("" : "+v"(v)); return v; };  // (STEP: four addresses per element)
   if constexpr (LDSX) {
 #pragma unroll
     for (int k0 = 0; k0 < EPL; k0 += 4) {  // twelve loads in flight per lane
@@ -343,7 +394,18 @@ __global__ __launch_bounds__(THREADS) void k_b2_coop(double* y, const double* q,
   // (VALUE) the exit exchange: hv of the pass whose stores stand -> the same total in every workgroup -> lambda * total.  Once
   // per launch, in row 63 whatever np has reached: the root loop may have used every row below it.
   auto publish = [&]() {
-    if constexpr (VALUE) {
+    if constexpr (STEP) {
+      double v[6] = {hv, hq, hy, 0.0, 0.0, 0.0};
+      np = kB2MaxPass - 1;
+      reduce(v, 7u);
+      if (blockIdx.x == 0 && t == 0) {
+        const bool nan = spx_poisoned(hdr);
+        const double qnan = __longlong_as_double(0x7ff8000000000000ll);
+        const double r0 = nan ? qnan : vlam * v[0], r1 = nan ? qnan : v[1], r2 = nan ? qnan : v[2];
+        if (sres_hdr != nullptr) { sres_hdr[0] = r0; sres_hdr[1] = r1; sres_hdr[2] = r2; }
+        if (sres_dev != nullptr) { sres_dev[0] = r0; sres_dev[1] = r1; sres_dev[2] = r2; }
+      }
+    } else if constexpr (VALUE) {
       double v[6] = {hv, 0.0, 0.0, 0.0, 0.0, 0.0};
       np = kB2MaxPass - 1;
       reduce(v, 1u);
@@ -373,6 +435,7 @@ __global__ __launch_bounds__(THREADS) void k_b2_coop(double* y, const double* q,
     double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     bad = false;
     if constexpr (VALUE) { if (store) hv = 0.0; }
+    if constexpr (STEP) { if (store) hq = hy = 0.0; }
     auto one = [&](double lo, double hi, double x) {
       const double pz = acc(lo, hi, x, r, v[0], v[1]);
       if (first) {
@@ -392,7 +455,14 @@ __global__ __launch_bounds__(THREADS) void k_b2_coop(double* y, const double* q,
           double x, lo, hi;
           elem(k, lsv, x, lo, hi);
           one(lo, hi, x);
-          if constexpr (VALUE) {
+          if constexpr (STEP) {
+            if (store) {
+              const double s = sj[i], o = outv(lo, hi, x, s, r, rinv);
+              y[i] = o;
+              hv += fabs((x + s) + o);
+              step_one(i, q_again(i), x, s, o);
+            }
+          } else if constexpr (VALUE) {
             if (store) {
               const double s = sj[i], o = outv(lo, hi, x, s, r, rinv);
               y[i] = o;
@@ -432,7 +502,7 @@ __global__ __launch_bounds__(THREADS) void k_b2_coop(double* y, const double* q,
   __shared__ unsigned int next_tile;
   unsigned int* const tile_ctr = reinterpret_cast<unsigned int*>(rows + (size_t)(kB2MaxPass - 1) * kB2Cols * kB2Words + 7);  // (row 63 is
   // never reached by a reduction; word 7 of a slot is never a partial sum; zeroed with the set like everything else in it)
-  auto stream = [&](auto&& visit_pair, bool dynamic = false) {  // visit_pair(valid, pair index, q pair (VALUE: scaled), xk pair, sj pair), called by every lane
+  auto stream = [&](auto&& visit_pair, bool dynamic = false) {  // visit_pair(valid, pair index, q pair (VALUE: scaled), xk pair, sj pair, q pair as passed), called by every lane
 #ifndef SPX_B2_VALUE_DYNAMIC_AB  // (A/B builds only, tools/b2_proxval_timing.py --ab-lib: what on-demand tiles would buy; hv then varies run to run)
     if constexpr (VALUE) dynamic = false;  // (the sums of a storing pass must not depend on who took which tile)
 #endif
@@ -470,7 +540,7 @@ __global__ __launch_bounds__(THREADS) void k_b2_coop(double* y, const double* q,
           const f64x2 a = *reinterpret_cast<const f64x2*>(wl + (0 * kB2DmaKiB + k) * 1024 + lane * 16);
           const f64x2 b = *reinterpret_cast<const f64x2*>(wl + (1 * kB2DmaKiB + k) * 1024 + lane * 16);
           const f64x2 d = *reinterpret_cast<const f64x2*>(wl + (2 * kB2DmaKiB + k) * 1024 + lane * 16);
-          visit_pair(i < n2, i, b2_qs<VALUE>(qsc, a), b, d);
+          visit_pair(i < n2, i, b2_qs<VALUE>(qsc, a), b, d, a);
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this tile's LDS reads are done before the next tile's loads are issued
         if (dynamic) {
@@ -495,7 +565,7 @@ __global__ __launch_bounds__(THREADS) void k_b2_coop(double* y, const double* q,
 #pragma unroll
       for (int k = 0; k < KP; ++k) {
         const int64_t i = tile * kTilePairs + t + k * THREADS;
-        visit_pair(i < n2, i, b2_qs<VALUE>(qsc, a[k]), b[k], d[k]);
+        visit_pair(i < n2, i, b2_qs<VALUE>(qsc, a[k]), b[k], d[k], a[k]);
       }
     };
     f64x2 a0[KP], b0[KP], d0[KP], a1[KP], b1[KP], d1[KP];
@@ -518,12 +588,19 @@ __global__ __launch_bounds__(THREADS) void k_b2_coop(double* y, const double* q,
   bool y_written = false;  // (!REG) an earlier pass of this launch stored y: the storing pass must then keep the static mapping
   auto store_pass = [&](double r, double rinv) {
     if constexpr (VALUE) hv = 0.0;
+    if constexpr (STEP) hq = hy = 0.0;
     if constexpr (!REG) {
       if (n2 > 0)
-        stream([&](bool valid, int64_t i, f64x2 a, f64x2 b, f64x2 d) {
+        stream([&](bool valid, int64_t i, f64x2 a, f64x2 b, f64x2 d, f64x2 ar) {
           if (valid) {
             const double sq0 = d.x + a.x, sq1 = d.y + a.y;
-            if constexpr (VALUE) {
+            if constexpr (STEP) {
+              const f64x2 o{outv(sq0 - ls, sq0 + ls, b.x, d.x, r, rinv), outv(sq1 - ls, sq1 + ls, b.y, d.y, r, rinv)};
+              b2_st<VEC>(y, i, o);
+              hv += fabs((b.x + d.x) + o.x);
+              hv += fabs((b.y + d.y) + o.y);
+              step_pair(i, ar, b, d, o);
+            } else if constexpr (VALUE) {
               const f64x2 o{outv(sq0 - ls, sq0 + ls, b.x, d.x, r, rinv), outv(sq1 - ls, sq1 + ls, b.y, d.y, r, rinv)};
               b2_st<VEC>(y, i, o);
               hv += fabs((b.x + d.x) + o.x);
@@ -535,7 +612,12 @@ __global__ __launch_bounds__(THREADS) void k_b2_coop(double* y, const double* q,
         }, !y_written && G > 1 && ntiles >= 8 * (int64_t)G);  // (a few tiles per workgroup: the hand-out costs more than it balances -- n = 6e6, 4 tiles each: 128 -> 135 us; n = 1.6e7, 10 each: 220 -> 212)
       if ((n & 1) && blockIdx.x == 0 && t == 0) {
         const double sql = sj[n - 1] + b2_qs<VALUE>(qsc, q[n - 1]);
-        if constexpr (VALUE) {
+        if constexpr (STEP) {
+          const double ql = q[n - 1], xl = xk[n - 1], sl = sj[n - 1], o = outv(sql - ls, sql + ls, xl, sl, r, rinv);
+          y[n - 1] = o;
+          hv += fabs((xl + sl) + o);
+          step_one(n - 1, ql, xl, sl, o);
+        } else if constexpr (VALUE) {
           const double xl = xk[n - 1], sl = sj[n - 1], o = outv(sql - ls, sql + ls, xl, sl, r, rinv);
           y[n - 1] = o;
           hv += fabs((xl + sl) + o);
@@ -544,13 +626,20 @@ __global__ __launch_bounds__(THREADS) void k_b2_coop(double* y, const double* q,
         }
       }
     } else {
+      int64_t ntv = 0;
+      if constexpr (STEP) ntv = opaque_i(NT);
 #pragma unroll
       for (int k = 0; k < EPL; ++k) {
-        const int64_t i = gtid + (int64_t)k * NT;
+        const int64_t i = gtid + (int64_t)k * (STEP ? ntv : NT);  // (the plain and VALUE kernels: the expression they always had)
         if (i < n) {
           double x, lo, hi;
           elem(k, ls, x, lo, hi);
-          if constexpr (VALUE) {
+          if constexpr (STEP) {
+            const double s = sj[i], o = outv(lo, hi, x, s, r, rinv);
+            y[i] = o;
+            hv += fabs((x + s) + o);
+            step_one(i, q_again(i), x, s, o);
+          } else if constexpr (VALUE) {
             const double s = sj[i], o = outv(lo, hi, x, s, r, rinv);
             y[i] = o;
             hv += fabs((x + s) + o);
@@ -568,6 +657,7 @@ __global__ __launch_bounds__(THREADS) void k_b2_coop(double* y, const double* q,
     bad = false;
     if (store) y_written = true;
     if constexpr (VALUE) { if (store) hv = 0.0; }
+    if constexpr (STEP) { if (store) hq = hy = 0.0; }
     if constexpr (!REG) {
       auto one = [&](double qv, double x, double s) -> double {
         const double sq = s + qv;
@@ -582,15 +672,21 @@ __global__ __launch_bounds__(THREADS) void k_b2_coop(double* y, const double* q,
         }
       };
       if (n2 > 0)
-        stream([&](bool valid, int64_t i, f64x2 a, f64x2 b, f64x2 d) {
+        stream([&](bool valid, int64_t i, f64x2 a, f64x2 b, f64x2 d, f64x2 ar) {
           if (valid) {
             const f64x2 o{one(a.x, b.x, d.x), one(a.y, b.y, d.y)};
-            if (store) b2_st<VEC>(y, i, o);
+            if (store) {
+              b2_st<VEC>(y, i, o);
+              if constexpr (STEP) step_pair(i, ar, b, d, o);
+            }
           }
         });
       if ((n & 1) && blockIdx.x == 0 && t == 0) {
         const double o = one(b2_qs<VALUE>(qsc, q[n - 1]), xk[n - 1], sj[n - 1]);
-        if (store) y[n - 1] = o;
+        if (store) {
+          y[n - 1] = o;
+          if constexpr (STEP) step_one(n - 1, q[n - 1], xk[n - 1], sj[n - 1], o);
+        }
       }
     }
     if (bad) v[0] = __longlong_as_double(0x7ff8000000000000ll);
@@ -624,11 +720,28 @@ __global__ __launch_bounds__(THREADS) void k_b2_coop(double* y, const double* q,
         }
       };
       if constexpr (VALUE) hv = 0.0;
+      if constexpr (STEP) hq = hy = 0.0;
       if (n2 > 0)
-        stream([&](bool valid, int64_t i, f64x2 a, f64x2 b, f64x2 d) {
-          if (valid) b2_st<VEC>(y, i, f64x2{one0(a.x, b.x, d.x), one0(a.y, b.y, d.y)});
+        stream([&](bool valid, int64_t i, f64x2 a, f64x2 b, f64x2 d, f64x2 ar) {
+          if constexpr (STEP) {
+            if (valid) {
+              const f64x2 o{one0(a.x, b.x, d.x), one0(a.y, b.y, d.y)};
+              b2_st<VEC>(y, i, o);
+              step_pair(i, ar, b, d, o);
+            }
+          } else {
+            if (valid) b2_st<VEC>(y, i, f64x2{one0(a.x, b.x, d.x), one0(a.y, b.y, d.y)});
+          }
         }, true);
-      if ((n & 1) && blockIdx.x == 0 && t == 0) y[n - 1] = one0(b2_qs<VALUE>(qsc, q[n - 1]), xk[n - 1], sj[n - 1]);
+      if constexpr (STEP) {
+        if ((n & 1) && blockIdx.x == 0 && t == 0) {
+          const double o = one0(b2_qs<VALUE>(qsc, q[n - 1]), xk[n - 1], sj[n - 1]);
+          y[n - 1] = o;
+          step_one(n - 1, q[n - 1], xk[n - 1], sj[n - 1], o);
+        }
+      } else {
+        if ((n & 1) && blockIdx.x == 0 && t == 0) y[n - 1] = one0(b2_qs<VALUE>(qsc, q[n - 1]), xk[n - 1], sj[n - 1]);
+      }
       // (one wavefront per workgroup issues the write-back, after all of the workgroup's stores have left: a fence per
       //  wavefront -- 4096 L2 write-back scans -- made the pass slower than the static one)
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -737,15 +850,22 @@ __global__ __launch_bounds__(THREADS) void k_b2_coop(double* y, const double* q,
     };
     if (store_first) y_written = true;
     if constexpr (VALUE) hv = 0.0;
+    if constexpr (STEP) hq = hy = 0.0;
     if (n2 > 0)
-      stream([&](bool valid, int64_t i, f64x2 a, f64x2 b, f64x2 d) {
+      stream([&](bool valid, int64_t i, f64x2 a, f64x2 b, f64x2 d, f64x2 ar) {
         const f64x2 o{one(valid, a.x, b.x, d.x), one(valid, a.y, b.y, d.y)};
-        if (store_first && valid) b2_st<VEC>(y, i, o);
+        if (store_first && valid) {
+          b2_st<VEC>(y, i, o);
+          if constexpr (STEP) step_pair(i, ar, b, d, o);
+        }
       });
     if (n & 1) {  // the odd last element rides with wavefront 0 of workgroup 0 (all of its lanes call `one`)
       if (blockIdx.x == 0 && t < 64) {
         const double o = one(t == 0, b2_qs<VALUE>(qsc, q[n - 1]), xk[n - 1], sj[n - 1]);
-        if (store_first && t == 0) y[n - 1] = o;
+        if (store_first && t == 0) {
+          y[n - 1] = o;
+          if constexpr (STEP) step_one(n - 1, q[n - 1], xk[n - 1], sj[n - 1], o);
+        }
       }
     }
     if (bad) v[0] = __longlong_as_double(0x7ff8000000000000ll);
@@ -943,22 +1063,58 @@ SPX_EXPORT int spx_obj_l1_b2(spx_ctx* ctx, const double* y, const double* xk, co
 
 namespace {
 
-// the kernel of one form; VALUE: with the B2Val argument behind the plain ones
-template <bool REG, int EPL, int THREADS, bool VEC, bool LDSX, bool VALUE>
+// the kernel of one form; VALUE: with the B2Val argument behind the plain ones; STEP: with a B2Step there
+template <bool REG, int EPL, int THREADS, bool VEC, bool LDSX, bool VALUE, bool STEP = false>
 constexpr auto b2_kernel() {
-  if constexpr (VALUE) return &k_b2_coop<REG, EPL, THREADS, VEC, LDSX, true, B2Val>;
+  if constexpr (STEP) return &k_b2_coop<REG, EPL, THREADS, VEC, LDSX, true, true, B2Step>;
+  else if constexpr (VALUE) return &k_b2_coop<REG, EPL, THREADS, VEC, LDSX, true, false, B2Val>;
   else return &k_b2_coop<REG, EPL, THREADS, VEC, LDSX, false>;
 }
 
+// spx_proxstep_l1_b2: which forms have a fused STEP kernel (profiles/b2_proxstep_kres.txt: the rule is "no more scratch than the
+// VALUE twin of the form"); the others -- and every form under tuning key 18 = 1 -- take the composed route of the same call.
+enum B2Form { kB2FormReg = 0, kB2FormLds = 1, kB2FormVec = 2, kB2Form8 = 3 };
+#ifndef SPX_B2_STEP_FUSED  // (tools/kres.sh compiles all four STEP kernels for the table: -DSPX_B2_STEP_FUSED=1,1,1,1)
+#define SPX_B2_STEP_FUSED 1, 1, 1, 0
+#endif
+constexpr bool kB2StepFused[4] = {SPX_B2_STEP_FUSED};
+// the kernel of form F and its lanes per workgroup
+template <int F, bool VALUE, bool STEP>
+constexpr auto b2_form_kernel() {
+  if constexpr (F == kB2FormLds) return b2_kernel<true, kB2Epl, 1024, true, true, VALUE, STEP>();
+  else if constexpr (F == kB2FormReg) return b2_kernel<true, kB2Epl, kB2RegThreads, true, false, VALUE, STEP>();
+  else if constexpr (F == kB2FormVec) return b2_kernel<false, 1, 1024, true, false, VALUE, STEP>();
+  else return b2_kernel<false, 1, 1024, false, false, VALUE, STEP>();
+}
+constexpr int b2_form_threads(int form) { return form == kB2FormReg ? kB2RegThreads : 1024; }
+template <class Fn>
+void b2_with_form(B2Form form, Fn&& fn) {
+  switch (form) {
+    case kB2FormReg: fn(std::integral_constant<int, kB2FormReg>{}); break;
+    case kB2FormLds: fn(std::integral_constant<int, kB2FormLds>{}); break;
+    case kB2FormVec: fn(std::integral_constant<int, kB2FormVec>{}); break;
+    default: fn(std::integral_constant<int, kB2Form8>{}); break;
+  }
+}
+struct B2StepArgs {
+  double* xkn;
+  double* stats;
+  double* stats_dev;
+};
+int b2_step_composed(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n, double lambda,
+                     double sigma, double delta, double chi_lambda, double q_scale, const B2StepArgs& st);
+
 // One host body for spx_prox_l1_b2 (VALUE = false: q_scale and value are not looked at) and spx_proxval_l1_b2.  The form and
 // the grid are chosen from the PLAIN kernels' residency in both: y's bits depend on the grid (the partition of every sum).
-template <bool VALUE>
+// STEP (spx_proxstep_l1_b2, st != NULL; the arguments were checked by the entry point, n > 0): the same choice of form and grid
+// -- xkn takes no part in it and does not change can_spec -- and then either the STEP kernel of the form or the composed route.
+template <bool VALUE, bool STEP = false>
 int run_b2(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n, double lambda, double sigma,
-           double delta, double chi_lambda, double q_scale, double* value) {
-  if constexpr (VALUE) SPX_REQUIRE(value != nullptr, "value is NULL");
+           double delta, double chi_lambda, double q_scale, double* value, const B2StepArgs* st = nullptr) {
+  if constexpr (VALUE && !STEP) SPX_REQUIRE(value != nullptr, "value is NULL");
   int rc = spx_check_common(ctx, y, q, xk, sj, n);
   if (rc) return rc;
-  if constexpr (VALUE) {
+  if constexpr (VALUE && !STEP) {
     if (!ctx->value_target) {  // (refused before anything is enqueued)
       const int rcc = spx_require_not_capturing(ctx, "returning the value to the host");
       if (rcc) return rcc;
@@ -1000,14 +1156,21 @@ int run_b2(spx_ctx* ctx, double* y, const double* q, const double* xk, const dou
     if (gg > g) g = gg;
   }
   if (g < 1) g = 1;
+  const B2Form form = ldsx ? kB2FormLds : reg ? kB2FormReg : vec ? kB2FormVec : kB2Form8;
+  if constexpr (STEP) {
+    if (ctx->tune_b2_step_compose || !kB2StepFused[form])
+      return b2_step_composed(ctx, y, q, xk, sj, n, lambda, sigma, delta, chi_lambda, q_scale, *st);
+  }
   if constexpr (VALUE) {
     // FUSED on all four forms: the VALUE kernel of the form runs with the grid chosen above (same LDS, same lanes per workgroup as
     // its plain twin: resident wherever that one is)
-    const int64_t cap_val =
-        ldsx  ? spx_resident_cap(ctx, reinterpret_cast<const void*>(b2_kernel<true, kB2Epl, 1024, true, true, true>()), 1024, 0)
-        : reg ? spx_resident_cap(ctx, reinterpret_cast<const void*>(b2_kernel<true, kB2Epl, kB2RegThreads, true, false, true>()), kB2RegThreads, 0)
-        : vec ? spx_resident_cap(ctx, reinterpret_cast<const void*>(b2_kernel<false, 1, 1024, true, false, true>()), 1024, 0)
-              : spx_resident_cap(ctx, reinterpret_cast<const void*>(b2_kernel<false, 1, 1024, false, false, true>()), 1024, 0);
+    // (a form without a fused STEP kernel has left through b2_step_composed above: its STEP kernel is never instantiated)
+    int64_t cap_val = 0;
+    b2_with_form(form, [&](auto fc) {
+      constexpr int F = decltype(fc)::value;
+      if constexpr (!STEP || kB2StepFused[F])
+        cap_val = spx_resident_cap(ctx, reinterpret_cast<const void*>(b2_form_kernel<F, true, STEP>()), b2_form_threads(F), 0);
+    });
     if (cap_val < 1) return SPX_ERR_INTERNAL;  // (message set by spx_resident_cap)
     if (cap_val < g) {
       spx_set_error("internal error: the fused ShiftedNormL1B2 kernel is resident with %lld workgroups, the prox takes %lld",
@@ -1051,7 +1214,16 @@ int run_b2(spx_ctx* ctx, double* y, const double* q, const double* xk, const dou
   {
     SpxCoopLaunchGuard guard(ctx);
     auto launch = [&](auto kern, int threads) {
-      if constexpr (VALUE)
+      if constexpr (STEP) {
+        B2Step bs{};
+        static_cast<B2Val&>(bs) = B2Val{q_scale, lambda, nullptr};
+        bs.xkn = st->xkn;
+        bs.res_hdr = st->stats ? hdr->b2_step : nullptr;
+        bs.res_dev = st->stats_dev;
+        bs.xvec = spx_aligned16(st->xkn) ? 1 : 0;
+        hipLaunchKernelGGL(kern, dim3((unsigned)g), dim3(threads), 0, ctx->stream, y, q, xk, sj, n, ls, delta, chi_lambda, rows,
+                           clear_rows, clear_g, hdr, can_spec, cand, cand_cap, bs);
+      } else if constexpr (VALUE)
         hipLaunchKernelGGL(kern, dim3((unsigned)g), dim3(threads), 0, ctx->stream, y, q, xk, sj, n, ls, delta, chi_lambda, rows,
                            clear_rows, clear_g, hdr, can_spec, cand, cand_cap,
                            B2Val{q_scale, lambda, ctx->value_target ? ctx->value_target : &hdr->b2_value});
@@ -1059,10 +1231,10 @@ int run_b2(spx_ctx* ctx, double* y, const double* q, const double* xk, const dou
         hipLaunchKernelGGL(kern, dim3((unsigned)g), dim3(threads), 0, ctx->stream, y, q, xk, sj, n, ls, delta, chi_lambda, rows,
                            clear_rows, clear_g, hdr, can_spec, cand, cand_cap);
     };
-    if (ldsx) launch(b2_kernel<true, kB2Epl, 1024, true, true, VALUE>(), 1024);
-    else if (reg) launch(b2_kernel<true, kB2Epl, kB2RegThreads, true, false, VALUE>(), kB2RegThreads);
-    else if (vec) launch(b2_kernel<false, 1, 1024, true, false, VALUE>(), 1024);
-    else launch(b2_kernel<false, 1, 1024, false, false, VALUE>(), 1024);
+    b2_with_form(form, [&](auto fc) {
+      constexpr int F = decltype(fc)::value;
+      if constexpr (!STEP || kB2StepFused[F]) launch(b2_form_kernel<F, VALUE, STEP>(), b2_form_threads(F));
+    });
   }
   if (graph_safe) {  // both sets count as used by the widest grid from here on (a replay may have touched set 0)
     ctx->track.b2_dirty_g[0] = ctx->track.b2_dirty_g[1] = kB2Cols;
@@ -1072,7 +1244,12 @@ int run_b2(spx_ctx* ctx, double* y, const double* q, const double* xk, const dou
     ctx->track.b2_set = other;
   }
   SPX_LAUNCH_CHECK();
-  if constexpr (VALUE) {
+  if constexpr (STEP) {
+    if (st->stats == nullptr) return SPX_OK;  // device results only: the call returns after enqueueing
+    SPX_HIP(hipMemcpyAsync(st->stats, hdr->b2_step, 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    SPX_HIP(hipStreamSynchronize(ctx->stream));
+    return SPX_OK;
+  } else if constexpr (VALUE) {
     if (ctx->value_target) {  // device-resident value: nothing is read back, the call returns after enqueueing
       *value = std::nan("");
       return SPX_OK;
@@ -1094,4 +1271,51 @@ SPX_EXPORT int spx_prox_l1_b2(spx_ctx* ctx, double* y, const double* q, const do
 SPX_EXPORT int spx_proxval_l1_b2(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
                                  double lambda, double sigma, double delta, double chi_lambda, double q_scale, double* value) {
   return run_b2<true>(ctx, y, q, xk, sj, n, lambda, sigma, delta, chi_lambda, q_scale, value);
+}
+
+namespace {
+
+// The composed route of spx_proxstep_l1_b2 (forms whose STEP kernel would spill more than their VALUE twin; every form under
+// tuning key 18 = 1): the unchanged run_b2<VALUE> -- y and h, h kept on the device in SpxSyncHeader::b2_step[0] -- then the
+// streaming launch the group operators' composed routes end in (spx_step_tail_*, spx_group.hip) for xkn and the two sums, which
+// also hands h on to the result slots.  Its workspace is reserved before anything is enqueued.
+int b2_step_composed(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n, double lambda,
+                     double sigma, double delta, double chi_lambda, double q_scale, const B2StepArgs& st) {
+  const SpxStepTail tail = spx_step_tail_plan(ctx, y, q, xk, sj, st.xkn, n);
+  int rc = spx_ws_reserve(ctx, tail.bytes);
+  if (rc) return rc;
+  rc = spx_sync_ready(ctx);
+  if (rc) return rc;
+  SpxSyncHeader* hdr = spx_sync_header(ctx);
+  double* const caller_target = ctx->value_target;  // (does not apply to this call: h goes to the library's own word)
+  ctx->value_target = &hdr->b2_step[0];
+  double unused;
+  rc = run_b2<true>(ctx, y, q, xk, sj, n, lambda, sigma, delta, chi_lambda, q_scale, &unused);
+  ctx->value_target = caller_target;
+  if (rc) return rc;
+  return spx_step_tail_run(ctx, tail, q, y, xk, sj, st.xkn, n, &hdr->b2_step[0], st.stats, st.stats_dev);
+}
+
+}  // namespace
+
+// prox! fused with the step statistics (include/spx.h): fused in the launch that stores y where the STEP kernel of the form
+// fits its registers, composed inside the same call elsewhere (kB2StepFused).
+SPX_EXPORT int spx_proxstep_l1_b2(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
+                                  double lambda, double sigma, double delta, double chi_lambda, double q_scale, double* xkn,
+                                  double* stats, double* stats_dev) {
+  int rc = spx_check_common(ctx, y, q, xk, sj, n);
+  if (rc) return rc;
+  SPX_REQUIRE(stats != nullptr || stats_dev != nullptr, "stats and stats_dev are both NULL");
+  SPX_REQUIRE(y == nullptr || y != q, "y aliases q (<q, y> of an overwritten q)");
+  if (xkn != nullptr) SPX_REQUIRE(xkn != y && xkn != q && xkn != xk && xkn != sj, "xkn is one of the other vectors");
+  // the host copy synchronises: refused under a capture before anything is enqueued
+  if (stats != nullptr) { rc = spx_require_not_capturing(ctx, "returning the step statistics to the host (pass stats = NULL)"); if (rc) return rc; }
+  if (stats) stats[0] = stats[1] = stats[2] = 0.0;
+  if (n == 0) {
+    if (stats_dev == nullptr) return SPX_OK;
+    SPX_ON_DEVICE(ctx);
+    return spx_zero_async(ctx, stats_dev, 3 * sizeof(double));  // (a kernel, not a memset node)
+  }
+  const B2StepArgs st{xkn, stats, stats_dev};
+  return run_b2<true, true>(ctx, y, q, xk, sj, n, lambda, sigma, delta, chi_lambda, q_scale, nullptr, &st);
 }

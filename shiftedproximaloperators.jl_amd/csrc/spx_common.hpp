@@ -74,6 +74,8 @@ struct spx_ctx {
                                    //         grid (0 = default, see group_route_general in spx_group.hip); an A/B knob
   int tune_fewer_launches = 1;     // key 17: psi(y) in one launch (the last workgroup finishes: spx_fin_ticket) and the Binf group operators without the
                                    //         zero-fill launch of their deferred list (count words that alternate); 0 = the launches of rounds 1-3
+  int tune_b2_step_compose = 0;    // key 18: spx_proxstep_l1_b2 takes its composed route (the VALUE launch + one streaming launch) on every form;
+                                   //         0 = fused wherever the form has a STEP kernel.  An A/B knob: y, xkn and [0] keep their bits
   int tune_force_grid = 0;         // key 100, test builds only (-DSPX_TEST_HOOKS): launch the one-launch top-r with THIS many workgroups,
                                    //          residency or not -- the planted fault behind tests/test_gpu_robustness.py
   int tune_force_team = 0;         // key 102, test builds only: the last workgroup of every team of k_group_team arrives late (spx_group_team.hip)
@@ -131,6 +133,21 @@ int spx_group_team_plan(spx_ctx* ctx, bool binf, const double* y, const double* 
 int spx_group_team_launch(spx_ctx* ctx, bool binf, double* y, const double* q, const double* xk, const double* sj, int64_t n,
                           const int64_t* offsets, int64_t gsize, int64_t ngroups, const double* lambda, double sigma,
                           double delta);
+
+// The streaming launch that the composed routes of spx_proxstep_group_* and spx_proxstep_l1_b2 end in (spx_group.hip): after a
+// value call has stored y and left h in the device double *h, ONE launch stores xkn = (xk + sj) + y (xkn may be NULL) and forms
+// <q, y> and <y, y>; its last workgroup stores {*h, <q, y>, <y, y>} to stats_dev and / or reads them back to stats.
+// plan: the launch shape and the workspace it needs from offset 0 of spx_ctx::ws (reserve it before the call's first launch; the
+// value call may use the same bytes, it has finished with them on the stream before the tail runs).
+struct SpxStepTail {
+  bool vec;       // 16-byte accesses: every vector, xkn included, is 16-byte aligned
+  int64_t blocks;
+  size_t bytes;
+};
+SpxStepTail spx_step_tail_plan(spx_ctx* ctx, const double* y, const double* q, const double* xk, const double* sj, const double* xkn,
+                               int64_t n);
+int spx_step_tail_run(spx_ctx* ctx, const SpxStepTail& tail, const double* q, const double* y, const double* xk, const double* sj,
+                      double* xkn, int64_t n, const double* h, double* stats, double* stats_dev);
 
 // Two launches that synchronise inside themselves must not run side by side on one device: each would hold CUs while it
 // waits for workgroups of its own that cannot be placed.  Contexts on different streams are therefore chained through one
@@ -324,7 +341,9 @@ struct SpxSyncHeader {
   int fin_flag;               // ... and their infeasibility bits; zero between launches
   double b2_value;            // spx_proxval_l1_b2 without a device value target: the launch stores h here, the host reads it back
   double grp_step_h;          // spx_proxstep_group_*, composed routes: h of the value call, picked up by the tail launch (spx_group.hip)
-  int pad[18];
+  double b2_step[3];          // spx_proxstep_l1_b2 with a host result: the launch stores {h, <q, y>, <y, y>} here, the host reads them back
+                              // (composed route: [0] is h of the value call, picked up by the tail launch)
+  int pad[12];
   unsigned int fin_class[kSpxBarSplit * 32];  // first-level tickets, one 128-byte line each
 };
 static_assert(sizeof(SpxSyncHeader) == 2 * kSpxBarSplit * 32 * 4 + 128 + kSpxBarSplit * 32 * 4, "SpxSyncHeader layout");

@@ -1361,6 +1361,36 @@ __global__ __launch_bounds__(256) void k_group_step_tail(const double* q, const 
   gval_finish(acc, false, gv);
 }
 
+// [GroupStepWs | three planes of partials] of the tail launch (spx_common.hpp: shared with spx_proxstep_l1_b2)
+SpxStepTail spx_step_tail_plan(spx_ctx* ctx, const double* y, const double* q, const double* xk, const double* sj, const double* xkn,
+                               int64_t n) {
+  SpxStepTail tail;
+  tail.vec = spx_aligned16(y) && spx_aligned16(q) && spx_aligned16(xk) && spx_aligned16(sj) && spx_aligned16(xkn);
+  const int64_t work = tail.vec ? (n + 1) / 2 : n;
+  tail.blocks = (work + 255) / 256;
+  if (tail.blocks > (int64_t)ctx->num_cu * 8) tail.blocks = (int64_t)ctx->num_cu * 8;
+  tail.bytes = sizeof(GroupStepWs) + (size_t)tail.blocks * 3 * sizeof(double) + 256;
+  return tail;
+}
+
+int spx_step_tail_run(spx_ctx* ctx, const SpxStepTail& tail, const double* q, const double* y, const double* xk, const double* sj,
+                      double* xkn, int64_t n, const double* h, double* stats, double* stats_dev) {
+  SPX_ON_DEVICE(ctx);
+  GroupStep gv{};
+  GroupStepWs* sws = reinterpret_cast<GroupStepWs*>(ctx->ws);
+  static_cast<GroupVal&>(gv) = GroupVal{1.0, reinterpret_cast<double*>(sws + 1), nullptr, (int)tail.blocks, false, spx_sync_header(ctx), nullptr, nullptr, nullptr, nullptr, 64};
+  gv.xkn = xkn;
+  gv.stats_dev = stats_dev;
+  gv.sws = sws;
+  if (tail.vec) hipLaunchKernelGGL(k_group_step_tail<true>, dim3((unsigned)tail.blocks), dim3(256), 0, ctx->stream, q, y, xk, sj, xkn, n, h, gv);
+  else hipLaunchKernelGGL(k_group_step_tail<false>, dim3((unsigned)tail.blocks), dim3(256), 0, ctx->stream, q, y, xk, sj, xkn, n, h, gv);
+  SPX_LAUNCH_CHECK();
+  if (stats == nullptr) return SPX_OK;  // device results only: the call returns after enqueueing
+  SPX_HIP(hipMemcpyAsync(stats, sws->result, 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  SPX_HIP(hipStreamSynchronize(ctx->stream));
+  return SPX_OK;
+}
+
 template <bool BINF>
 static int run_group_step(const GroupCall& c, double q_scale, double* xkn, double* stats, double* stats_dev) {
   GroupRoute route;
@@ -1380,12 +1410,9 @@ static int run_group_step(const GroupCall& c, double q_scale, double* xkn, doubl
     return spx_zero_async(ctx, stats_dev, 3 * sizeof(double));  // (a kernel, not a memset node)
   }
   if (route == GroupRoute::Reg && c.offsets == nullptr) return group_route_reg<BINF, true, true>(c, q_scale, stats, {xkn, stats_dev});
-  // composed: [GroupStepWs | three planes of partials] of the tail launch, reserved before anything is enqueued
-  const bool vec = spx_aligned16(c.y) && spx_aligned16(c.q) && spx_aligned16(c.xk) && spx_aligned16(c.sj) && spx_aligned16(xkn);
-  const int64_t work = vec ? (c.n + 1) / 2 : c.n;
-  int64_t blocks = (work + 255) / 256;
-  if (blocks > (int64_t)ctx->num_cu * 8) blocks = (int64_t)ctx->num_cu * 8;
-  rc = spx_ws_reserve(ctx, sizeof(GroupStepWs) + (size_t)blocks * 3 * sizeof(double) + 256);
+  // composed: the workspace of the tail launch is reserved before anything is enqueued
+  const SpxStepTail tail = spx_step_tail_plan(ctx, c.y, c.q, c.xk, c.sj, xkn, c.n);
+  rc = spx_ws_reserve(ctx, tail.bytes);
   if (rc) return rc;
   rc = spx_sync_ready(ctx);
   if (rc) return rc;
@@ -1396,20 +1423,7 @@ static int run_group_step(const GroupCall& c, double q_scale, double* xkn, doubl
   rc = run_group_val<BINF>(c, q_scale, &unused);
   ctx->value_target = caller_target;
   if (rc) return rc;
-  SPX_ON_DEVICE(ctx);
-  GroupStep gv{};
-  GroupStepWs* sws = reinterpret_cast<GroupStepWs*>(ctx->ws);
-  static_cast<GroupVal&>(gv) = GroupVal{1.0, reinterpret_cast<double*>(sws + 1), nullptr, (int)blocks, false, hdr, nullptr, nullptr, nullptr, nullptr, 64};
-  gv.xkn = xkn;
-  gv.stats_dev = stats_dev;
-  gv.sws = sws;
-  if (vec) hipLaunchKernelGGL(k_group_step_tail<true>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, c.q, (const double*)c.y, c.xk, c.sj, xkn, c.n, (const double*)&hdr->grp_step_h, gv);
-  else hipLaunchKernelGGL(k_group_step_tail<false>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, c.q, (const double*)c.y, c.xk, c.sj, xkn, c.n, (const double*)&hdr->grp_step_h, gv);
-  SPX_LAUNCH_CHECK();
-  if (stats == nullptr) return SPX_OK;  // device results only: the call returns after enqueueing
-  SPX_HIP(hipMemcpyAsync(stats, sws->result, 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  SPX_HIP(hipStreamSynchronize(ctx->stream));
-  return SPX_OK;
+  return spx_step_tail_run(ctx, tail, c.q, c.y, c.xk, c.sj, xkn, c.n, &hdr->grp_step_h, stats, stats_dev);
 }
 
 SPX_EXPORT int spx_proxstep_group_l2(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,

@@ -923,6 +923,39 @@ def group_prox_step(ψ, q, σ, q_scale=1.0, xkn=None, out=None):
     return group_prox_step_bang(ψ.sol, ψ, q, σ, q_scale, xkn, out)
 
 
+def b2_prox_step_bang(y, ψ, q, σ, q_scale=1.0, xkn=None, out=None):
+    """prox_step_bang for ShiftedNormL1B2, the ℓ1 regulariser inside an ℓ2 trust region (spx_proxstep_l1_b2):
+    prox!(y, ψ, q_scale .* q, σ) and the step statistics of a trust-region iteration in one library call,
+
+        h  = λ · Σ over ALL i of |(xk[i] + sj[i]) + y[i]|   -- the value prox_value returns (the h part of ψ(y))
+        qy = Σ over ALL i of q[i] · y[i]   -- with the UNSCALED q as passed, not q_scale · q
+        yy = Σ over ALL i of y[i]²
+        xkn[i] = (xk[i] + sj[i]) + y[i] for every i (a device vector like ψ.xk that is none of y, q, ψ.xk, ψ.sj; None:
+                 not stored)
+
+    y has the bits of prox!(y, ψ, q_scale .* q, σ).  Where the fused kernel of a form fits its registers everything comes out
+    of the one launch that stores y; the other forms run prox_value's launch followed by one streaming launch inside the same
+    call -- the same results, not the same speed.  Arguments, `out` and the return shapes are prox_step_bang's: (y, h, qy, yy)
+    as Python floats, or (y, out) with a float64 device tensor `out` of at least 3 elements (nothing read back, capturable
+    into a graph once the same call has run before).  `device_values` does not apply.  y must not be q.  Device Float64
+    vectors only: host ψ, Float32 and every other ψ raise TypeError."""
+    if not isinstance(ψ, ShiftedNormL1B2):
+        raise TypeError("b2_prox_step is available for ShiftedNormL1B2 (the separable operators: prox_step; the group "
+                        "operators: group_prox_step)")
+    if _is_host(ψ.xk) or ψ.xk.dtype != torch.float64:
+        raise TypeError("b2_prox_step needs device Float64 vectors")
+
+    def call(L, ctx, n, tail):
+        return L.spx_proxstep_l1_b2(ctx, _ptr(y), _ptr(q), _ptr(ψ.xk), _ptr(ψ.sj), n, ψ.h.lam, float(σ), ψ.Δ, ψ.χ.lam, *tail)
+
+    return _prox_step_call("b2_prox_step", y, ψ, q, q_scale, xkn, out, call)
+
+
+def b2_prox_step(ψ, q, σ, q_scale=1.0, xkn=None, out=None):
+    """b2_prox_step_bang(ψ.sol, ψ, q, σ, ...): (ψ.sol, h, qy, yy), or (ψ.sol, out) with a device `out`"""
+    return b2_prox_step_bang(ψ.sol, ψ, q, σ, q_scale, xkn, out)
+
+
 def iprox_bang(y, ψ, g, d, check=True):
     """iprox!(y, ψ, g, d): y <- argmin_t ½ tᵀDt + gᵀt + ψ(t), D = diag(d); returns y.  Defined for ShiftedNormL1/L0 and
     their Box forms (as in the reference).  The unboxed forms assert d .> 0 like the reference (`check=True`
