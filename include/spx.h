@@ -265,7 +265,22 @@ int spx_obj_group_l2_binf_f32(spx_ctx* ctx, const float* y, const float* xk, con
  * lambda * sum sqrt|v| (src/ShiftedProximalOperators.jl:51-54, Box forms src/shiftedNormL1Box.jl:70-82 without the
  * feasibility scan: a prox result lies inside the box by construction).  The prox is taken at q_scale * q[i], formed on
  * the fly (R2's `mnu_grad .= -nu .* grad` without the extra pass; pass 1.0 for q itself; bit-identical to scaling q
- * beforehand).  Synchronous: *value is written on the host. */
+ * beforehand).  Synchronous: *value is written on the host.
+ * NON-FINITE DATA (NaN, +-Inf, subnormals in q, xk or sj) -- the contract of every spx_proxval_* and spx_proxstep_* entry
+ * point, the group forms and the ShiftedNormL1B2 forms below included (tests/test_gpu_nonfinite.py):
+ *   y     : as spx_prox_X on the same data -- the same bits, NaN where that is NaN; xkn = (xk + sj) + y of that y.
+ *   sums  : *value and the three sums of spx_proxstep_* follow IEEE addition of their terms -- the terms formed from the STORED
+ *           y and, for [1], the q that was passed -- whatever the order they are added in: NaN if a term is NaN or if +Inf and
+ *           -Inf both occur among the terms, that Inf if only one sign of Inf occurs, finite otherwise (as long as the sum of the
+ *           magnitudes does not overflow).  No NaN is dropped by a min / max, no Inf * 0 arises in a padded lane.  The NormL0
+ *           value is a count (a NaN entry counts as a nonzero): always finite.
+ *   status: a data NaN is not an abandoned wait.  The call returns 0, it never sets SPX_ERR_INTERNAL, and it leaves the
+ *           context as a call on finite data leaves it: the next call returns 0 and gives the bits it gives on a fresh context
+ *           after the same sequence of calls.
+ *   ShiftedNormL1B2 with +-Inf in q or sj: chi(ProjB(-xk)) is +Inf, froot has no finite zero and the root is taken at infinity,
+ *           where the reference's bracket doubling ends -- NaN (Inf * 0) at those elements, -sj exactly at every other.
+ *           ShiftedGroupNormL2Binf: a group that holds a NaN is NaN throughout, whatever its bracket looks like and whichever
+ *           kernel form owns it (register tiles, one workgroup, a team of workgroups on chip or streamed). */
 int spx_proxval_l1(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
                    double lambda, double sigma, double q_scale, double* value);
 int spx_proxval_l0(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
@@ -441,8 +456,9 @@ int spx_obj_l1_b2(spx_ctx* ctx, const double* y, const double* xk, const double*
  *   return : as the other spx_proxval_*: without a device value target the call synchronises and writes the host double;
  *            with spx_ctx_set_value_target the kernel stores the device double (one 8-byte store), *value is NaN and nothing
  *            is read back.  A launch poisoned by an expired wait stores NaN as the value, and NaN in y as spx_prox_l1_b2
- *            does.  n == 0: value 0 (on the host, or the device target zeroed).  value == NULL is SPX_ERR_INVALID_ARG,
- *            nothing launched.  Capturable exactly where spx_prox_l1_b2 is, given a device value target and one warm-up call.
+ *            does.  Non-finite DATA are not that case: "NON-FINITE DATA" at spx_proxval_* above holds here too.  n == 0: value 0
+ *            (on the host, or the device target zeroed).  value == NULL is SPX_ERR_INVALID_ARG, nothing launched.  Capturable
+ *            exactly where spx_prox_l1_b2 is, given a device value target and one warm-up call.
  * FUSED route -- all four forms: the value comes out of the launch that stores y, nothing is read a second time.  The grid
  * and the form are the ones spx_prox_l1_b2 takes for the same arguments (y's bits depend on the partition of its sums).
  * COMPOSED route -- none: no form composes y = q_scale * q, the plain prox and spx_obj_l1 inside this call.  (The fused
@@ -473,7 +489,7 @@ int spx_proxval_l1_b2(spx_ctx* ctx, double* y, const double* q, const double* xk
  *   n == 0: three zeros on the host, and three zeros stored to stats_dev by a kernel (no memset node).
  *   Every sum is formed in a fixed order (static partition in every storing pass, partial sums exchanged in workgroup order): a
  *   repeat gives the same bits, independent of which workgroup took which tile.  After an expired wait y is NaN as in
- *   spx_prox_l1_b2 and the three sums are NaN.
+ *   spx_prox_l1_b2 and the three sums are NaN.  Non-finite data: "NON-FINITE DATA" at spx_proxval_* above.
  * FUSED route -- the register-resident form, the LDS form and the 16-byte streaming form: y, xkn and the three sums come out
  * of the ONE launch that stores y (streaming: 64 B/element, 40 with the trust region inactive; the register and LDS forms read
  * q a second time at the store, they keep only sj + q_scale * q across the root find).
@@ -532,6 +548,8 @@ int spx_prox_group_l2_binf(spx_ctx* ctx, double* y, const double* q, const doubl
  *            is read back.  Capturable under the conditions stated at spx_ctx_set_value_target (device value target, one
  *            warm-up call, contiguous layouts).  n == 0 or ngroups == 0: value 0, y as the plain operator leaves it.
  *            Argument checks as spx_prox_group_l2; value == NULL is SPX_ERR_INVALID_ARG, nothing launched.
+ *            Non-finite data: "NON-FINITE DATA" at spx_proxval_* above (a group with a NaN in it is NaN throughout, as in the
+ *            reference, and its term is NaN).
  * FUSED routes -- the value comes out of the launches that store y, no second sweep over the vectors: uniform groups of at
  * most 512 elements and CSR offsets with a size bound (group_size) of at most 512, the register-tile kernels.  Uniform
  * layouts: one launch (plain), two (Binf: the main launch and the launch over its deferred list, each adding the terms of
@@ -561,6 +579,7 @@ int spx_proxval_group_l2_binf(spx_ctx* ctx, double* y, const double* q, const do
  *   stats / stats_dev, capture, spx_ctx_set_value_target (no effect), y == q (refused): as spx_proxstep_*.  The sums are added
  *              in a fixed order: two runs on the same inputs give the same bits.
  *   n == 0 or ngroups == 0: three zeros, stored to stats_dev by a kernel; y as the plain operator leaves it.
+ *   Non-finite data: "NON-FINITE DATA" at spx_proxval_* above.
  * FUSED route -- uniform groups of at most 512 elements (group_offsets == NULL, the register-tile kernels): y, xkn and the
  * three sums come out of the launches that store y; 40 B/element + one more read of q that is served on chip (the kernel
  * keeps no copy of q across the group's reductions).  One launch (plain), two (Binf).

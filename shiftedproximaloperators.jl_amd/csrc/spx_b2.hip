@@ -905,6 +905,10 @@ __global__ __launch_bounds__(THREADS) void k_b2_coop(double* y, const double* q,
   // could never accept and ran out of reductions 3e-10 away: tests/test_gpu_stress.py::test_b2_integer_lattices_exact_roots.)
   const bool scaled = delta < chiy;
   if (blockIdx.x == 0 && t == 0) hdr->b2_last_scaled = scaled ? 1 : 0;
+  // chi(y) = +Inf (a +-Inf in q or sj: both ends of that element's box are infinite): froot(eta) = eta - Inf < 0 at every finite
+  // eta, the root lies at infinity -- where the reference's bracket doubling ends.  eta = Inf, r = Inf, rinv = 0: Inf * 0 = NaN at
+  // the infinite elements, -sj elsewhere, without thirty doubling passes that end on an arbitrary finite eta.
+  const bool root_at_inf = scaled && !(chiy < INFINITY);
   double eta = delta;
   bool stored = !scaled && store_first;
   if (scaled) {
@@ -916,7 +920,7 @@ __global__ __launch_bounds__(THREADS) void k_b2_coop(double* y, const double* q,
     const bool ub_ok = eta_ub > delta && eta_ub < INFINITY;
     bool have_eval = false;
     const double P1 = P, C1 = C;  // (the sums at r = 1)
-    if (have_bracket) {
+    if (have_bracket && !root_at_inf) {
       // does the bracket hold the root?  froot at both ends and at the sample's root, exact on aggregate + candidates, one sweep
       const double eta_c = (eta_s > eta_a && eta_s < eta_b) ? eta_s : 0.5 * (eta_a + eta_b);
       pass_cand(eta_a / delta, eta_b / delta, eta_c / delta);
@@ -941,7 +945,7 @@ __global__ __launch_bounds__(THREADS) void k_b2_coop(double* y, const double* q,
     }
     double y_eta = -1.0;
     double prev_step = -1.0;  // relative size of the previous exact step
-    for (int it = 0; it < kB2MaxPass - 34 && np < kB2MaxPass - 1; ++it) {
+    for (int it = 0; it < kB2MaxPass - 34 && np < kB2MaxPass - 1 && !root_at_inf; ++it) {
       const double r = eta / delta;
       const double f = eta - chil * sqrt(r * r * P + C);
       if (f == 0.0 || (exact_step && P == pP && C == pC)) break;
@@ -983,6 +987,7 @@ __global__ __launch_bounds__(THREADS) void k_b2_coop(double* y, const double* q,
       y_eta = spec ? eta : -1.0;
     }
     stored = (y_eta == eta);
+    if (root_at_inf) eta = INFINITY;
   }
 #ifdef SPX_B2_PROFILE
   if (stored && blockIdx.x == 0 && t == 0) g_b2_nstamp = nst;

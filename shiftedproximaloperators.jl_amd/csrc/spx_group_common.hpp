@@ -648,6 +648,10 @@ __device__ __forceinline__ int binf_root(const G& grp, double lam, double sigma,
     team_sum2<TEAM>(sS, sX, lds);
     mX = team_max<TEAM>(mX, lds);
   }
+  // A NaN in the group (q, xk or sj: S carries all three) makes every norm of the reference NaN and the whole group NaN.
+  // sqrt_pos returns 0 for a NaN argument, and the decisions below would take ||S|| = 0 for granted and write zeros: the literal
+  // evaluation follows the reference operation by operation.
+  if (!(sS + sX == sS + sX)) return BINF_LITERAL;
   const double nS = sqrt_pos(sS), nX = sqrt_pos(sX);
   // X == 0 in the whole group and sigma lambda > ||S||: the group of a sparse iterate that stays zero -- the bulk of the
   // groups in a group-lasso run, so it must not take the literal path its (usually degenerate: lmax = ||S|| + sigma zlmax

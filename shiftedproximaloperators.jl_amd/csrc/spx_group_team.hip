@@ -360,6 +360,7 @@ __device__ __forceinline__ int binf_team_fast(const double* P, double lam, doubl
   const double ul = lmin - sl;
   const double taul = ul * fast_rcp(lmin);
   const double sS = P[0], sX = P[1], sz = P[2], sal = P[3], sbl = P[4], mX = P[8], gap = -P[9];
+  if (!(sS + sX == sS + sX)) return BINF_LITERAL;  // a NaN in the group: as binf_root, the literal evaluation (sqrt_pos(NaN) is 0)
   const double nS = sqrt_pos(sS), nX = sqrt_pos(sX);
   if (mX == 0.0 && sl < INFINITY && sl * (1.0 - 1e-9) > nS) return BINF_ZERO;
   const double ubound = sqrt_pos(sS + sX) * (1.0 + 8 * eps);
