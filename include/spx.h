@@ -368,6 +368,59 @@ int spx_iprox_l0_box(spx_ctx* ctx, double* y, const double* g, const double* d, 
                      const double* sj, int64_t n, double lambda, const double* l_vec,
                      const double* u_vec, double l_scalar, double u_scalar, const uint8_t* sel_mask);
 
+/* ---- iprox! fused with the step statistics of a diagonal quasi-Newton iteration ----------------- */
+/* What an R2DH iteration does around iprox! -- `s = iprox!(s, psi, grad, d)`, `h(xk + s)`, `dot(grad, s)`,
+ * `dot(s, d .* s)`, `xk + s`, `norm(s)` -- in the ONE pass that stores y: 48 B/element (g, d, xk, sj in; y, xkn out) instead
+ * of about 128 in five or six separate passes.  The argument list of spx_iprox_X, then the tail of spx_proxstep_*; there is
+ * no q_scale (g and d enter as they are).
+ *   y        : bit-identical to spx_iprox_X on the same arguments, on every kernel form (LDS-staged, register-staged and
+ *              element-wise kernels, peeled head and odd tail, vector or scalar bounds, mask or none).
+ *   xkn      : device pointer to n doubles, or NULL.  xkn[i] = (xk[i] + sj[i]) + y[i], in that association, for EVERY i,
+ *              selected or not.  A pointer EQUAL to one of y, g, d, xk, sj, l_vec, u_vec or the mask returns
+ *              SPX_ERR_INVALID_ARG and nothing is launched; nothing else about overlap is checked.  Any 8-byte alignment
+ *              (when it differs from the other vectors' the call takes the element-wise kernel, as spx_proxstep_* does).
+ *   four sums, {[0], [1], [2], [3]}:
+ *     [0] = lambda * sum over the SELECTED indices of Term((xk + sj) + y): |v| (NormL1), the count of nonzeros (NormL0);
+ *           Box forms: the h part only;
+ *     [1] = sum over ALL i of g[i] * y[i];
+ *     [2] = sum over ALL i of (d[i] * y[i]) * y[i], formed in that association and never contracted -- the model of the
+ *           iteration is [1] + [2] / 2: the caller halves it;
+ *     [3] = sum over ALL i of y[i] * y[i].
+ *   stats    : host double[4], or NULL.  stats_dev: DEVICE double[4], or NULL.  At least one must be non-NULL
+ *              (SPX_ERR_INVALID_ARG otherwise).  With stats == NULL the call only enqueues -- no read-back, no
+ *              synchronisation -- and is capturable under the rules of the value entry points (device pointers, the same
+ *              call made once before on the context: the workspace holds four planes of partial sums and does not grow
+ *              while capturing).  With stats != NULL the call copies 32 bytes back and synchronises, and is refused under a
+ *              capture (SPX_ERR_INVALID_ARG, nothing launched).  Both given: the same bits in both.
+ *   spx_ctx_set_value_target does not affect these calls.
+ *   y == g and y == d return SPX_ERR_INVALID_ARG (the sums would read an overwritten input).
+ *   check_d  : (unboxed forms) non-zero requires stats != NULL -- that call synchronises anyway -- and returns
+ *              SPX_ERR_ASSERT if some d[i] <= 0; non-zero with stats == NULL is SPX_ERR_INVALID_ARG.  check_d == 0:
+ *              asynchronous, IEEE results, as spx_iprox_X.  (The flag word the kernels raise lies clear of the four result
+ *              doubles at the front of the workspace.)
+ *   n == 0   : four zeros on the host, and four zeros stored to stats_dev by a kernel (no memset node).
+ *   NON-FINITE DATA in g, d, xk or sj: the contract stated at spx_proxval_* -- y keeps the bits of spx_iprox_X, the sums
+ *              follow IEEE addition of the terms formed from the stored y, the NormL0 count stays finite, the call returns 0
+ *              and leaves the context as a call on finite data leaves it.
+ * The four sums are added in a fixed order: reproducible run to run, and the same bits with tuning key 17 at 0 and at 1.
+ * All four operators are FUSED: each runs on the skeleton of its plain iprox! (ShiftedNormL1Box register-staged, the other
+ * three LDS-staged) and none carries scratch (profiles/iproxstep_kres.txt), so no operator takes a composed route.
+ * Float64 and device pointers only: no Float32 form and no host-pointer twin (spx_host_*). */
+int spx_iproxstep_l1(spx_ctx* ctx, double* y, const double* g, const double* d, const double* xk,
+                     const double* sj, int64_t n, double lambda, int check_d,
+                     double* xkn, double* stats, double* stats_dev);
+int spx_iproxstep_l0(spx_ctx* ctx, double* y, const double* g, const double* d, const double* xk,
+                     const double* sj, int64_t n, double lambda, int check_d,
+                     double* xkn, double* stats, double* stats_dev);
+int spx_iproxstep_l1_box(spx_ctx* ctx, double* y, const double* g, const double* d, const double* xk,
+                         const double* sj, int64_t n, double lambda, const double* l_vec,
+                         const double* u_vec, double l_scalar, double u_scalar, const uint8_t* sel_mask,
+                         double* xkn, double* stats, double* stats_dev);
+int spx_iproxstep_l0_box(spx_ctx* ctx, double* y, const double* g, const double* d, const double* xk,
+                         const double* sj, int64_t n, double lambda, const double* l_vec,
+                         const double* u_vec, double l_scalar, double u_scalar, const uint8_t* sel_mask,
+                         double* xkn, double* stats, double* stats_dev);
+
 /* ---- psi(y): objective value h(xk + sj + y) [+ indicator of the box / trust region] ------------------------ */
 /* Generic form src/ShiftedProximalOperators.jl:51-54; *value is written on the HOST; synchronous.
  * NormL1: lambda * sum |v|, NormL0: lambda * #nonzeros, RootNormLhalf: lambda * sum sqrt|v| (src/rootNormLhalf.jl:27-29). */

@@ -255,6 +255,49 @@ function prox_step!(y::DVec, ψ::ShiftedNormL1{Float64, <:DVec, <:DVec, <:DVec},
 end
 
 # ---------------------------------------------------------------------------------------------
+# iprox! fused with the step statistics of a diagonal quasi-Newton iteration (spx_iproxstep_*; no counterpart in the
+# reference: what R2DH does around iprox! -- `ψ(s)`, `dot(∇fk, s)`, `dot(s, d .* s)`, `xk + s`, `norm(s)` -- in the pass that
+# stores s).  Returns (y, h, gy, ydy, yy):
+#   h   = λ Σ over the selected indices of Term((xk + sj) + y)
+#   gy  = Σ over all i of g[i] y[i]      ydy = Σ over all i of (d[i] y[i]) y[i]  (the caller halves)      yy = Σ over all i of y[i]^2
+# xkn (a device vector that is none of y, g, d, ψ.xk, ψ.sj, l, u; or nothing) receives (xk + sj) + y.
+# `out` = a ROCVector{Float64} of at least 4 elements: the four sums stay on the device, nothing is read back and the call
+# does not synchronise; returns (y, out).  check_d = true (unboxed forms) asserts d .> 0 and needs out === nothing.
+# y must be neither g nor d.  Headline operator and the unboxed ℓ1 norm shown; spx_iproxstep_l0 / l0_box follow the same pattern.
+# ---------------------------------------------------------------------------------------------
+function iprox_step!(y::DVec, ψ::ShiftedNormL1Box{Float64, <:DVec, <:DVec, <:DVec}, g::DVec, d::DVec;
+                     xkn::Union{Nothing, DVec} = nothing, out::Union{Nothing, DVec} = nothing)
+  n = length(ψ.xk)
+  (length(y) == n && length(g) == n && length(d) == n && (xkn === nothing || length(xkn) == n)) || throw(BoundsError())
+  (out === nothing || length(out) >= 4) || throw(ArgumentError("out needs at least 4 elements"))
+  m = mask_for(ψ)
+  stats = zeros(Cdouble, 4)
+  check(ccall((:spx_iproxstep_l1_box, libspx), Cint,
+              (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int64, Cdouble,
+               Ptr{Cdouble}, Ptr{Cdouble}, Cdouble, Cdouble, Ptr{UInt8}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+              ctx(), dptr(y), dptr(g), dptr(d), dptr(ψ.xk), dptr(ψ.sj), n, ψ.λ,
+              dptr(vec_or_nothing(ψ.l)), dptr(vec_or_nothing(ψ.u)), scal(ψ.l), scal(ψ.u),
+              mptr(m), dptr(xkn), out === nothing ? pointer(stats) : Ptr{Cdouble}(C_NULL), dptr(out)))
+  return out === nothing ? (y, stats[1], stats[2], stats[3], stats[4]) : (y, out)
+end
+function iprox_step!(y::DVec, ψ::ShiftedNormL1{Float64, <:DVec, <:DVec, <:DVec}, g::DVec, d::DVec;
+                     check_d::Bool = false, xkn::Union{Nothing, DVec} = nothing, out::Union{Nothing, DVec} = nothing)
+  n = length(ψ.xk)
+  (length(y) == n && length(g) == n && length(d) == n && (xkn === nothing || length(xkn) == n)) || throw(BoundsError())
+  (out === nothing || length(out) >= 4) || throw(ArgumentError("out needs at least 4 elements"))
+  (check_d && out !== nothing) && throw(ArgumentError("check_d = true needs the host form of the statistics (out = nothing)"))
+  stats = zeros(Cdouble, 4)
+  st = ccall((:spx_iproxstep_l1, libspx), Cint,
+             (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int64, Cdouble, Cint,
+              Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+             ctx(), dptr(y), dptr(g), dptr(d), dptr(ψ.xk), dptr(ψ.sj), n, ψ.λ, check_d ? 1 : 0,
+             dptr(xkn), out === nothing ? pointer(stats) : Ptr{Cdouble}(C_NULL), dptr(out))
+  st == 6 && throw(AssertionError("d[i] > 0"))      # SPX_ERR_ASSERT
+  check(st)
+  return out === nothing ? (y, stats[1], stats[2], stats[3], stats[4]) : (y, out)
+end
+
+# ---------------------------------------------------------------------------------------------
 # l1 norm + l2-ball trust region      src/shiftedNormL1B2.jl:50-67   (χ = NormL2(χ.lambda))
 # ---------------------------------------------------------------------------------------------
 function prox!(y::DVec, ψ::ShiftedProximalOperators.ShiftedNormL1B2{Float64, <:DVec, <:DVec, <:DVec}, q::DVec, σ::Float64)

@@ -62,6 +62,10 @@ SIGNATURES = {
     "spx_iprox_l0": [_p, _p, _p, _p, _p, _p, _i64, _d, _int],
     "spx_iprox_l1_box": [_p, _p, _p, _p, _p, _p, _i64, _d, _p, _p, _d, _d, _p],
     "spx_iprox_l0_box": [_p, _p, _p, _p, _p, _p, _i64, _d, _p, _p, _d, _d, _p],
+    "spx_iproxstep_l1": [_p, _p, _p, _p, _p, _p, _i64, _d, _int, _p, ctypes.POINTER(_d), _p],
+    "spx_iproxstep_l0": [_p, _p, _p, _p, _p, _p, _i64, _d, _int, _p, ctypes.POINTER(_d), _p],
+    "spx_iproxstep_l1_box": [_p, _p, _p, _p, _p, _p, _i64, _d, _p, _p, _d, _d, _p, _p, ctypes.POINTER(_d), _p],
+    "spx_iproxstep_l0_box": [_p, _p, _p, _p, _p, _p, _i64, _d, _p, _p, _d, _d, _p, _p, ctypes.POINTER(_d), _p],
     "spx_obj_l1": [_p, _p, _p, _p, _i64, _d, ctypes.POINTER(_d)],
     "spx_obj_l0": [_p, _p, _p, _p, _i64, _d, ctypes.POINTER(_d)],
     "spx_obj_lhalf": [_p, _p, _p, _p, _i64, _d, ctypes.POINTER(_d)],

@@ -436,9 +436,20 @@ struct WithStep : WithValue<Base, Term> {
   double* xkn = nullptr;  // NULL: no store
   int64_t plane = 0;      // doubles between the planes of `partials`
 };
-// kSumsOf<Op>: the sums a call adds besides y -- 0 (plain prox! / iprox!), 1 (WithValue: h), 3 (WithStep: h, <q, y>, <y, y>).
+// iprox! fused with the step statistics of a diagonal quasi-Newton iteration (spx_iproxstep_*): Base is one of the four Iprox*
+// functors (kNIn = 4: call4(g, d, xk, sj, ...) is Base's own, so y keeps the bits of spx_iprox_X).  hterm, xkn, plane, partials
+// and the fin_* fields are WithStep's (qscale is not read: g and d enter as they are).  Four partial sums per slot, in four
+// planes: the h terms over the selected indices, then g[i] * y[i], (d[i] * y[i]) * y[i] -- twice the quadratic term of the
+// model, the lane has d in a register -- and y[i]^2 over ALL i.
+template <class Base, class Term>
+struct WithIstep : WithStep<Base, Term> {
+  static constexpr int kNIn = 4;
+  static constexpr int kSums = 4;
+};
+// kSumsOf<Op>: the sums a call adds besides y -- 0 (plain prox! / iprox!), 1 (WithValue: h), 3 (WithStep: h, <q, y>, <y, y>),
+// 4 (WithIstep: h, <g, y>, <d .* y, y>, <y, y>).
 // Everything below is written once over that count: plane p of a list of partials is added with the same statements, hence
-// in the same order and to the same bits, whether it is the only plane or one of three.
+// in the same order and to the same bits, whether it is the only plane or one of three or four.
 template <class Op, class = void>
 struct SumsOf { static constexpr int value = 0; };
 template <class Op>
@@ -525,7 +536,7 @@ __device__ __forceinline__ SepSums<NS> value_reduce_small(const double* partials
 // The partial sums t.v[0..NS) of this workgroup (valid in thread 0) go to its slot of the NS planes.  value_store: a later
 // launch adds them -- all there is to do in a launch that can never be the only one of its call.  value_publish: in the
 // one-launch form ONE ticket per workgroup (spx_fin_ticket) publishes all NS of them, and the workgroup that takes the last
-// one adds the planes and stores {fin_scale * h, <q, y>, <y, y>} (NS = 1: the first of them) to the library's result slots and
+// one adds the planes and stores {fin_scale * h, <q, y>, <y, y>} (NS = 1: the first of them; NS = 4: {fin_scale * h, <g, y>, <d .* y, y>, <y, y>}) to the library's result slots and
 // to fin_target if set.  Every lane of the workgroup must call it.
 template <class Op, int NS>
 __device__ __forceinline__ void value_store(const Op& op, int64_t slot, SepSums<NS> t) {
@@ -559,7 +570,8 @@ __device__ __forceinline__ void value_publish(const Op& op, int64_t slot, SepSum
 }
 
 // Workgroup b adds plane b of the partials, partials[b * plane + (0..count)), in a fixed order (reproducible run to run) and
-// stores out[b], and target[b] when target != NULL (the caller's device slots): {scale * h, <q, y>, <y, y>}.
+// stores out[b], and target[b] when target != NULL (the caller's device slots): {scale * h, <q, y>, <y, y>} (NS = 4:
+// {scale * h, <g, y>, <d .* y, y>, <y, y>}).
 // Grid: NS workgroups.
 template <int NS>
 __global__ __launch_bounds__(1024) void k_value_reduce(const double* partials, int64_t plane, int64_t count, double* out,
@@ -623,25 +635,30 @@ __device__ __forceinline__ double at_point(double x, double s, double y) { retur
 __device__ __forceinline__ f64x2 at_point(f64x2 x, f64x2 s, f64x2 y) { return f64x2{(x.x + s.x) + y.x, (x.y + s.y) + y.y}; }
 __device__ __forceinline__ double sum_prod(double a, double b) { return a * b; }
 __device__ __forceinline__ double sum_prod(f64x2 a, f64x2 b) { return a.x * b.x + a.y * b.y; }
+// (d * y) * y in that association (the library is built without contraction), the term of <d .* y, y>
+__device__ __forceinline__ double sum_prod3(double d, double y) { return (d * y) * y; }
+__device__ __forceinline__ double sum_prod3(f64x2 d, f64x2 y) { return (d.x * y.x) * y.x + (d.y * y.y) * y.y; }
 // The sums and the xkn store of one element site, written once for the three kernels: V = f64x2 is the 16-byte pair `i` of
 // the vector skeletons (s0, s1: its selection bits), V = double element `i` of the scalar kernel (s0).  q, x, s: the loaded
-// q (as passed, unscaled), xk, sj; r: the result(s).  NT: the store to xn (NULL: none) is non-temporal.  Returns acc with the
-// site's terms added (by value: see SepSums).
+// q (as passed, unscaled), d (read by the four-sum form only), xk, sj; r: the result(s).  NT: the store to xn (NULL: none) is
+// non-temporal.  Returns acc with the site's terms added (by value: see SepSums).  The last plane is always <y, y>.
 template <bool NT, class Op, class V>
-__device__ __forceinline__ SumsFor<Op> sep_accumulate(const Op& op, SumsFor<Op> acc, V q, V x, V s, V r, bool s0, bool s1,
+__device__ __forceinline__ SumsFor<Op> sep_accumulate(const Op& op, SumsFor<Op> acc, V q, V d, V x, V s, V r, bool s0, bool s1,
                                                       V* xn, int64_t i) {
-  if constexpr (kSumsOf<Op> >= 1) acc.v[0] += op.hterm(x, s, r, s0, s1);
-  if constexpr (kSumsOf<Op> == 3) {
+  constexpr int NS = kSumsOf<Op>;
+  if constexpr (NS >= 1) acc.v[0] += op.hterm(x, s, r, s0, s1);
+  if constexpr (NS >= 3) {
     acc.v[1] += sum_prod(q, r);
-    acc.v[2] += sum_prod(r, r);
+    if constexpr (NS == 4) acc.v[2] += sum_prod3(d, r);
+    acc.v[NS - 1] += sum_prod(r, r);
     if (xn) st2<NT>(xn + i, at_point(x, s, r));
   }
   return acc;
 }
-// (WithStep) where xkn goes, as pairs or elements; NULL: no store
+// (WithStep, WithIstep) where xkn goes, as pairs or elements; NULL: no store
 template <class V, class Op>
 __device__ __forceinline__ V* xkn_of(const Op& op) {
-  if constexpr (kSumsOf<Op> == 3) return reinterpret_cast<V*>(op.xkn);
+  if constexpr (kSumsOf<Op> >= 3) return reinterpret_cast<V*>(op.xkn);
   else return nullptr;
 }
 
@@ -690,7 +707,7 @@ __global__ __launch_bounds__(256) void k_sep_vec(double* y_, const double* q_, c
         f64x2 r;
         r.x = apply_op(op, vq[k].x, vd[k].x, vx[k].x, vs[k].x, l0, u0, s0);
         r.y = apply_op(op, vq[k].y, vd[k].y, vx[k].y, vs[k].y, l1, u1, s1);
-        acc = sep_accumulate<NT>(op, acc, vq[k], vx[k], vs[k], r, s0, s1, xn, i);
+        acc = sep_accumulate<NT>(op, acc, vq[k], vd[k], vx[k], vs[k], r, s0, s1, xn, i);
         st2<NT>(y + i, r);
       }
     } else {  // last, partial tile
@@ -711,7 +728,7 @@ __global__ __launch_bounds__(256) void k_sep_vec(double* y_, const double* q_, c
           f64x2 r;
           r.x = apply_op(op, a.x, dd.x, b.x, c.x, l0, u0, s0);
           r.y = apply_op(op, a.y, dd.y, b.y, c.y, l1, u1, s1);
-          acc = sep_accumulate<false>(op, acc, a, b, c, r, s0, s1, xn, i);
+          acc = sep_accumulate<false>(op, acc, a, dd, b, c, r, s0, s1, xn, i);
           y[i] = r;
         }
       }
@@ -805,7 +822,7 @@ __global__ __launch_bounds__(256) void k_sep_lds(double* y_, const double* q_, c
     r.x = apply_op(op, a.x, dd.x, b.x, c.x, l0, u0, s0);
     r.y = apply_op(op, a.y, dd.y, b.y, c.y, l1, u1, s1);
     if constexpr (kSumsOf<Op> > 0) {  // (the tail's lanes hold a copy of the last pair)
-      if (i < n2) acc = sep_accumulate<true>(op, acc, a, b, c, r, s0, s1, xn, i);  // (xkn out of registers: the extra store needs no LDS)
+      if (i < n2) acc = sep_accumulate<true>(op, acc, a, dd, b, c, r, s0, s1, xn, i);  // (xkn out of registers: the extra store needs no LDS)
     }
     if (i < n2) __builtin_nontemporal_store(r, y + i);
   }
@@ -832,7 +849,7 @@ __global__ __launch_bounds__(256) void k_sep_scalar(double* y, const double* q, 
     const double xi = xk[i], si = sj[i];
     const double qi = q[i];
     const double yi = apply_op(op, qi, di, xi, si, li, ui, sel);
-    acc = sep_accumulate<false>(op, acc, qi, xi, si, yi, sel, false, xn, i);
+    acc = sep_accumulate<false>(op, acc, qi, di, xi, si, yi, sel, false, xn, i);
     y[i] = yi;
   }
   if constexpr (kSumsOf<Op> > 0) value_store(op, blockIdx.x, block_sum4(acc));  // (never the only launch of a call)
@@ -893,7 +910,12 @@ static int launch_vec(spx_ctx* ctx, double* y, const double* q, const double* d,
   return SPX_OK;
 }
 
-// kSumsOf<Op> > 0: the sums {value_scale * h, <q, y>, <y, y>} (WithValue: the first of them) go to the library's result slots,
+// The workspace of a call with sums: [NS result doubles | kSepFlagOffset: the d > 0 flag word of spx_iproxstep_* | pad to 256 B
+// | NS planes of partial slots].  sep_plane: doubles per plane, at least the slots of any route.
+constexpr size_t kSepFlagOffset = 128;
+static int64_t sep_plane(const spx_ctx* ctx, int64_t n) { return ((n / 2) / (256 * 3) + 2) * 4 + 2 * (int64_t)ctx->num_cu * 8 + 16; }
+static size_t sep_ws_bytes(const spx_ctx* ctx, int64_t n, int ns) { return 256 + (size_t)ns * (size_t)sep_plane(ctx, n) * sizeof(double); }
+// kSumsOf<Op> > 0: the sums {value_scale * h, <q, y>, <y, y>} (WithValue: the first of them; WithIstep: the four) go to the library's result slots,
 // to result_dev (device doubles, or NULL) and, when result_host != NULL, back to the host -- that form synchronises and is
 // refused under a capture; those callers answer n == 0 themselves.
 template <class Op>
@@ -907,8 +929,8 @@ static int run_separable(spx_ctx* ctx, double* y, const double* q, const double*
   double* partials = nullptr;  // ws: [results | pad to 256 B | NS planes of partial slots]
   int64_t used = 0, plane = 0;
   if constexpr (NS > 0) {
-    plane = ((n / 2) / (256 * 3) + 2) * 4 + 2 * (int64_t)ctx->num_cu * 8 + 16;  // at least the slots of any route
-    int rcw = spx_ws_reserve(ctx, 256 + (size_t)NS * (size_t)plane * sizeof(double));
+    plane = sep_plane(ctx, n);
+    int rcw = spx_ws_reserve(ctx, sep_ws_bytes(ctx, n, NS));
     if (rcw) return rcw;
     partials = reinterpret_cast<double*>(static_cast<char*>(ctx->ws) + 256);
     if constexpr (NS > 1) op.plane = plane;
@@ -930,7 +952,7 @@ static int run_separable(spx_ctx* ctx, double* y, const double* q, const double*
     const int64_t cap = (int64_t)ctx->num_cu * 8;
     if (blocks > cap) blocks = cap;
     if constexpr (NS > 0) op.partials = partials + used;
-    if constexpr (NS == 3) op.xkn = xkn;  // (indexed from element 0)
+    if constexpr (NS >= 3) op.xkn = xkn;  // (indexed from element 0)
     hipLaunchKernelGGL((k_sep_scalar<Op>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, y, q, d, xk, sj, l, u,
                        mask, ls, us, begin, end, op);
     SPX_LAUNCH_CHECK();
@@ -964,7 +986,7 @@ static int run_separable(spx_ctx* ctx, double* y, const double* q, const double*
         op.fin_scale = value_scale;
       }
     }
-    if constexpr (NS == 3) op.xkn = xkn ? xkn + head : nullptr;
+    if constexpr (NS >= 3) op.xkn = xkn ? xkn + head : nullptr;
     if constexpr (Op::kBox) {
       const bool vecb = (l || u);
       const bool msk = (mask != nullptr);
@@ -1443,6 +1465,88 @@ SPX_EXPORT int spx_iprox_l0_box(spx_ctx* ctx, double* y, const double* g, const 
   if (rc) return rc;
   SPX_REQUIRE(n == 0 || d != nullptr, "d is NULL");
   return run_separable(ctx, y, g, xk, sj, n, l_vec, u_vec, l_scalar, u_scalar, sel_mask, OpIproxL0Box{lambda}, d);
+}
+
+// ---------------------------------------------------------------------------------------------
+// iprox! + step statistics in one pass (spx_iproxstep_*): y, xkn = (xk + sj) + y and {h, <g, y>, <d .* y, y>, <y, y>} to a host
+// double[4] (synchronous) and / or a device double[4] (enqueue only).  Float64, device pointers.  All four operators take the
+// fused route, each on the skeleton of its plain iprox! (profiles/iproxstep_kres.txt).
+// ---------------------------------------------------------------------------------------------
+// flagged: the unboxed forms, whose functor raises a flag word where d[i] <= 0
+template <class Base, class Term, bool FLAGGED>
+static int run_iproxstep(spx_ctx* ctx, double* y, const double* g, const double* d, const double* xk, const double* sj,
+                         int64_t n, double lambda, int check_d, const double* l, const double* u, double ls, double us,
+                         const uint8_t* mask, double* xkn, double* stats, double* stats_dev) {
+  int rc = spx_check_common(ctx, y, g, xk, sj, n);
+  if (rc) return rc;
+  SPX_REQUIRE(n == 0 || d != nullptr, "d is NULL");
+  SPX_REQUIRE(stats != nullptr || stats_dev != nullptr, "stats and stats_dev are both NULL");
+  SPX_REQUIRE(!check_d || stats != nullptr, "check_d needs the host form of the statistics (stats != NULL): it synchronises");
+  SPX_REQUIRE(y == nullptr || (y != g && y != d), "y aliases g or d (the sums would read an overwritten input)");
+  if (xkn != nullptr) {
+    const void* x = xkn;
+    SPX_REQUIRE(x != y && x != g && x != d && x != xk && x != sj && x != l && x != u && x != mask, "xkn is one of the other vectors");
+  }
+  // the host copy synchronises: refused under a capture before anything is enqueued
+  if (stats != nullptr) { rc = spx_require_not_capturing(ctx, "returning the step statistics to the host (pass stats = NULL)"); if (rc) return rc; }
+  if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0.0;
+  if (n == 0) {
+    if (stats_dev == nullptr) return SPX_OK;
+    SPX_ON_DEVICE(ctx);
+    return spx_zero_async(ctx, stats_dev, 4 * sizeof(double));  // (a kernel, not a memset node)
+  }
+  WithIstep<Base, Term> op{};
+  op.lambda = lambda;
+  int* flag = nullptr;
+  if constexpr (FLAGGED) {
+    // the whole workspace of the call is reserved here, so that the flag word keeps its address through run_separable
+    rc = spx_ws_reserve(ctx, sep_ws_bytes(ctx, n, 4));
+    if (rc) return rc;
+    SPX_ON_DEVICE(ctx);
+    flag = reinterpret_cast<int*>(static_cast<char*>(ctx->ws) + kSepFlagOffset);  // (clear of the four result doubles)
+    { const int rz = spx_zero_async(ctx, flag, sizeof(int)); if (rz) return rz; }
+    op.flag = flag;
+  }
+  // (the context's value target applies to prox_value only)
+  rc = run_separable(ctx, y, g, xk, sj, n, l, u, ls, us, mask, op, d, stats, stats_dev, lambda, xkn);
+  if (rc || !check_d) return rc;
+  if constexpr (FLAGGED) {
+    int bad = 0;  // (the stream has been synchronised by the copy of the statistics)
+    SPX_HIP(hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    SPX_HIP(hipStreamSynchronize(ctx->stream));
+    if (bad) {
+      spx_set_error("AssertionError: d[i] > 0");
+      return SPX_ERR_ASSERT;
+    }
+  }
+  return SPX_OK;
+}
+
+SPX_EXPORT int spx_iproxstep_l1(spx_ctx* ctx, double* y, const double* g, const double* d, const double* xk,
+                                const double* sj, int64_t n, double lambda, int check_d, double* xkn, double* stats,
+                                double* stats_dev) {
+  return run_iproxstep<OpIproxL1, HTermL1, true>(ctx, y, g, d, xk, sj, n, lambda, check_d, nullptr, nullptr, 0.0, 0.0, nullptr,
+                                                 xkn, stats, stats_dev);
+}
+SPX_EXPORT int spx_iproxstep_l0(spx_ctx* ctx, double* y, const double* g, const double* d, const double* xk,
+                                const double* sj, int64_t n, double lambda, int check_d, double* xkn, double* stats,
+                                double* stats_dev) {
+  return run_iproxstep<OpIproxL0, HTermL0, true>(ctx, y, g, d, xk, sj, n, lambda, check_d, nullptr, nullptr, 0.0, 0.0, nullptr,
+                                                 xkn, stats, stats_dev);
+}
+SPX_EXPORT int spx_iproxstep_l1_box(spx_ctx* ctx, double* y, const double* g, const double* d, const double* xk,
+                                    const double* sj, int64_t n, double lambda, const double* l_vec, const double* u_vec,
+                                    double l_scalar, double u_scalar, const uint8_t* sel_mask, double* xkn, double* stats,
+                                    double* stats_dev) {
+  return run_iproxstep<OpIproxL1Box, HTermL1, false>(ctx, y, g, d, xk, sj, n, lambda, 0, l_vec, u_vec, l_scalar, u_scalar,
+                                                     sel_mask, xkn, stats, stats_dev);
+}
+SPX_EXPORT int spx_iproxstep_l0_box(spx_ctx* ctx, double* y, const double* g, const double* d, const double* xk,
+                                    const double* sj, int64_t n, double lambda, const double* l_vec, const double* u_vec,
+                                    double l_scalar, double u_scalar, const uint8_t* sel_mask, double* xkn, double* stats,
+                                    double* stats_dev) {
+  return run_iproxstep<OpIproxL0Box, HTermL0, false>(ctx, y, g, d, xk, sj, n, lambda, 0, l_vec, u_vec, l_scalar, u_scalar,
+                                                     sel_mask, xkn, stats, stats_dev);
 }
 
 SPX_EXPORT int spx_iprox_l1_f32(spx_ctx* ctx, float* y, const float* g, const float* d, const float* xk, const float* sj,

@@ -976,6 +976,66 @@ def iprox(ψ, g, d):
     return iprox_bang(ψ.sol, ψ, g, d)
 
 
+def iprox_step_bang(y, ψ, g, d, check=False, xkn=None, out=None):
+    """iprox!(y, ψ, g, d) and the step statistics of a diagonal quasi-Newton iteration (R2DH: `h(xk + s)`, `∇fᵀs`,
+    `sᵀ(d .* s)`, `xk + s`, `‖s‖`) in ONE pass over the vectors (spx_iproxstep_*):
+
+        h   = λ · Σ over the SELECTED indices of Term((xk + sj) + y)   -- |v| (NormL1), nonzero count (NormL0); Box forms: h part only
+        gy  = Σ over ALL i of g[i] · y[i]
+        ydy = Σ over ALL i of (d[i] · y[i]) · y[i]   -- in that association; the model is gy + ydy / 2, the caller halves
+        yy  = Σ over ALL i of y[i]²
+        xkn[i] = (xk[i] + sj[i]) + y[i] for every i, selected or not (a device vector like ψ.xk that is none of y, g, d, ψ.xk,
+                 ψ.sj, l, u; None: not stored)
+
+    y has the bits of iprox!(y, ψ, g, d).  out=None: returns (y, h, gy, ydy, yy) as Python floats (synchronises).  out = a
+    float64 device tensor with at least 4 elements: out[0:4] = (h, gy, ydy, yy), nothing is read back and the stream is not
+    synchronised; returns (y, out) -- this form can be captured into a graph once the same call has run before.
+    `device_values` does not apply.  check=True (unboxed forms) asserts d .> 0 like the reference: it raises AssertionError
+    and needs the host form (out=None), which synchronises anyway.  y must be neither g nor d.
+    Supported: ShiftedNormL1 / NormL0 and their Box forms on device Float64 vectors; everything else raises TypeError."""
+    if not isinstance(ψ, (ShiftedNormL1, ShiftedNormL0, ShiftedNormL1Box, ShiftedNormL0Box)) or ψ.host or ψ.f32:
+        raise TypeError("iprox_step is available for ShiftedNormL1 / ShiftedNormL0 and their Box forms on device Float64 "
+                        "vectors (no host ψ, no Float32, no other operator)")
+    n = _n(ψ.xk)
+    _vec(g, "g", n, like=ψ.xk)
+    _vec(d, "d", n, like=ψ.xk)
+    _vec(y, "y", n, like=ψ.xk)
+    if xkn is not None:
+        _vec(xkn, "xkn", n, like=ψ.xk)
+    if y is g or y is d:
+        raise TypeError("iprox_step: y must be neither g nor d (gy and ydy are taken with the g and d that were passed)")
+    if out is not None and not (type(out) is _Tensor and out.is_cuda and out.dtype == torch.float64 and out.dim() == 1
+                                and out.numel() >= 4 and out.stride(0) == 1 and out.device == ψ.xk.device):
+        raise TypeError("out must be a contiguous float64 device tensor with at least 4 elements on ψ.xk's device")
+    boxed = isinstance(ψ, _Boxed)
+    if check and not boxed and out is not None:
+        raise TypeError("iprox_step: check=True needs the host form of the statistics (out=None)")
+    ψ._refresh()
+    host = (ctypes.c_double * 4)() if out is None else None
+    tail = (_ptr(xkn), host, ctypes.c_void_p(out.data_ptr()) if out is not None else _NULL)
+    L, ctx = _lib.load(), _ctx(_dev(y))
+    fn = getattr(L, ψ._ifn.replace("spx_iprox_", "spx_iproxstep_"))
+    if not boxed:
+        st = fn(ctx, _ptr(y), _ptr(g), _ptr(d), _ptr(ψ.xk), _ptr(ψ.sj), n, ψ.h.lam, 1 if check else 0, *tail)
+        if st == 6:  # SPX_ERR_ASSERT: the reference's `@assert d[i] > 0`
+            raise AssertionError("d[i] > 0")
+    else:
+        lv = None if _is_real(ψ.l) else _vec(ψ.l, "l", n, like=y)
+        uv = None if _is_real(ψ.u) else _vec(ψ.u, "u", n, like=y)
+        st = fn(ctx, _ptr(y), _ptr(g), _ptr(d), _ptr(ψ.xk), _ptr(ψ.sj), n, ψ.h.lam, _ptr(lv), _ptr(uv),
+                float(ψ.l) if lv is None else 0.0, float(ψ.u) if uv is None else 0.0,
+                _ptr(ψ._mask[0]) if ψ._mask is not None else ctypes.c_void_p(0), *tail)
+    _lib.check(st)
+    if out is not None:
+        return y, out
+    return y, host[0], host[1], host[2], host[3]
+
+
+def iprox_step(ψ, g, d, check=False, xkn=None, out=None):
+    """iprox_step_bang(ψ.sol, ψ, g, d, ...): (ψ.sol, h, gy, ydy, yy), or (ψ.sol, out) with a device `out`; see iprox_step_bang"""
+    return iprox_step_bang(ψ.sol, ψ, g, d, check, xkn, out)
+
+
 def shift_bang(ψ, shift):
     """shift!(ψ, v): in-place copy into ψ.sj (twice shifted) or ψ.xk -- i.e. into the caller's tensor
     (src/ShiftedProximalOperators.jl:72-79)."""
