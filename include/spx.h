@@ -235,8 +235,11 @@ int spx_iprox_l0_box_f32(spx_ctx* ctx, float* y, const float* g, const float* d,
  * operation as in the reference ((xk + sj) + y, sj + y, the box ends -+ sqrt(eps(Float32)), each square root); `1.1 * Delta`
  * and the comparison against it are Float64 (Julia promotes the literal); the SUM is formed in Float64 and *value is a
  * double -- round it to Float32 to compare with the reference's Float32 result (counts and +Inf decisions are exact, sums
- * agree to Float32 rounding of the reference's own pairwise Float32 summation).  Device value targets and the host
- * read-back behave as for the Float64 forms. */
+ * agree to Float32 rounding of the reference's own pairwise Float32 summation).  The BInf forms add (sj + y) + xk, as the
+ * reference does; the group forms square each Float32 element as a Float64 product (exact) and multiply (double)lambda_g by the
+ * Float64 root.  That fixes every term exactly (oracle/spx_oracle_f32.c states them): *value is (double)lambda times their sum
+ * to 1e-12 of sum |term|, asserted in tests/test_gpu_f32_exact.py.  Device value targets and the host read-back behave as for
+ * the Float64 forms. */
 int spx_obj_l1_f32(spx_ctx* ctx, const float* y, const float* xk, const float* sj, int64_t n, float lambda, double* value);
 int spx_obj_l0_f32(spx_ctx* ctx, const float* y, const float* xk, const float* sj, int64_t n, float lambda, double* value);
 int spx_obj_lhalf_f32(spx_ctx* ctx, const float* y, const float* xk, const float* sj, int64_t n, float lambda, double* value);
@@ -649,8 +652,12 @@ int spx_proxstep_group_l2_binf(spx_ctx* ctx, double* y, const double* q, const d
                                double sigma, double delta, double q_scale, double* xkn, double* stats, double* stats_dev);
 
 /* ShiftedGroupNormL2.prox! on Float32 vectors (round 3; the method is generic in R, src/shiftedGroupNormL2.jl:52-79): every
- * elementwise operation in Float32; the group norm is accumulated in Float64 and rounded once (the reference's `norm` is
- * BLAS / a generic loop: agreement to a few Float32 ulps of the operands, not bits).  Contiguous groups (uniform or CSR).
+ * elementwise operation in Float32 -- sol = (q + xk) + sj, alpha = max(1 - sigma * lambda / snorm, 0), alpha * sol - (xk + sj);
+ * the squares of a group are Float64 products of Float32 values (exact), their sum is Float64 and the norm is rounded to
+ * Float32 once.  (The reference's own `norm` is BLAS / a generic loop, which pins no last ulp: this is the statement.)  Asserted
+ * bit for bit against that restatement (oracle/spx_oracle_f32.c, tests/test_gpu_f32_exact.py), with one exception: a group
+ * whose exact norm lies within 1e-12 relative of the midpoint of two adjacent Float32 values equals, bit for bit, the result with
+ * one of those two as its norm.  Indices in no group end as (y on entry) - (xk + sj).  Contiguous groups (uniform or CSR).
  * ShiftedGroupNormL2Binf has no Float32 form. */
 int spx_prox_group_l2_f32(spx_ctx* ctx, float* y, const float* q, const float* xk, const float* sj, int64_t n,
                           const int64_t* group_offsets, int64_t group_size, int64_t ngroups, const float* lambda_vec,

@@ -492,6 +492,13 @@ def lib32():
         L.orc32_iprox_l1_box.argtypes = [fp, fp, fp, fp, fp, i64, f, fp, fp, f, f, up]
         L.orc32_iprox_l0_box.argtypes = [fp, fp, fp, fp, fp, i64, f, fp, fp, f, f, up]
         L.orc32_iprox_l1_box.restype = L.orc32_iprox_l0_box.restype = None
+        ci, dp, ip = ctypes.c_int, _c_double_p, _c_int64_p
+        L.orc32_obj_terms.argtypes = [dp, ci, ci, fp, fp, fp, i64, fp, fp, f, f, up, f]
+        L.orc32_obj_terms.restype = ci
+        L.orc32_obj_group_terms.argtypes = [dp, fp, fp, fp, i64, ip, i64, i64, fp, ci, f]
+        L.orc32_obj_group_terms.restype = ci
+        L.orc32_prox_group_l2.argtypes = [fp, fp, fp, fp, i64, ip, i64, i64, fp, f, fp]
+        L.orc32_prox_group_l2.restype = None
         _lib32 = L
     return _lib32
 
@@ -594,4 +601,76 @@ def prox_indball_l0_f32(q, xk, sj, r, delta=None, _order=None):
         d = np.float32(delta)
         # Julia min / max: NaN propagates (a NaN entry stays NaN); -0.0 < +0.0 is irrelevant for a clamp at +-delta != 0
         y = np.where(np.isnan(y), y, np.minimum(np.maximum(y, -d), d)).astype(np.float32)
+    return y
+
+
+# ---- psi(y) and ShiftedGroupNormL2.prox! with R = Float32 (the second half of oracle/spx_oracle_f32.c) ------------------------
+def _bounds32(l, u):
+    assert l is not None and u is not None, "the Box form takes both bounds (a scalar or a vector each)"
+    lv = uv = None
+    ls = us = np.float32(0)
+    if np.ndim(l) == 0: ls = np.float32(l)
+    else: lv = _f32(l)
+    if np.ndim(u) == 0: us = np.float32(u)
+    else: uv = _f32(u)
+    return lv, uv, ls, us
+
+
+def obj_f32(kind, y, xk, sj, l=None, u=None, mask=None, delta=None):
+    """The terms of psi(y) on Float32 vectors WITHOUT lambda, and the verdict: (terms float64[n], infeasible bool).
+    kind in {"l1", "l0", "lhalf"}; l, u given: the Box form (scalars or vectors, mask = uint8 or None); delta given: the BInf
+    form (v = (sj + y) + xk, |sj + y| <= 1.1 Delta in Float64); neither: the generic form.  psi(y) = +Inf if infeasible, else
+    (double)lambda * (exact sum of the terms); IndBallL0: +Inf if infeasible or the sum of the "l0" terms exceeds r, else 0."""
+    y, xk, sj = _f32(y), _f32(xk), _f32(sj)
+    n = y.shape[0]
+    assert xk.shape[0] == n and sj.shape[0] == n and not ((l is not None or u is not None) and delta is not None)
+    terms = np.empty(n, dtype=np.float64)
+    lv = uv = mp = None
+    ls = us = np.float32(0)
+    mode = 0
+    if l is not None or u is not None:
+        mode = 1
+        lv, uv, ls, us = _bounds32(l, u)
+        assert (lv is None or lv.shape[0] == n) and (uv is None or uv.shape[0] == n)
+        m, mp = _mask(mask, n)
+    elif delta is not None:
+        mode = 2
+    bad = lib32().orc32_obj_terms(_dp(terms), _KIND[kind], mode, _fp(y), _fp(xk), _fp(sj), n, _fp(lv), _fp(uv), ls, us, mp,
+                                  np.float32(0 if delta is None else delta))
+    return terms, bool(bad)
+
+
+def _groups32(n, offsets, gsize):
+    if offsets is not None:
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        return off, off.ctypes.data_as(_c_int64_p), 0, off.shape[0] - 1
+    assert gsize > 0 and n % gsize == 0
+    return None, None, int(gsize), n // gsize
+
+
+def obj_group_f32(y, xk, sj, lam, offsets=None, gsize=0, delta=None):
+    """(terms float64[ngroups] = (double)lambda_g * ||v_g||, outside bool, bad_offsets bool) of GroupNormL2(Binf) on Float32
+    vectors.  outside: |sj + y| > 1.1 Delta somewhere in [0, n) (delta given); bad_offsets: decreasing or outside [0, n] --
+    the terms are then NaN."""
+    y, xk, sj, lam = _f32(y), _f32(xk), _f32(sj), _f32(lam)
+    n = y.shape[0]
+    off, offp, gs, ng = _groups32(n, offsets, gsize)
+    assert lam.shape[0] == ng
+    terms = np.full(ng, np.nan, dtype=np.float64)
+    v = lib32().orc32_obj_group_terms(_dp(terms), _fp(y), _fp(xk), _fp(sj), n, offp, gs, ng, _fp(lam), int(delta is not None),
+                                      np.float32(0 if delta is None else delta))
+    return terms, bool(v & 1), bool(v & 2)
+
+
+def prox_group_l2_f32(q, xk, sj, lam, sigma, offsets=None, gsize=0, y0=None, snorm=None):
+    """ShiftedGroupNormL2.prox! on Float32 vectors.  y0 = y on entry (indices in no group end as y0 - (xk + sj); default zeros);
+    snorm = per-group norm override (float32[ngroups], NaN = none).  y === q gives the same result: sol is formed first."""
+    q, xk, sj, lam = _f32(q), _f32(xk), _f32(sj), _f32(lam)
+    n = q.shape[0]
+    off, offp, gs, ng = _groups32(n, offsets, gsize)
+    assert lam.shape[0] == ng
+    y = np.zeros(n, dtype=np.float32) if y0 is None else _f32(y0).copy()
+    sn = None if snorm is None else _f32(snorm)
+    assert sn is None or sn.shape[0] == ng
+    lib32().orc32_prox_group_l2(_fp(y), _fp(q), _fp(xk), _fp(sj), n, offp, gs, ng, _fp(lam), np.float32(sigma), _fp(sn))
     return y

@@ -4,8 +4,9 @@
 //     sol = (q + xk) + sj;   per group: snorm = norm(sol[idx]);  y[idx] = snorm == 0 ? 0 : max(1 - sigma lambda / snorm, 0) sol[idx];
 //     y -= xk + sj
 // every elementwise operation is a Float32 operation; `norm` of a Float32 vector is BLAS snrm2 / a scaled generic loop [ext],
-// whose accumulation order is not pinned -- here the squares are summed in Float64 and the norm rounded to Float32 once (within
-// an ulp of the exact Float32 norm); parity is therefore to a few Float32 ulps of the operands' scale, not bits.
+// whose accumulation order is not pinned -- here the squares are Float64 products (exact), summed in Float64, and the norm is
+// rounded to Float32 once: that fixes every bit of the result, but for a group whose exact norm sits within 1e-12 of a Float32
+// rounding boundary, which may take either neighbour (include/spx.h states it; tests/test_gpu_f32_exact.py asserts it).
 // Contiguous groups (uniform size or CSR offsets), 16 B/element.  1..64 lanes per group, the group re-read from L1 / L2 for
 // the second pass: a generality path, not the tuned register-tile kernels of the Float64 form (spx_group.hip).
 // ShiftedGroupNormL2Binf has NO Float32 form: its root find would run `fzero` in Float32, whose result next to the pole of

@@ -9,10 +9,24 @@ hand-derivable known answers for operators whose prox the reference's tests leav
 """
 import json
 import os
+import struct
 
 NU = 1 / 9.1e4
 QRAW = [2631.441298528196, -533.9101219466443, 466.56156501426733, 1770.8953574224836, -2554.7769423950244]
 Q5 = [-NU * v for v in QRAW]
+
+
+def f32(v):
+    """v rounded to Float32 once, as a Python float"""
+    return struct.unpack("f", struct.pack("f", v))[0]
+
+
+# Float32 values the "f32_forms" answers are built from (each a Float32 held in a double)
+A30, B30 = f32(1e30), f32(1e-30)
+SLACK32 = f32(2.0 ** -11.5)                      # sqrt(eps(Float32)) = 2^-11.5 rounded to Float32
+T_LOW = f32(-1.5 - SLACK32)                      # l - sqrt(eps32) with l = -1.5, one Float32 subtraction
+T_OUT = f32(1.6500001)                           # the Float32 above 1.1 * 1.5 = 1.6500000000000001; 1.1f * 1.5f rounds to it
+H38 = f32(3e38)
 
 kats = {
     "provenance": "transcribed from /root/reference/test (v0.2.2); see cite fields",
@@ -114,6 +128,28 @@ kats = {
             "r2": [2.0, -2.0, 0.0, 0.0, 0.0, 0.0],
             "r3": [2.0, -2.0, 0.0, 2.0, 0.0, 0.0],
             "r4": [2.0, -2.0, 1.0, 2.0, 0.0, 0.0],
+        },
+        "f32_forms": {
+            "provenance": "psi(y) and ShiftedGroupNormL2.prox! on Float32 vectors as include/spx.h states their arithmetic; every number is a Float32 held in a double, every answer follows by hand, and each differs from an evaluation in one precision throughout",
+            "overflow": {
+                "note": "(xk + sj) + y overflows Float32 at 3e38: the term is +Inf; in Float64 it is 3e38 + 1.75",
+                "x": [H38, 1.0], "s": [H38, 0.5], "y": [-H38, 0.25], "l1_terms": ["+Inf", 1.75],
+            },
+            "group_1e30_1e-30": {
+                "note": "squares as Float64 products: norms 2e30 and 2e-30; as Float32 products they are +Inf and 0.  prox!: sigma lambda / snorm = 0 (alpha = 1) and 0.25 (alpha = 0.75)",
+                "x": [0.0] * 8, "s": [0.0] * 8, "v": [A30] * 4 + [B30] * 4, "gsize": 4, "lambda": [1.0, B30], "sigma": 0.5,
+                "terms": [2 * A30, B30 * (2 * B30)],
+                "prox": [A30] * 4 + [f32(0.75 * B30)] * 4,
+            },
+            "box_slack": {
+                "note": "sj + y = l - sqrt(eps(Float32)) formed in Float32: feasible, psi = lambda |v|; with the Float64 slack 1.49e-8 it is +Inf; one Float32 down is +Inf",
+                "x": [0.0], "s": [0.25], "y": [T_LOW - 0.25], "y_below": [(T_LOW - 2.0 ** -23) - 0.25], "l": -1.5, "u": 1.5,
+                "lambda": 2.0, "psi": 2.0 * -T_LOW,
+            },
+            "binf_radius": {
+                "note": "|sj + y| = 1.6500001 > 1.1 * 1.5 in Float64: +Inf; 1.1f * 1.5f in Float32 is 1.6500001 and would admit it",
+                "x": [0.0], "s": [0.25], "y": [T_OUT - 0.25], "delta": 1.5, "r": 1, "infeasible": True,
+            },
         },
     },
 }

@@ -84,6 +84,12 @@ class Guarded:
     def ptr(self):
         return self.t.data_ptr()
 
+    def set_input(self, p, value):
+        """interior element p of an input rewritten by the test itself: in the buffer and in the snapshot check() compares with"""
+        assert 0 <= p < self.n
+        self.t[p] = value
+        self.snap.view(self.dtype)[self.start // self.es + p] = value
+
     def _first_bad(self, lo, hi):
         """first byte in [lo, hi) of the buffer that differs from the snapshot, or None"""
         if hi <= lo:

@@ -156,14 +156,23 @@ F32 = np.float32
 EPS32 = F32(np.sqrt(np.finfo(np.float32).eps))
 
 
-def _close32(got, exp):
-    if np.isinf(exp) or np.isinf(got):
-        return got == exp
-    return abs(got - exp) <= 4 * np.finfo(np.float32).eps * max(abs(exp), 1e-30)
+def _rounded32(got, terms, factor, what, infeasible=False):
+    """psi(y) as the Python API returns it for Float32 operators: the device's double rounded to Float32.  The double is held
+    to 1e-12 of sum |term| around factor * (the exact sum of the oracle's terms) (tests/nonfinite.py::check_sum's bar), so `got`
+    must be the Float32 rounding of a number in that interval.  (The double itself is checked in tests/test_gpu_f32_exact.py.)"""
+    import math
+    if infeasible:
+        assert got == np.inf, (what, got)
+        return
+    ref = factor * math.fsum(terms.tolist())
+    tol = 1e-12 * factor * math.fsum(np.abs(terms).tolist())
+    assert float(F32(ref - tol)) <= got <= float(F32(ref + tol)), (what, got, ref, tol)
 
 
 @pytest.mark.parametrize("n", [1, 5, 1000, 300_001])
-def test_f32_objective_every_operator(s, n):
+def test_f32_objective_every_operator(s, orc, n):
+    """psi(y) of every operator built on Float32 vectors, through the Python API, against the Float32 restatement of the oracle
+    (oracle.obj_f32 / obj_group_f32: the terms; summed exactly here)."""
     import torch
     rng = np.random.default_rng(3200 + n)
     x = rng.normal(size=n).astype(F32); sj = rng.uniform(-0.5, 0.5, size=n).astype(F32)
@@ -174,49 +183,44 @@ def test_f32_objective_every_operator(s, n):
         if n >= 5:
             y[1] = -(x[1] + sj[1])           # an exact zero of xk + sj + y in Float32 (NormL0 / IndBallL0 count it out)
         yd = torch.from_numpy(y).cuda()
-        xsy = (x + sj) + y                    # float32 + float32, as `@. xsy = xk + sj + y`
-        assert xsy.dtype == np.float32
         t = sj + y
         # unboxed forms (src/ShiftedProximalOperators.jl:51-54)
-        exp = {"l1": np.sum(np.abs(xsy), dtype=np.float64), "l0": float(np.count_nonzero(xsy)),
-               "lhalf": np.sum(np.sqrt(np.abs(xsy)), dtype=np.float64)}
         for H, key in ((s.NormL1, "l1"), (s.NormL0, "l0"), (s.RootNormLhalf, "lhalf")):
+            terms, _ = orc.obj_f32(key, y, x, sj)
             psi = s.shifted(s.shifted(H(float(lam)), xd), sd)
-            assert _close32(psi(yd), float(F32(float(lam) * exp[key]))), (key, n, scale)
+            _rounded32(psi(yd), terms, float(lam), (key, n, scale))
             # Box forms: feasibility of sj + y against [l - sqrt(eps32), u + sqrt(eps32)], all in Float32 (shiftedNormL1Box.jl:70-82)
             for lo, up in ((-10.0, 10.0), (float(t.min()), float(t.max())), (float(t.min()) + 1e-3, 10.0),
                            (float(F32(t.min()) + F32(0.5) * EPS32), 10.0)):
                 lo32, up32 = F32(lo), F32(up)
-                feasible = bool(np.all((F32(lo32 - EPS32) <= t) & (t <= F32(up32 + EPS32))))
+                terms, infeasible = orc.obj_f32(key, y, x, sj, l=lo32, u=up32)
                 pb = s.shifted(s.shifted(H(float(lam)), xd, float(lo32), float(up32)), sd)
-                want = float(F32(float(lam) * exp[key])) if feasible else np.inf
-                assert _close32(pb(yd), want), (key, "box", n, scale, lo, up, feasible)
+                _rounded32(pb(yd), terms, float(lam), (key, "box", n, scale, lo, up), infeasible)
         # IndBallL0 / IndBallL0BInf (count <= r; |sj + y| <= 1.1 Delta with the product in Float64: shiftedIndBallL0BInf.jl:44-49)
-        nnz = int(np.count_nonzero(xsy))
+        nnz = int(orc.obj_f32("l0", y, x, sj)[0].sum())
         for r in (max(nnz - 1, 0), nnz, n):
             if r < 1:
                 continue
             pi = s.shifted(s.shifted(s.IndBallL0(r), xd), sd)
             assert pi(yd) == (0.0 if nnz <= r else np.inf), (n, scale, r)
             for delta in (F32(0.25), F32(np.abs(t).max() / 1.1 * 1.0001), F32(10.0)):
-                inside = bool(np.all(np.abs(t.astype(np.float64)) <= 1.1 * float(delta)))
+                terms, outside = orc.obj_f32("l0", y, x, sj, delta=delta)
                 pbi = s.shifted(s.shifted(s.IndBallL0(r), xd, float(delta), s.NormLinf(1.0)), sd)
-                assert pbi(yd) == (0.0 if (nnz <= r and inside) else np.inf), (n, scale, r, float(delta))
-        # GroupNormL2 / GroupNormL2Binf on uniform groups
+                assert pbi(yd) == (0.0 if (int(terms.sum()) <= r and not outside) else np.inf), (n, scale, r, float(delta))
+        # GroupNormL2 / GroupNormL2Binf on uniform groups (every group size and the CSR layouts: tests/test_gpu_f32_exact.py)
         for gs in (1, 5, 100):
             if n % gs:
                 continue
             ng = n // gs
             lam_g = rng.uniform(0.5, 1.5, size=ng).astype(F32)
-            norms = np.sqrt(np.sum(xsy.astype(np.float64).reshape(ng, gs) ** 2, axis=1))
-            want = float(F32(np.sum(lam_g.astype(np.float64) * norms)))
             h = s.GroupNormL2.uniform(torch.from_numpy(lam_g).cuda(), gs)
             pg = s.shifted(s.shifted(h, xd), sd)
-            assert _close32(pg(yd), want), ("group", n, gs)
+            terms, _, _ = orc.obj_group_f32(y, x, sj, lam_g, gsize=gs)
+            _rounded32(pg(yd), terms, 1.0, ("group", n, gs))
             for delta in (F32(0.25), F32(10.0)):
-                inside = bool(np.all(np.abs(t.astype(np.float64)) <= 1.1 * float(delta)))
+                terms, outside, _ = orc.obj_group_f32(y, x, sj, lam_g, gsize=gs, delta=delta)
                 pgb = s.shifted(s.shifted(h, xd, float(delta), s.NormLinf(1.0)), sd)
-                assert _close32(pgb(yd), want if inside else np.inf), ("group binf", n, gs, float(delta))
+                _rounded32(pgb(yd), terms, 1.0, ("group binf", n, gs, float(delta)), outside)
 
 
 def test_f32_reference_type_block(s):
@@ -276,7 +280,13 @@ def test_strided_xk_views(s, orc, dtype):
     assert torch.equal(bd[::st], new)
     mask = torch.ones(n * st, dtype=torch.bool, device="cuda"); mask[::st] = False
     assert torch.equal(bd[mask], others[mask])         # nothing between the strided elements was touched
-    assert abs(parent(torch.zeros(n, dtype=td, device="cuda")) - float(new.abs().sum())) <= 1e-5 * float(new.abs().sum())
+    got = parent(torch.zeros(n, dtype=td, device="cuda"))
+    if dtype == "float32":   # the terms of the Float32 restatement, summed exactly (the API rounds the device's double to Float32)
+        z = np.zeros(n, dtype=nd)
+        terms, infeasible = orc.obj_f32("l1", z, new.cpu().numpy(), z, l=-1.0, u=1.0)
+        _rounded32(got, terms, 1.0, "strided xk", infeasible)
+    else:
+        assert abs(got - float(new.abs().sum())) <= 1e-5 * float(new.abs().sum())
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -429,42 +439,24 @@ def test_f32_topr_folded_first_digit(s, orc, kind, n):
 # ------------------------------------------------------------------------------------------------------------------
 # ShiftedGroupNormL2 in Float32 (round 3): elementwise operations in Float32, the norm to a Float32 ulp
 # ------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("gs", [1, 2, 3, 4, 7, 9, 16, 33, 64, 128, 1000])
-def test_f32_group_l2(s, gs):
-    """uniform groups and ragged CSR groups (incl. indices in no group: y - (xk + sj), src/shiftedGroupNormL2.jl:77), y === q.
-    Reference: the method restated in numpy with Float32 operations and the norm formed in Float64 and rounded once (the
-    reference's own `norm` is BLAS / a generic loop: neither pins the last ulp) -- bar 1e-6 of the operands' scale."""
+@pytest.mark.parametrize("gs", __import__("f32_exact").API_GROUP_SIZES)
+def test_f32_group_l2(s, orc, gs):
+    """uniform groups through the Python API, then y === q: bit for bit against the restatement (oracle.prox_group_l2_f32) with
+    every group's exact norm rounded to Float32 once; a group whose exact norm lies within 1e-12 of a Float32 rounding boundary
+    may take either neighbour's result (tests/f32_exact.py: census, check_prox).  Ragged CSR groups, empty groups and indices in
+    no group (y on entry - (xk + sj), src/shiftedGroupNormL2.jl:77) run through the C ABI in tests/test_gpu_f32_exact.py."""
     import torch
-    rng = np.random.default_rng(500 + gs)
-    ng = 3000
-    n = ng * gs
-    x, sj, q = _data(n, 500 + gs)
-    lam = rng.uniform(0.2, 3.0, size=ng).astype(np.float32)
-    sigma = np.float32(0.8)
-
-    def ref(offs, y_in):
-        S = ((q + x) + sj).astype(np.float32)
-        y = y_in.copy()
-        for g in range(len(offs) - 1):
-            lo, hi = offs[g], offs[g + 1]
-            sn = np.float32(np.sqrt(np.sum(S[lo:hi].astype(np.float64) ** 2)))
-            if sn == 0:
-                y[lo:hi] = 0
-            else:
-                a = np.maximum(np.float32(1) - sigma * lam[g] / sn, np.float32(0))
-                y[lo:hi] = a * S[lo:hi]
-        return (y - (x + sj)).astype(np.float32), S
-
+    import f32_exact as fx
+    lay, d, sigma = fx.api_group_case(gs)        # (its census holds the cap: tests/test_oracle_f32_forms.py, on the CPU)
+    n, ng = lay[1], lay[4]
+    x, sj, q, lam = d["x"], d["sj"], d["q"], d["lam"]
+    ref, amb, alts = fx.prox_reference(orc, lay, d, sigma=sigma)
     xd, sd, qd = _dev(x, sj, q)
     h = s.GroupNormL2.uniform(torch.from_numpy(lam).cuda(), gs)
     psi = s.shifted(s.shifted(h, xd), sd)
     assert psi.f32
     y = s.prox(psi, qd, float(sigma)).cpu().numpy()
-    offs = np.arange(0, n + 1, gs)
-    want, S = ref(offs, np.zeros(n, dtype=np.float32))
-    nrm = np.repeat(np.sqrt(np.add.reduceat(S.astype(np.float64) ** 2, offs[:-1])), gs)
-    scale = np.maximum(np.maximum(np.abs(want), np.abs(x + sj)), nrm)
-    assert np.all(np.abs(y - want) <= 1e-6 * np.maximum(scale, 1e-30)), float(np.max(np.abs(y - want) / np.maximum(scale, 1e-30)))
+    fx.check_prox(y, lay, ref, amb, alts, "gs %d" % gs)
     qa = qd.clone()
     s.prox_bang(qa, psi, qa, float(sigma))                 # y === q
-    assert np.all(np.abs(qa.cpu().numpy() - want) <= 1e-6 * np.maximum(scale, 1e-30))
+    fx.check_prox(qa.cpu().numpy(), lay, ref, amb, alts, "gs %d, y === q" % gs)

@@ -7,7 +7,10 @@ case runs on a workspace that another family has just left dirty, as a real call
 
 Sizes sit on both sides of each dispatch boundary (the comments name it); alignment modes for Float64 (redzone.F64_MODES):
 A all vectors 16-byte aligned (the vec forms), B all at +8 B (the ioff forms of top-r, the 8-byte forms elsewhere), C y aligned
-and the inputs at +8 B (non-vec, non-ioff forms), D y aliases q.  Float32 vectors sit at +0, +4, +8, +12 B."""
+and the inputs at +8 B (non-vec, non-ioff forms), D y aliases q.  Float32 vectors sit at +0, +4, +8, +12 B.
+
+The Float32 psi(y) and group prox cases are held to the Float32 restatement of the oracle with the bars of tests/f32_exact.py
+(check_sum at 1e-12 of sum |term|; the bit rule); tests/test_gpu_f32_exact.py runs those entry points at every size and edge."""
 import ctypes
 import itertools
 import zlib
@@ -16,6 +19,8 @@ import numpy as np
 import pytest
 
 import arbiter
+import f32_exact
+import nonfinite
 import redzone
 
 pytestmark = pytest.mark.gpu
@@ -319,7 +324,9 @@ def _obj(c, op, n, fewer, f32):
         kind = op[:-4]
         c.call("spx_obj_%s%s" % (op, sfx), yb.ptr(), xb.ptr(), sb.ptr(), n, P(lam), lb.ptr(), ub.ptr(), P(0.0), P(0.0), mb.ptr(),
                ctypes.byref(val))
-        ref = _obj_ref_f32(kind, y, x, sj, lam, l, u, mask) if f32 else c.orc.obj_box(kind, y, x, sj, lam, l, u, mask)
+        if f32:
+            return _obj_f32_check(c, op, n, val.value, lam, *c.orc.obj_f32(kind, y, x, sj, l=l, u=u, mask=mask))
+        ref = c.orc.obj_box(kind, y, x, sj, lam, l, u, mask)
     elif op.startswith("indball"):
         r = max(n // 2, 1)
         if op == "indball_binf":
@@ -327,32 +334,36 @@ def _obj(c, op, n, fewer, f32):
         else:
             c.call("spx_obj_indball_l0" + sfx, yb.ptr(), xb.ptr(), sb.ptr(), n, r, ctypes.byref(val))
         d = delta if op == "indball_binf" else None
-        ref = c.orc.obj_indball_l0(np.float64(y), np.float64(x), np.float64(sj), r, delta=d)
-        if not f32:
-            # a count over n elements: exact.  Every y of this data has more than r nonzeros: +Inf
-            assert val.value == ref, (op, n, val.value, ref)
+        if f32:   # the count of the Float32 terms and the Float64 ball test of the Float32 restatement: exact
+            terms, outside = c.orc.obj_f32("l0", y, x, sj, delta=d)
+            assert val.value == (np.inf if outside or int(terms.sum()) > r else 0.0), (op, n, val.value)
             c.finish()
             return
+        ref = c.orc.obj_indball_l0(y, x, sj, r, delta=d)
+        # a count over n elements: exact.  Every y of this data has more than r nonzeros: +Inf
+        assert val.value == ref, (op, n, val.value, ref)
+        c.finish()
+        return
     else:
         c.call("spx_obj_%s%s" % (op, sfx), yb.ptr(), xb.ptr(), sb.ptr(), n, P(lam), ctypes.byref(val))
-        ref = _obj_ref_f32(op, y, x, sj, lam) if f32 else c.orc.obj_plain(op, y, x, sj, lam)
-    tol = 1e-6 if f32 else 1e-12
-    assert val.value == ref or abs(val.value - ref) <= tol * abs(ref), (op, n, f32, val.value, ref)
+        if f32:
+            return _obj_f32_check(c, op, n, val.value, lam, *c.orc.obj_f32(op, y, x, sj))
+        ref = c.orc.obj_plain(op, y, x, sj, lam)
+    assert val.value == ref or abs(val.value - ref) <= 1e-12 * abs(ref), (op, n, val.value, ref)
     c.finish()
 
 
-def _obj_ref_f32(kind, y, x, sj, lam, l=None, u=None, mask=None):
-    """psi(y) of the Float32 forms restated: the element operations in Float32, the sum in Float64 (no Float32 oracle)"""
-    v = ((x + sj).astype(np.float32) + y).astype(np.float32).astype(np.float64)
-    if l is not None:
-        t = (sj + y).astype(np.float32)
-        sl = np.float32(3.4526698300124393e-04)
-        if not np.all(((l - sl).astype(np.float32) <= t) & (t <= (u + sl).astype(np.float32))):
-            return np.inf
-        v = v[mask != 0]
-    if kind == "l0":
-        return float(np.float32(lam)) * float(np.count_nonzero(v))
-    return float(np.float32(lam)) * float(np.sum(np.abs(v)))
+def _obj_f32_check(c, op, n, got, lam, terms, infeasible):
+    """a Float32 psi(y) against the terms of the Float32 restatement (oracle.obj_f32), summed exactly: the bar of the step
+    statistics, 1e-12 of sum |term| times (double)lambda; NormL0 is one rounded product of a count; +Inf decisions are exact"""
+    factor = float(np.float32(lam))
+    if infeasible:
+        assert got == np.inf, (op, n, got)
+    elif op.startswith("l0"):
+        assert got == factor * float(int(terms.sum())), (op, n, got)
+    else:
+        nonfinite.check_sum(got, terms, "obj-f32 %s n=%d" % (op, n), factor=factor)
+    c.finish()
 
 
 def _layout(lay, rng):
@@ -415,11 +426,14 @@ def _obj_group(c, lay, binf, fewer, f32):
     else:
         ob = c.ints(offsets, n, "offsets") if offsets is not None else None
         c.call(name + sfx, yb.ptr(), xb.ptr(), sb.ptr(), n, ob.ptr() if ob else None, gsize, ng, lb.ptr(), *tail, ctypes.byref(val))
-        if f32:   # the element operations in Float32, the norms in Float64: xsy formed here, the oracle adds zeros to it
-            y, x, sj = ((x + sj).astype(np.float32) + y).astype(np.float64), np.zeros(n), np.zeros(n)
-        ref = c.orc.obj_group_l2(y, x, sj, np.float64(lam), offsets=offsets, gsize=gsize, delta=delta if binf else None)
-    tol = 1e-6 if f32 else 1e-12
-    assert val.value == ref or abs(val.value - ref) <= tol * abs(ref), (lay, binf, fewer, f32, val.value, ref)
+        if f32:   # the per-group terms of the Float32 restatement, summed exactly
+            terms, outside, bad = c.orc.obj_group_f32(y, x, sj, lam, offsets=offsets, gsize=gsize, delta=delta if binf else None)
+            assert not outside and not bad
+            nonfinite.check_sum(val.value, terms, "objgrp-f32 " + lay)
+            c.finish()
+            return
+        ref = c.orc.obj_group_l2(y, x, sj, lam, offsets=offsets, gsize=gsize, delta=delta if binf else None)
+    assert val.value == ref or abs(val.value - ref) <= 1e-12 * abs(ref), (lay, binf, fewer, val.value, ref)
     c.finish()
 
 
@@ -534,11 +548,27 @@ def _group_cases():
                 out.append(("grp-%s-binf%d%s" % (lay, binf, "".join("-k%d_%d" % kv for kv in k.items())),
                             lambda c, lay=lay, b=binf, k=k: _group(c, lay, b, keys=k)))
     for lay in ("uniform", "ragged"):
-        out.append(("grp-f32-%s" % lay, lambda c, lay=lay: _group(c, lay, False, gs=16, f32=True)))
+        out.append(("grp-f32-%s" % lay, lambda c, lay=lay: _group_f32(c, lay)))
     return out
 
 
-def _group(c, lay, binf, gs=0, keys=None, f32=False):
+def _group_f32(c, name):
+    """spx_prox_group_l2_f32 on guarded buffers: the bit rule of tests/f32_exact.py -- the restatement with every group's exact
+    norm rounded once; a group within 1e-12 of a rounding boundary of its norm may take either neighbour's result (the census of
+    these seeds holds its cap: tests/test_oracle_f32_forms.py, on the CPU)"""
+    t = c.torch
+    lay, d, sigma = f32_exact.redzone_group_case(name)
+    _, n, offsets, gs, ng, _ = lay
+    y = c.out(n, 0, t.float32)
+    qb, xb, sb, lb = (c.vec(d[k], 0, t.float32, name=nm) for k, nm in (("q", "q"), ("x", "xk"), ("sj", "sj"), ("lam", "lambda")))
+    ob = c.ints(offsets, n, "offsets") if offsets is not None else None
+    c.call("spx_prox_group_l2_f32", y.ptr(), qb.ptr(), xb.ptr(), sb.ptr(), n, ob.ptr() if ob else None, gs, ng, lb.ptr(), _F(float(sigma)))
+    ref, amb, alts = f32_exact.prox_reference(c.orc, lay, d, sigma=sigma)
+    f32_exact.check_prox(y.t.cpu().numpy(), lay, ref, amb, alts, "grp-f32-" + name)
+    c.finish()
+
+
+def _group(c, lay, binf, gs=0, keys=None):
     t = c.torch
     rng = _rng("g%s%d%d" % (lay, gs, binf))
     groups = offsets = None
@@ -581,11 +611,9 @@ def _group(c, lay, binf, gs=0, keys=None, f32=False):
     sigma, delta = 0.9, 0.8
     for k, v in (keys or {}).items():
         c.tune(k, v)
-    dt = t.float32 if f32 else t.float64
-    if f32:
-        x, sj, q, lam = (v.astype(np.float32) for v in (x, sj, q, lam))
+    dt = t.float64
     if lay in ("uncovered", "empty"):   # (y outside the groups: the shift-only entries, or y on entry)
-        y = c.zone.add(n, dt, 0, data=np.zeros(n, dtype=np.float32 if f32 else np.float64), role="inout", name="y")
+        y = c.zone.add(n, dt, 0, data=np.zeros(n), role="inout", name="y")
     else:
         y = c.out(n, 0, dt)
     qb, xb, sb, lb = c.vec(q, 0, dt, name="q"), c.vec(x, 0, dt, name="xk"), c.vec(sj, 0, dt, name="sj"), c.vec(lam, 0, dt, name="lambda")
@@ -605,16 +633,6 @@ def _group(c, lay, binf, gs=0, keys=None, f32=False):
         c.finish()
         return
     ob = c.ints(offsets, n, "offsets") if offsets is not None else None
-    if f32:
-        c.call("spx_prox_group_l2_f32", y.ptr(), qb.ptr(), xb.ptr(), sb.ptr(), n, ob.ptr() if ob else None, gs if ob is None else 0, ng,
-               lb.ptr(), _F(sigma))
-        ref = c.orc.prox_group_l2(np.float64(q), np.float64(x), np.float64(sj), np.float64(lam), sigma,
-                                  offsets=offsets, gsize=gs if offsets is None else 0)
-        got = y.t.cpu().numpy().astype(np.float64)
-        S = np.abs((np.float64(q) + x) + sj)
-        assert np.all(np.abs(got - ref) <= 1e-5 * np.maximum(np.maximum(np.abs(ref), S), 1.0)), (lay,)
-        c.finish()
-        return
     c.call(name, y.ptr(), qb.ptr(), xb.ptr(), sb.ptr(), n, ob.ptr() if ob else None, bound if ob else gs, ng, lb.ptr(), _D(sigma), *tail)
     offs = offsets if offsets is not None else np.arange(0, n + 1, gs)
     if binf:

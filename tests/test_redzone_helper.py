@@ -103,3 +103,15 @@ def test_modes():
     assert set(redzone.F64_MODES) == {"A", "B", "C", "D"}
     for k, (ay, ai) in redzone.F64_MODES.items():
         assert ay % 8 == 0 and ai % 8 == 0
+
+
+def test_set_input_moves_the_snapshot_with_the_element():
+    """an input element the test rewrites itself passes check(); the same element written behind the helper's back does not"""
+    x = np.arange(7, dtype=np.float32)
+    g = redzone.guarded(7, torch.float32, 12, data=x, device="cpu", name="x")
+    g.set_input(3, 2.5)
+    assert g.a[3] == np.float32(2.5)
+    g.check()
+    g.t[3] = 1.0
+    with pytest.raises(AssertionError, match="read-only input changed at interior element 3"):
+        g.check()
