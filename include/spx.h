@@ -88,7 +88,9 @@ int spx_sync(spx_ctx* ctx);
  * the host and synchronise the stream.  With a non-NULL device_value they store it in that DEVICE double instead (one
  * 8-byte store by the last kernel of the call) and return after enqueueing: the host `*value` is then set to NaN and
  * nothing is read back -- a solver's accept / reject test can consume the value on the device, or copy it later.
- * NULL restores the default.  (An out-of-range gather index cannot be reported from an asynchronous call: the device
+ * NULL restores the default.  An empty call (n == 0; for the group forms also ngroups == 0) of every one of these entry
+ * points stores 0 in the device double (by a kernel, no memset node) and leaves the host `*value` as without a target: 0,
+ * lambda * 0 for the separable spx_proxval_*.  (An out-of-range gather index cannot be reported from an asynchronous call: the device
  * value is NaN then.)  Mirrors no reference function: psi(y) in the reference returns a host Float64
  * (src/ShiftedProximalOperators.jl:51-54); this is the asynchronous form of the same value. */
 int spx_ctx_set_value_target(spx_ctx* ctx, double* device_value);

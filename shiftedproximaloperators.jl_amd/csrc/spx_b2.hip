@@ -1022,12 +1022,10 @@ __global__ void k_b2_obj_value(const B2Ws* ws, double lambda, double delta, doub
 
 // ShiftedNormL1B2 as a function (src/shiftedNormL1B2.jl:32).  IndBallL2(Delta)(v) [ext: ProximalOperators.jl] is 0 iff
 // ||v|| <= Delta or ||v|| ~ Delta (isapprox, atol = eps, rtol = sqrt(eps)), +Inf otherwise.
-SPX_EXPORT int spx_obj_l1_b2(spx_ctx* ctx, const double* y, const double* xk, const double* sj, int64_t n,
-                             double lambda, double delta, double* value) {
-  SPX_REQUIRE(ctx != nullptr && value != nullptr, "ctx or value is NULL");
-  SPX_REQUIRE(n >= 0, "n < 0");
-  *value = 0.0;
-  double P = 0.0, C = 0.0;
+static int obj_l1_b2(spx_ctx* ctx, const double* y, const double* xk, const double* sj, int64_t n, double lambda, double delta,
+                     const SpxDest& dest) {
+  spx_dest_zero_host(dest);
+  double pc[2] = {0.0, 0.0};  // P, C
   if (n > 0) {
     SPX_REQUIRE(y && xk && sj, "NULL vector with n > 0");
     int rc = spx_ws_reserve(ctx, sizeof(B2Ws) + 256);
@@ -1042,28 +1040,35 @@ SPX_EXPORT int spx_obj_l1_b2(spx_ctx* ctx, const double* y, const double* xk, co
     else hipLaunchKernelGGL((k_b2_obj<false>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, y, xk, sj, n, ws);
     hipLaunchKernelGGL(k_b2_reduce, dim3(1), dim3(256), 0, ctx->stream, ws, (int)blocks, 0);
     SPX_LAUNCH_CHECK();
-    if (ctx->value_target) {  // device-resident value: psi(y) from (P, C) on the device, nothing read back
-      hipLaunchKernelGGL(k_b2_obj_value, dim3(1), dim3(1), 0, ctx->stream, (const B2Ws*)ws, lambda, delta, ctx->value_target);
+    if (dest.dev) {  // device-resident value: psi(y) from (P, C) on the device, nothing read back
+      hipLaunchKernelGGL(k_b2_obj_value, dim3(1), dim3(1), 0, ctx->stream, (const B2Ws*)ws, lambda, delta, dest.dev);
       SPX_LAUNCH_CHECK();
-      *value = std::nan("");
       return SPX_OK;
     }
-    double pc[2];
-    { const int rcc = spx_require_not_capturing(ctx, "returning psi(y) to the host"); if (rcc) return rcc; }
-    SPX_HIP(hipMemcpyAsync(pc, &ws->P, sizeof(pc), hipMemcpyDeviceToHost, ctx->stream));
-    SPX_HIP(hipStreamSynchronize(ctx->stream));
-    P = pc[0];
-    C = pc[1];
-  } else if (ctx->value_target) {
-    { const int rz = spx_zero_async(ctx, ctx->value_target, sizeof(double)); if (rz) return rz; }
-    return SPX_OK;
+    rc = spx_dest_check_capture(ctx, dest, "returning psi(y) to the host");
+    if (rc) return rc;
+    rc = spx_dest_return(ctx, dest, &ws->P, sizeof(pc), pc);
+    if (rc) return rc;
+  } else if (dest.dev) {
+    return spx_dest_empty(ctx, dest);
   }
+  const double P = pc[0], C = pc[1];
   const double nrm = std::sqrt(C);
   const double eps = 2.220446049250313e-16;
   const double tol = std::fmax(eps, std::sqrt(eps) * std::fmax(nrm, std::fabs(delta)));
   const bool inside = (nrm <= delta) || (std::fabs(nrm - delta) <= tol);
-  *value = inside ? lambda * P : INFINITY;
+  *dest.host = inside ? lambda * P : INFINITY;
   return SPX_OK;
+}
+SPX_EXPORT int spx_obj_l1_b2(spx_ctx* ctx, const double* y, const double* xk, const double* sj, int64_t n,
+                             double lambda, double delta, double* value) {
+  SPX_REQUIRE(ctx != nullptr && value != nullptr, "ctx or value is NULL");
+  SPX_REQUIRE(n >= 0, "n < 0");
+  const SpxDest dest = spx_value_dest(ctx, value);
+  *value = 0.0;
+  const int rc = obj_l1_b2(ctx, y, xk, sj, n, lambda, delta, dest);
+  spx_value_nan_on_device(rc, dest, n == 0, value);
+  return rc;
 }
 
 namespace {
@@ -1101,31 +1106,24 @@ void b2_with_form(B2Form form, Fn&& fn) {
     default: fn(std::integral_constant<int, kB2Form8>{}); break;
   }
 }
-struct B2StepArgs {
-  double* xkn;
-  double* stats;
-  double* stats_dev;
-};
 int b2_step_composed(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n, double lambda,
-                     double sigma, double delta, double chi_lambda, double q_scale, const B2StepArgs& st);
+                     double sigma, double delta, double chi_lambda, double q_scale, double* xkn, const SpxDest& dest);
 
-// One host body for spx_prox_l1_b2 (VALUE = false: q_scale and value are not looked at) and spx_proxval_l1_b2.  The form and
+// One host body for spx_prox_l1_b2 (VALUE = false: q_scale and dest are not looked at) and spx_proxval_l1_b2.  The form and
 // the grid are chosen from the PLAIN kernels' residency in both: y's bits depend on the grid (the partition of every sum).
-// STEP (spx_proxstep_l1_b2, st != NULL; the arguments were checked by the entry point, n > 0): the same choice of form and grid
+// STEP (spx_proxstep_l1_b2: dest is that of the three statistics; the entry point has checked the arguments, n > 0): the same choice of
+// form and grid
 // -- xkn takes no part in it and does not change can_spec -- and then either the STEP kernel of the form or the composed route.
 template <bool VALUE, bool STEP = false>
 int run_b2(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n, double lambda, double sigma,
-           double delta, double chi_lambda, double q_scale, double* value, const B2StepArgs* st = nullptr) {
-  if constexpr (VALUE && !STEP) SPX_REQUIRE(value != nullptr, "value is NULL");
+           double delta, double chi_lambda, double q_scale, const SpxDest& dest = {nullptr, nullptr, 0}, double* xkn = nullptr) {
   int rc = spx_check_common(ctx, y, q, xk, sj, n);
   if (rc) return rc;
   if constexpr (VALUE && !STEP) {
-    if (!ctx->value_target) {  // (refused before anything is enqueued)
-      const int rcc = spx_require_not_capturing(ctx, "returning the value to the host");
-      if (rcc) return rcc;
-    }
-    *value = 0.0;
-    if (n == 0 && ctx->value_target) return spx_zero_async(ctx, ctx->value_target, sizeof(double));
+    rc = spx_dest_check_capture(ctx, dest, "returning the value to the host");  // (refused before anything is enqueued)
+    if (rc) return rc;
+    if (n == 0) return spx_dest_empty(ctx, dest);
+    spx_dest_zero_host(dest);
   }
   if (n == 0) return SPX_OK;
   SPX_ON_DEVICE(ctx);
@@ -1164,7 +1162,7 @@ int run_b2(spx_ctx* ctx, double* y, const double* q, const double* xk, const dou
   const B2Form form = ldsx ? kB2FormLds : reg ? kB2FormReg : vec ? kB2FormVec : kB2Form8;
   if constexpr (STEP) {
     if (ctx->tune_b2_step_compose || !kB2StepFused[form])
-      return b2_step_composed(ctx, y, q, xk, sj, n, lambda, sigma, delta, chi_lambda, q_scale, *st);
+      return b2_step_composed(ctx, y, q, xk, sj, n, lambda, sigma, delta, chi_lambda, q_scale, xkn, dest);
   }
   if constexpr (VALUE) {
     // FUSED on all four forms: the VALUE kernel of the form runs with the grid chosen above (same LDS, same lanes per workgroup as
@@ -1222,16 +1220,16 @@ int run_b2(spx_ctx* ctx, double* y, const double* q, const double* xk, const dou
       if constexpr (STEP) {
         B2Step bs{};
         static_cast<B2Val&>(bs) = B2Val{q_scale, lambda, nullptr};
-        bs.xkn = st->xkn;
-        bs.res_hdr = st->stats ? hdr->b2_step : nullptr;
-        bs.res_dev = st->stats_dev;
-        bs.xvec = spx_aligned16(st->xkn) ? 1 : 0;
+        bs.xkn = xkn;
+        bs.res_hdr = dest.host ? hdr->b2_step : nullptr;
+        bs.res_dev = dest.dev;
+        bs.xvec = spx_aligned16(xkn) ? 1 : 0;
         hipLaunchKernelGGL(kern, dim3((unsigned)g), dim3(threads), 0, ctx->stream, y, q, xk, sj, n, ls, delta, chi_lambda, rows,
                            clear_rows, clear_g, hdr, can_spec, cand, cand_cap, bs);
       } else if constexpr (VALUE)
         hipLaunchKernelGGL(kern, dim3((unsigned)g), dim3(threads), 0, ctx->stream, y, q, xk, sj, n, ls, delta, chi_lambda, rows,
                            clear_rows, clear_g, hdr, can_spec, cand, cand_cap,
-                           B2Val{q_scale, lambda, ctx->value_target ? ctx->value_target : &hdr->b2_value});
+                           B2Val{q_scale, lambda, dest.dev ? dest.dev : &hdr->b2_value});
       else
         hipLaunchKernelGGL(kern, dim3((unsigned)g), dim3(threads), 0, ctx->stream, y, q, xk, sj, n, ls, delta, chi_lambda, rows,
                            clear_rows, clear_g, hdr, can_spec, cand, cand_cap);
@@ -1249,19 +1247,7 @@ int run_b2(spx_ctx* ctx, double* y, const double* q, const double* xk, const dou
     ctx->track.b2_set = other;
   }
   SPX_LAUNCH_CHECK();
-  if constexpr (STEP) {
-    if (st->stats == nullptr) return SPX_OK;  // device results only: the call returns after enqueueing
-    SPX_HIP(hipMemcpyAsync(st->stats, hdr->b2_step, 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    SPX_HIP(hipStreamSynchronize(ctx->stream));
-    return SPX_OK;
-  } else if constexpr (VALUE) {
-    if (ctx->value_target) {  // device-resident value: nothing is read back, the call returns after enqueueing
-      *value = std::nan("");
-      return SPX_OK;
-    }
-    SPX_HIP(hipMemcpyAsync(value, &hdr->b2_value, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    SPX_HIP(hipStreamSynchronize(ctx->stream));
-  }
+  if constexpr (VALUE) return spx_dest_return(ctx, dest, STEP ? hdr->b2_step : &hdr->b2_value, (size_t)dest.count * sizeof(double));
   return SPX_OK;
 }
 
@@ -1269,36 +1255,37 @@ int run_b2(spx_ctx* ctx, double* y, const double* q, const double* xk, const dou
 
 SPX_EXPORT int spx_prox_l1_b2(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
                               double lambda, double sigma, double delta, double chi_lambda) {
-  return run_b2<false>(ctx, y, q, xk, sj, n, lambda, sigma, delta, chi_lambda, 1.0, nullptr);
+  return run_b2<false>(ctx, y, q, xk, sj, n, lambda, sigma, delta, chi_lambda, 1.0);
 }
 
 // prox! fused with h at the result (include/spx.h): the value comes out of the launch that stores y, on every form.
 SPX_EXPORT int spx_proxval_l1_b2(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
                                  double lambda, double sigma, double delta, double chi_lambda, double q_scale, double* value) {
-  return run_b2<true>(ctx, y, q, xk, sj, n, lambda, sigma, delta, chi_lambda, q_scale, value);
+  SPX_REQUIRE(value != nullptr, "value is NULL");
+  const SpxDest dest = spx_value_dest(ctx, value);
+  *value = 0.0;
+  const int rc = run_b2<true>(ctx, y, q, xk, sj, n, lambda, sigma, delta, chi_lambda, q_scale, dest);
+  spx_value_nan_on_device(rc, dest, n == 0, value);
+  return rc;
 }
 
 namespace {
 
 // The composed route of spx_proxstep_l1_b2 (forms whose STEP kernel would spill more than their VALUE twin; every form under
-// tuning key 18 = 1): the unchanged run_b2<VALUE> -- y and h, h kept on the device in SpxSyncHeader::b2_step[0] -- then the
+// tuning key 18 = 1): the unchanged run_b2<VALUE> with SpxSyncHeader::b2_step[0] as its device destination -- y and h -- then the
 // streaming launch the group operators' composed routes end in (spx_step_tail_*, spx_group.hip) for xkn and the two sums, which
 // also hands h on to the result slots.  Its workspace is reserved before anything is enqueued.
 int b2_step_composed(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n, double lambda,
-                     double sigma, double delta, double chi_lambda, double q_scale, const B2StepArgs& st) {
-  const SpxStepTail tail = spx_step_tail_plan(ctx, y, q, xk, sj, st.xkn, n);
+                     double sigma, double delta, double chi_lambda, double q_scale, double* xkn, const SpxDest& dest) {
+  const SpxStepTail tail = spx_step_tail_plan(ctx, y, q, xk, sj, xkn, n);
   int rc = spx_ws_reserve(ctx, tail.bytes);
   if (rc) return rc;
   rc = spx_sync_ready(ctx);
   if (rc) return rc;
   SpxSyncHeader* hdr = spx_sync_header(ctx);
-  double* const caller_target = ctx->value_target;  // (does not apply to this call: h goes to the library's own word)
-  ctx->value_target = &hdr->b2_step[0];
-  double unused;
-  rc = run_b2<true>(ctx, y, q, xk, sj, n, lambda, sigma, delta, chi_lambda, q_scale, &unused);
-  ctx->value_target = caller_target;
+  rc = run_b2<true>(ctx, y, q, xk, sj, n, lambda, sigma, delta, chi_lambda, q_scale, {nullptr, &hdr->b2_step[0], 1});
   if (rc) return rc;
-  return spx_step_tail_run(ctx, tail, q, y, xk, sj, st.xkn, n, &hdr->b2_step[0], st.stats, st.stats_dev);
+  return spx_step_tail_run(ctx, tail, q, y, xk, sj, xkn, n, &hdr->b2_step[0], dest);
 }
 
 }  // namespace
@@ -1310,17 +1297,9 @@ SPX_EXPORT int spx_proxstep_l1_b2(spx_ctx* ctx, double* y, const double* q, cons
                                   double* stats, double* stats_dev) {
   int rc = spx_check_common(ctx, y, q, xk, sj, n);
   if (rc) return rc;
-  SPX_REQUIRE(stats != nullptr || stats_dev != nullptr, "stats and stats_dev are both NULL");
-  SPX_REQUIRE(y == nullptr || y != q, "y aliases q (<q, y> of an overwritten q)");
-  if (xkn != nullptr) SPX_REQUIRE(xkn != y && xkn != q && xkn != xk && xkn != sj, "xkn is one of the other vectors");
-  // the host copy synchronises: refused under a capture before anything is enqueued
-  if (stats != nullptr) { rc = spx_require_not_capturing(ctx, "returning the step statistics to the host (pass stats = NULL)"); if (rc) return rc; }
-  if (stats) stats[0] = stats[1] = stats[2] = 0.0;
-  if (n == 0) {
-    if (stats_dev == nullptr) return SPX_OK;
-    SPX_ON_DEVICE(ctx);
-    return spx_zero_async(ctx, stats_dev, 3 * sizeof(double));  // (a kernel, not a memset node)
-  }
-  const B2StepArgs st{xkn, stats, stats_dev};
-  return run_b2<true, true>(ctx, y, q, xk, sj, n, lambda, sigma, delta, chi_lambda, q_scale, nullptr, &st);
+  const SpxDest dest{stats, stats_dev, 3};
+  rc = spx_step_begin(ctx, dest, false, y, {q}, kSpxYAliasesQ, xkn, {y, q, xk, sj});
+  if (rc) return rc;
+  if (n == 0) return spx_dest_empty(ctx, dest);
+  return run_b2<true, true>(ctx, y, q, xk, sj, n, lambda, sigma, delta, chi_lambda, q_scale, dest, xkn);
 }

@@ -5,6 +5,7 @@
 
 #include <cstdarg>
 #include <cstdio>
+#include <initializer_list>
 
 #include "spx.h"
 
@@ -48,7 +49,8 @@ struct spx_ctx {
   // launch is preceded by a memset of exactly the state it uses (a node of the same graph) and the sets are fixed.
   int graph_safe = 0;
   // spx_ctx_set_value_target: when non-NULL, the value-returning entry points (spx_obj_*, spx_proxval_*) store their
-  // result in this DEVICE double and return after enqueueing, without the read-back / stream synchronisation
+  // result in this DEVICE double and return after enqueueing, without the read-back / stream synchronisation.  Read once per
+  // call, by spx_value_dest at the entry point; never written outside spx_ctx.hip
   double* value_target = nullptr;
   // tuning knobs (spx_ctx_set_tuning): per context, so that two contexts / threads never see each other's experiments
   int tune_sep_blocks_per_cu = 0;  // key 0: 0 = no cap (one tile per workgroup)
@@ -136,7 +138,7 @@ int spx_group_team_launch(spx_ctx* ctx, bool binf, double* y, const double* q, c
 
 // The streaming launch that the composed routes of spx_proxstep_group_* and spx_proxstep_l1_b2 end in (spx_group.hip): after a
 // value call has stored y and left h in the device double *h, ONE launch stores xkn = (xk + sj) + y (xkn may be NULL) and forms
-// <q, y> and <y, y>; its last workgroup stores {*h, <q, y>, <y, y>} to stats_dev and / or reads them back to stats.
+// <q, y> and <y, y>; its last workgroup stores {*h, <q, y>, <y, y>} to the device destination; a host destination reads them back.
 // plan: the launch shape and the workspace it needs from offset 0 of spx_ctx::ws (reserve it before the call's first launch; the
 // value call may use the same bytes, it has finished with them on the stream before the tail runs).
 struct SpxStepTail {
@@ -146,8 +148,9 @@ struct SpxStepTail {
 };
 SpxStepTail spx_step_tail_plan(spx_ctx* ctx, const double* y, const double* q, const double* xk, const double* sj, const double* xkn,
                                int64_t n);
+struct SpxDest;
 int spx_step_tail_run(spx_ctx* ctx, const SpxStepTail& tail, const double* q, const double* y, const double* xk, const double* sj,
-                      double* xkn, int64_t n, const double* h, double* stats, double* stats_dev);
+                      double* xkn, int64_t n, const double* h, const SpxDest& dest);
 
 // Two launches that synchronise inside themselves must not run side by side on one device: each would hold CUs while it
 // waits for workgroups of its own that cannot be placed.  Contexts on different streams are therefore chained through one
@@ -218,6 +221,68 @@ static inline int spx_check_common(spx_ctx* ctx, const void* y, const void* q, c
 }
 
 static inline bool spx_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// ---------------------------------------------------------------------------------------------
+// Where the `count` doubles that a call returns next to y go.  Built once, at the entry point, and passed down as an argument:
+// nothing below an entry point looks at spx_ctx::value_target.
+// ---------------------------------------------------------------------------------------------
+struct SpxDest {
+  double* host;  // non-NULL: the result is read back and the stream synchronised (refused under a capture)
+  double* dev;   // the caller's device doubles, or NULL
+  int count;
+};
+// A value call (spx_obj_*, spx_proxval_*): the context's device target if it has one, else the caller's host double.
+static inline SpxDest spx_value_dest(const spx_ctx* ctx, double* value) {
+  double* const target = ctx ? ctx->value_target : nullptr;
+  return target ? SpxDest{nullptr, target, 1} : SpxDest{value, nullptr, 1};
+}
+// ... whose host double is NaN when the value stays on the device.  (An empty or a failed call keeps the zero the entry point wrote.)
+static inline void spx_value_nan_on_device(int rc, const SpxDest& d, bool empty, double* value) {
+  if (rc == SPX_OK && d.dev != nullptr && !empty) *value = __builtin_nan("");
+}
+// A host destination synchronises: not under a capture.  what: the entry point's own words.
+static inline int spx_dest_check_capture(spx_ctx* ctx, const SpxDest& d, const char* what) {
+  return d.host ? spx_require_not_capturing(ctx, what) : SPX_OK;
+}
+static inline void spx_dest_zero_host(const SpxDest& d) {
+  if (d.host) for (int i = 0; i < d.count; ++i) d.host[i] = 0.0;
+}
+// The empty call (n == 0, no group at all): zeros, on the device by a kernel rather than a memset node (spx_zero_async).
+static inline int spx_dest_empty(spx_ctx* ctx, const SpxDest& d) {
+  spx_dest_zero_host(d);
+  if (!d.dev) return SPX_OK;
+  SPX_ON_DEVICE(ctx);
+  return spx_zero_async(ctx, d.dev, (size_t)d.count * sizeof(double));
+}
+// The return: with a host destination, `bytes` of the library's result words `words` (device memory) are copied to `into`
+// (d.host unless given) and the stream is synchronised; without one nothing is read back and the call returns after enqueueing.
+static inline int spx_dest_return(spx_ctx* ctx, const SpxDest& d, const void* words, size_t bytes, void* into = nullptr) {
+  if (!d.host) return SPX_OK;
+  SPX_HIP(hipMemcpyAsync(into ? into : d.host, words, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  SPX_HIP(hipStreamSynchronize(ctx->stream));
+  return SPX_OK;
+}
+// What every spx_proxstep_* / spx_iproxstep_* entry point checks before it enqueues anything, in this order: a destination at
+// all; check_d only with a host destination; y none of `inputs` (the sums read them after y is stored; y_msg names them); xkn
+// none of `others`; no host destination under a capture.  Then the host destination is zeroed.
+static inline int spx_step_begin(spx_ctx* ctx, const SpxDest& d, bool check_d, const void* y,
+                                 std::initializer_list<const void*> inputs, const char* y_msg, const void* xkn,
+                                 std::initializer_list<const void*> others) {
+  SPX_REQUIRE(d.host != nullptr || d.dev != nullptr, "stats and stats_dev are both NULL");
+  SPX_REQUIRE(!check_d || d.host != nullptr, "check_d needs the host form of the statistics (stats != NULL): it synchronises");
+  for (const void* p : inputs) SPX_REQUIRE(y == nullptr || y != p, y_msg);
+  if (xkn != nullptr)
+    for (const void* p : others) SPX_REQUIRE(xkn != p, "xkn is one of the other vectors");
+  const int rc = spx_dest_check_capture(ctx, d, "returning the step statistics to the host (pass stats = NULL)");
+  if (rc) return rc;
+  spx_dest_zero_host(d);
+  return SPX_OK;
+}
+constexpr const char* kSpxYAliasesQ = "y aliases q (<q, y> of an overwritten q)";
+// The contiguous-group objective h(xk + sj + y) with its destination as an argument (spx_objective.hip): what spx_obj_group_l2
+// runs, and what the composed routes of spx_proxval_group_* / spx_proxstep_group_* end in.
+int spx_obj_group_l2_to(spx_ctx* ctx, const double* y, const double* xk, const double* sj, int64_t n, const int64_t* group_offsets,
+                        int64_t group_size, int64_t ngroups, const double* lambda_vec, const SpxDest& dest);
 
 // ---------------------------------------------------------------------------------------------
 // device math with the reference's (Julia Base) semantics
@@ -340,9 +405,9 @@ struct SpxSyncHeader {
   unsigned int fin_top;       // the objective kernels' "last workgroup" tickets (spx_fin_ticket below); zero between launches
   int fin_flag;               // ... and their infeasibility bits; zero between launches
   double b2_value;            // spx_proxval_l1_b2 without a device value target: the launch stores h here, the host reads it back
-  double grp_step_h;          // spx_proxstep_group_*, composed routes: h of the value call, picked up by the tail launch (spx_group.hip)
+  double grp_step_h;          // spx_proxstep_group_*, composed routes: the device destination of the value part, picked up by the tail launch (spx_group.hip)
   double b2_step[3];          // spx_proxstep_l1_b2 with a host result: the launch stores {h, <q, y>, <y, y>} here, the host reads them back
-                              // (composed route: [0] is h of the value call, picked up by the tail launch)
+                              // (composed route: [0] is the device destination of the value part, picked up by the tail launch)
   int pad[12];
   unsigned int fin_class[kSpxBarSplit * 32];  // first-level tickets, one 128-byte line each
 };

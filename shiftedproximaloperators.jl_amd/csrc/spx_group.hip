@@ -66,7 +66,7 @@ struct GroupVal {
   bool behind;         // this launch runs behind the main one: it adds the main launch's partials, has none of its own
   SpxSyncHeader* hdr;  // non-NULL: this is the last launch of the call
   GroupValWs* ws;
-  double* target;      // spx_ctx::value_target (may be NULL)
+  double* target;      // the device destination of the value (SpxDest::dev, may be NULL)
   unsigned long long* dmask;  // [tile] (main launch: written; last launch: read for flagged workgroups)
   double* dterm;              // [group]
   int lpg_main;               // lanes per group of the main launch's tile (bit -> group)
@@ -89,6 +89,7 @@ struct GroupStep : GroupVal {
   int64_t dplane;     // doubles between the planes of `dterm`
 };
 static_assert(sizeof(GroupValWs) == 256 && sizeof(GroupStepWs) == 512, "the partials start on a 256-byte boundary");
+static_assert(offsetof(GroupValWs, result) == 0 && offsetof(GroupStepWs, result) == 0, "the host reads the result words from the start of the block");
 template <class GV>
 constexpr int kGroupSums = std::is_same<GV, GroupStep>::value ? 3 : 1;
 // x[i0], x[i0 + step], ... (cnt of them) added by the workgroup: lane t takes the elements t, t + 256, ..., eight loads in flight
@@ -1004,17 +1005,6 @@ static void group_uncovered(const GroupCall& c) {
     hipLaunchKernelGGL(k_csr_uncovered<double>, dim3(256), dim3(256), 0, c.ctx->stream, c.y, c.xk, c.sj, c.offsets, c.ngroups, c.n);
 }
 
-// The value of a fused call: NaN on the host when it goes to the context's device double (nothing read back), else read back.
-static int group_val_return(spx_ctx* ctx, GroupValWs* vws, double* value) {
-  if (ctx->value_target) {
-    *value = std::numeric_limits<double>::quiet_NaN();
-    return SPX_OK;
-  }
-  SPX_HIP(hipMemcpyAsync(value, &vws->result, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  SPX_HIP(hipStreamSynchronize(ctx->stream));
-  return SPX_OK;
-}
-
 // The routes of a contiguous-group call, by the group size (uniform) or the caller's bound on the sizes (CSR offsets).
 enum class GroupRoute {
   None,     // n == 0 or no group at all
@@ -1046,14 +1036,10 @@ static int group_classify(const GroupCall& c, GroupRoute* route) {
 
 // Register tiles.  Ragged groups (CSR offsets + an upper bound on the sizes in group_size) use the same tiles through the 8-byte
 // loads; a group that exceeds the bound after all is handed to the general kernel.
-// VALUE (run_group_val below): the launches also form h at the result, see GroupVal.
-// STEP (run_group_step below, uniform groups only): ... and xkn and the two other sums, see GroupStep; `value` is then the host
-// double[3] or NULL (nothing read back, the call only enqueues).
-struct GroupStepOut {
-  double *xkn, *stats_dev;
-};
+// VALUE (run_group_val below): the launches also form h at the result, see GroupVal; dest: where it goes.
+// STEP (run_group_step below, uniform groups only): ... and xkn and the two other sums, see GroupStep; dest: the three statistics.
 template <bool BINF, bool VALUE, bool STEP = false>
-static int group_route_reg(const GroupCall& c, double q_scale = 1.0, double* value = nullptr, GroupStepOut so = {nullptr, nullptr}) {
+static int group_route_reg(const GroupCall& c, double q_scale = 1.0, const SpxDest& dest = {nullptr, nullptr, 0}, double* xkn = nullptr) {
   static_assert(VALUE || !STEP, "the step form extends the value form");
   using GV = typename std::conditional<STEP, GroupStep, GroupVal>::type;
   constexpr int NS = STEP ? 3 : 1;  // sums per workgroup / handed-on group
@@ -1090,10 +1076,10 @@ static int group_route_reg(const GroupCall& c, double q_scale = 1.0, double* val
     unsigned long long* dmask = one ? nullptr : reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(part) + part_bytes);
     double* dterm = one ? nullptr : reinterpret_cast<double*>(reinterpret_cast<char*>(part) + part_bytes + mask_bytes);
     static_cast<GroupVal&>(gv_main) = GroupVal{q_scale, part, one ? nullptr : part + NS * blocks, (int)blocks, false, one ? spx_sync_header(ctx) : nullptr, vws,
-                                               STEP ? nullptr : ctx->value_target, dmask, dterm, lpg};
-    if constexpr (STEP) {  // (the context's value target does not apply)
-      gv_main.xkn = so.xkn;
-      gv_main.stats_dev = so.stats_dev;
+                                               STEP ? nullptr : dest.dev, dmask, dterm, lpg};
+    if constexpr (STEP) {
+      gv_main.xkn = xkn;
+      gv_main.stats_dev = dest.dev;
       gv_main.sws = reinterpret_cast<GroupStepWs*>(vws);
       gv_main.dplane = ngroups;
     }
@@ -1125,7 +1111,7 @@ static int group_route_reg(const GroupCall& c, double q_scale = 1.0, double* val
       rc = spx_zero_async(ctx, deferred, sizeof(long long)); if (rc) return rc;
     }
   }
-  const bool aligned = spx_aligned16(c.y) && spx_aligned16(c.q) && spx_aligned16(c.xk) && spx_aligned16(c.sj) && spx_aligned16(so.xkn);
+  const bool aligned = spx_aligned16(c.y) && spx_aligned16(c.q) && spx_aligned16(c.xk) && spx_aligned16(c.sj) && spx_aligned16(xkn);
   const GroupRegArgs args{c, deferred, dcount, !ragged && (c.gsize & 1) == 0 && aligned};
   group_uncovered<BINF>(c);
   Tiles::select(c.gsize, [&](auto row) {
@@ -1151,14 +1137,8 @@ static int group_route_reg(const GroupCall& c, double q_scale = 1.0, double* val
                          ctx->status_dev, ctx->tune_binf_literal, (const int*)nullptr, (int64_t)0);
   }
   SPX_LAUNCH_CHECK();
-  if constexpr (STEP) {
-    if (value == nullptr) return SPX_OK;  // device results only: the call returns after enqueueing
-    SPX_HIP(hipMemcpyAsync(value, reinterpret_cast<GroupStepWs*>(vws)->result, 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    SPX_HIP(hipStreamSynchronize(ctx->stream));
-    return SPX_OK;
-  } else if constexpr (VALUE) {
-    return group_val_return(ctx, vws, value);
-  }
+  // (STEP: GroupStepWs::result takes the place of GroupValWs::result, both at offset 0 -- static_assert at the structs)
+  if constexpr (VALUE) return spx_dest_return(ctx, dest, &vws->result, (size_t)dest.count * sizeof(double));
   return SPX_OK;
 }
 
@@ -1266,26 +1246,22 @@ SPX_EXPORT int spx_prox_group_l2_binf(spx_ctx* ctx, double* y, const double* q, 
 // prox! fused with h at the result (include/spx.h, "group forms").  The register-tile route: the value comes out of the
 // launches that store y.  Every other route (LDS-resident groups, the general kernels, teams of workgroups): composed in
 // this call -- y = q_scale * q where the scale is not 1, the unchanged prox at q := y, then the one-launch psi(y)
-// (spx_obj_group_l2) on the same stream.
+// (spx_obj_group_l2_to) on the same stream.
 // ---------------------------------------------------------------------------------------------
 template <bool BINF>
-static int run_group_val(const GroupCall& c, double q_scale, double* value) {
-  SPX_REQUIRE(value != nullptr, "value is NULL");
+static int run_group_val_to(const GroupCall& c, double q_scale, const SpxDest& dest) {
   GroupRoute route;
   int rc = group_classify<BINF>(c, &route);
   if (rc) return rc;
   spx_ctx* ctx = c.ctx;
-  if (!ctx->value_target) {  // (refused before anything is enqueued)
-    const int rcc = spx_require_not_capturing(ctx, "returning the value to the host");
-    if (rcc) return rcc;
-  }
-  *value = 0.0;
-  if (route == GroupRoute::Reg) return group_route_reg<BINF, true>(c, q_scale, value);
+  rc = spx_dest_check_capture(ctx, dest, "returning the value to the host");  // (refused before anything is enqueued)
+  if (rc) return rc;
+  spx_dest_zero_host(dest);
+  if (route == GroupRoute::Reg) return group_route_reg<BINF, true>(c, q_scale, dest);
   if (route == GroupRoute::None) {  // h of no group at all; y as the plain operator leaves it (it does not read q)
     rc = group_run<BINF>(c, route);
     if (rc) return rc;
-    if (ctx->value_target) return spx_zero_async(ctx, ctx->value_target, sizeof(double));
-    return SPX_OK;
+    return spx_dest_empty(ctx, dest);
   }
   GroupCall scaled = c;
   if (q_scale != 1.0) {
@@ -1298,7 +1274,18 @@ static int run_group_val(const GroupCall& c, double q_scale, double* value) {
   }
   rc = group_run<BINF>(scaled, route);
   if (rc) return rc;
-  return spx_obj_group_l2(ctx, c.y, c.xk, c.sj, c.n, c.offsets, c.gsize, c.ngroups, c.lambda, value);
+  // (the h part for the Binf operator too: not spx_obj_group_l2_binf)
+  return spx_obj_group_l2_to(ctx, c.y, c.xk, c.sj, c.n, c.offsets, c.gsize, c.ngroups, c.lambda, dest);
+}
+// the entry points' form: the destination from (ctx, value)
+template <bool BINF>
+static int run_group_val(const GroupCall& c, double q_scale, double* value) {
+  SPX_REQUIRE(value != nullptr, "value is NULL");
+  const SpxDest dest = spx_value_dest(c.ctx, value);
+  *value = 0.0;
+  const int rc = run_group_val_to<BINF>(c, q_scale, dest);
+  spx_value_nan_on_device(rc, dest, c.n == 0 || c.ngroups == 0, value);  // (no group at all: the empty call)
+  return rc;
 }
 
 SPX_EXPORT int spx_proxval_group_l2(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
@@ -1317,7 +1304,7 @@ SPX_EXPORT int spx_proxval_group_l2_binf(spx_ctx* ctx, double* y, const double* 
 // ---------------------------------------------------------------------------------------------
 // prox! fused with the step statistics (include/spx.h, "group forms" of spx_proxstep_*).  Uniform groups on the register tiles:
 // everything comes out of the launches that store y (k_group_reg, STEP).  Every other layout is composed in this call: the
-// unchanged run_group_val -- y and h, h kept on the device in SpxSyncHeader::grp_step_h -- then ONE streaming launch for xkn and
+// unchanged run_group_val with SpxSyncHeader::grp_step_h as its device destination -- y and h -- then ONE streaming launch for xkn and
 // the two sums, which also hands h on to the result slots.
 // ---------------------------------------------------------------------------------------------
 // xkn = (xk + sj) + y, <q, y>, <y, y> over [0, n): a grid-stride loop, VEC: 16-byte accesses (every vector 16-byte aligned; the
@@ -1374,21 +1361,18 @@ SpxStepTail spx_step_tail_plan(spx_ctx* ctx, const double* y, const double* q, c
 }
 
 int spx_step_tail_run(spx_ctx* ctx, const SpxStepTail& tail, const double* q, const double* y, const double* xk, const double* sj,
-                      double* xkn, int64_t n, const double* h, double* stats, double* stats_dev) {
+                      double* xkn, int64_t n, const double* h, const SpxDest& dest) {
   SPX_ON_DEVICE(ctx);
   GroupStep gv{};
   GroupStepWs* sws = reinterpret_cast<GroupStepWs*>(ctx->ws);
   static_cast<GroupVal&>(gv) = GroupVal{1.0, reinterpret_cast<double*>(sws + 1), nullptr, (int)tail.blocks, false, spx_sync_header(ctx), nullptr, nullptr, nullptr, nullptr, 64};
   gv.xkn = xkn;
-  gv.stats_dev = stats_dev;
+  gv.stats_dev = dest.dev;
   gv.sws = sws;
   if (tail.vec) hipLaunchKernelGGL(k_group_step_tail<true>, dim3((unsigned)tail.blocks), dim3(256), 0, ctx->stream, q, y, xk, sj, xkn, n, h, gv);
   else hipLaunchKernelGGL(k_group_step_tail<false>, dim3((unsigned)tail.blocks), dim3(256), 0, ctx->stream, q, y, xk, sj, xkn, n, h, gv);
   SPX_LAUNCH_CHECK();
-  if (stats == nullptr) return SPX_OK;  // device results only: the call returns after enqueueing
-  SPX_HIP(hipMemcpyAsync(stats, sws->result, 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  SPX_HIP(hipStreamSynchronize(ctx->stream));
-  return SPX_OK;
+  return spx_dest_return(ctx, dest, sws->result, 3 * sizeof(double));
 }
 
 template <bool BINF>
@@ -1397,19 +1381,15 @@ static int run_group_step(const GroupCall& c, double q_scale, double* xkn, doubl
   int rc = group_classify<BINF>(c, &route);
   if (rc) return rc;
   spx_ctx* ctx = c.ctx;
-  SPX_REQUIRE(stats != nullptr || stats_dev != nullptr, "stats and stats_dev are both NULL");
-  SPX_REQUIRE(c.y == nullptr || c.y != c.q, "y aliases q (<q, y> of an overwritten q)");
-  if (xkn != nullptr) SPX_REQUIRE(xkn != c.y && xkn != c.q && xkn != c.xk && xkn != c.sj, "xkn is one of the other vectors");
-  // the host copy synchronises: refused under a capture before anything is enqueued
-  if (stats != nullptr) { rc = spx_require_not_capturing(ctx, "returning the step statistics to the host (pass stats = NULL)"); if (rc) return rc; }
-  if (stats) stats[0] = stats[1] = stats[2] = 0.0;
+  const SpxDest dest{stats, stats_dev, 3};
+  rc = spx_step_begin(ctx, dest, false, c.y, {c.q}, kSpxYAliasesQ, xkn, {c.y, c.q, c.xk, c.sj});
+  if (rc) return rc;
   if (route == GroupRoute::None) {  // no group at all: three zeros; y as the plain operator leaves it (it does not read q)
     rc = group_run<BINF>(c, route);
-    if (rc || stats_dev == nullptr) return rc;
-    SPX_ON_DEVICE(ctx);
-    return spx_zero_async(ctx, stats_dev, 3 * sizeof(double));  // (a kernel, not a memset node)
+    if (rc) return rc;
+    return spx_dest_empty(ctx, dest);
   }
-  if (route == GroupRoute::Reg && c.offsets == nullptr) return group_route_reg<BINF, true, true>(c, q_scale, stats, {xkn, stats_dev});
+  if (route == GroupRoute::Reg && c.offsets == nullptr) return group_route_reg<BINF, true, true>(c, q_scale, dest, xkn);
   // composed: the workspace of the tail launch is reserved before anything is enqueued
   const SpxStepTail tail = spx_step_tail_plan(ctx, c.y, c.q, c.xk, c.sj, xkn, c.n);
   rc = spx_ws_reserve(ctx, tail.bytes);
@@ -1417,13 +1397,9 @@ static int run_group_step(const GroupCall& c, double q_scale, double* xkn, doubl
   rc = spx_sync_ready(ctx);
   if (rc) return rc;
   SpxSyncHeader* hdr = spx_sync_header(ctx);
-  double* const caller_target = ctx->value_target;  // (does not apply to this call: h goes to the library's own word)
-  ctx->value_target = &hdr->grp_step_h;
-  double unused;
-  rc = run_group_val<BINF>(c, q_scale, &unused);
-  ctx->value_target = caller_target;
+  rc = run_group_val_to<BINF>(c, q_scale, SpxDest{nullptr, &hdr->grp_step_h, 1});
   if (rc) return rc;
-  return spx_step_tail_run(ctx, tail, c.q, c.y, c.xk, c.sj, xkn, c.n, &hdr->grp_step_h, stats, stats_dev);
+  return spx_step_tail_run(ctx, tail, c.q, c.y, c.xk, c.sj, xkn, c.n, &hdr->grp_step_h, dest);
 }
 
 SPX_EXPORT int spx_proxstep_group_l2(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,

@@ -61,7 +61,7 @@ __device__ __forceinline__ double obj_value(int rule, int flag, double acc, doub
 // forms whose flags have a second source: ragged Binf layouts, the chunked sums of large groups).
 struct ObjFin {
   SpxSyncHeader* hdr;
-  double* target;  // spx_ctx::value_target (may be NULL)
+  double* target;  // the device destination of the value (SpxDest::dev, may be NULL)
   double scale, limit;
   int rule;
 };
@@ -494,31 +494,29 @@ __global__ __launch_bounds__(256) void k_obj_final(ObjWs* ws, int nblocks, int r
   }
 }
 
-// *value = psi(y) (read back, stream synchronised) -- or, with a device value target on the context, NaN on the host and
-// the value in the target, nothing read back.  *flags = the infeasibility bits (0 in the device-target case).
-int obj_finish(spx_ctx* ctx, ObjWs* ws, int blocks, int rule, double scale, double limit, double* value, int* flags,
+// psi(y) to its destination: read back (stream synchronised) together with the infeasibility bits, *flags -- or left in the
+// device destination, nothing read back and *flags = 0.
+int obj_finish(spx_ctx* ctx, ObjWs* ws, int blocks, int rule, double scale, double limit, const SpxDest& dest, int* flags,
                bool fused = false /* the reducing kernel's last workgroup has done k_obj_final's work (ObjFin) */) {
   if (!fused) {
-    hipLaunchKernelGGL(k_obj_final, dim3(1), dim3(256), 0, ctx->stream, ws, blocks, rule, scale, limit, ctx->value_target);
+    hipLaunchKernelGGL(k_obj_final, dim3(1), dim3(256), 0, ctx->stream, ws, blocks, rule, scale, limit, dest.dev);
     SPX_LAUNCH_CHECK();
   }
   *flags = 0;
-  if (ctx->value_target) {
-    *value = std::numeric_limits<double>::quiet_NaN();
-    return SPX_OK;
-  }
+  if (!dest.host) return SPX_OK;
   struct { double r; int f; int p; } host;
-  { const int rcc = spx_require_not_capturing(ctx, "returning psi(y) to the host"); if (rcc) return rcc; }
-  SPX_HIP(hipMemcpyAsync(&host, &ws->result, sizeof(host), hipMemcpyDeviceToHost, ctx->stream));
-  SPX_HIP(hipStreamSynchronize(ctx->stream));
-  *value = host.r;
+  int rc = spx_dest_check_capture(ctx, dest, "returning psi(y) to the host");
+  if (rc) return rc;
+  rc = spx_dest_return(ctx, dest, &ws->result, sizeof(host), &host);
+  if (rc) return rc;
+  *dest.host = host.r;
   *flags = host.f;
   return SPX_OK;
 }
 
 // The one-launch form (ObjFin) keeps its tickets in the synchronisation state's header.
-int obj_fin_prepare(spx_ctx* ctx, int rule, double scale, double limit, ObjFin* fin) {
-  *fin = ObjFin{nullptr, ctx->value_target, scale, limit, rule};
+int obj_fin_prepare(spx_ctx* ctx, int rule, double scale, double limit, const SpxDest& dest, ObjFin* fin) {
+  *fin = ObjFin{nullptr, dest.dev, scale, limit, rule};
   if (!ctx->tune_fewer_launches) return SPX_OK;
   const int rc = spx_sync_ready(ctx);
   if (rc) return rc;
@@ -527,22 +525,19 @@ int obj_fin_prepare(spx_ctx* ctx, int rule, double scale, double limit, ObjFin* 
 }
 
 template <class T, class Term, int MODE>
-int run_obj(spx_ctx* ctx, const T* y, const T* xk, const T* sj, int64_t n, const T* lv,
-            const T* uv, T ls, T us, const uint8_t* mask, double rad, int rule, double scale, double limit,
-            double* value) {
+int run_obj_to(spx_ctx* ctx, const T* y, const T* xk, const T* sj, int64_t n, const T* lv,
+               const T* uv, T ls, T us, const uint8_t* mask, double rad, int rule, double scale, double limit,
+               const SpxDest& dest) {
   SPX_REQUIRE(ctx != nullptr, "ctx is NULL");
   SPX_REQUIRE(n >= 0, "n < 0");
   SPX_REQUIRE(n == 0 || (y && xk && sj), "NULL vector with n > 0");
-  *value = 0.0;  // h of the empty vector (count rule: 0 <= limit)
-  if (n == 0) {
-    if (ctx->value_target) { const int rz = spx_zero_async(ctx, ctx->value_target, sizeof(double)); if (rz) return rz; }
-    return SPX_OK;
-  }
+  spx_dest_zero_host(dest);
+  if (n == 0) return spx_dest_empty(ctx, dest);  // h of the empty vector (count rule: 0 <= limit)
   int rc = spx_ws_reserve(ctx, sizeof(ObjWs) + 256);
   if (rc) return rc;
   SPX_ON_DEVICE(ctx);
   ObjFin fin;
-  rc = obj_fin_prepare(ctx, rule, scale, limit, &fin);
+  rc = obj_fin_prepare(ctx, rule, scale, limit, dest, &fin);
   if (rc) return rc;
   ObjWs* ws = reinterpret_cast<ObjWs*>(ctx->ws);
   if (!fin.hdr) { const int rz = spx_zero_async(ctx, &ws->infeasible, sizeof(int)); if (rz) return rz; }
@@ -552,17 +547,26 @@ int run_obj(spx_ctx* ctx, const T* y, const T* xk, const T* sj, int64_t n, const
                      us, rad, n, Term{}, ws, fin);
   SPX_LAUNCH_CHECK();
   int flags;
-  return obj_finish(ctx, ws, (int)blocks, rule, scale, limit, value, &flags, fin.hdr != nullptr);
+  return obj_finish(ctx, ws, (int)blocks, rule, scale, limit, dest, &flags, fin.hdr != nullptr);
+}
+// the entry points' form: the destination from (ctx, value)
+template <class T, class Term, int MODE>
+int run_obj(spx_ctx* ctx, const T* y, const T* xk, const T* sj, int64_t n, const T* lv, const T* uv, T ls, T us,
+            const uint8_t* mask, double rad, int rule, double scale, double limit, double* value) {
+  const SpxDest dest = spx_value_dest(ctx, value);
+  *value = 0.0;
+  const int rc = run_obj_to<T, Term, MODE>(ctx, y, xk, sj, n, lv, uv, ls, us, mask, rad, rule, scale, limit, dest);
+  spx_value_nan_on_device(rc, dest, n == 0, value);
+  return rc;
 }
 
 template <class T, int MODE>
-int run_obj_group(spx_ctx* ctx, const T* y, const T* xk, const T* sj, int64_t n,
-                  const int64_t* offsets, int64_t gsize, int64_t ngroups, const int64_t* index, int64_t nnz,
-                  const T* lambda, double rad, double* value) {
-  SPX_REQUIRE(ctx != nullptr && value != nullptr, "ctx or value is NULL");
+int run_obj_group_to(spx_ctx* ctx, const T* y, const T* xk, const T* sj, int64_t n,
+                     const int64_t* offsets, int64_t gsize, int64_t ngroups, const int64_t* index, int64_t nnz,
+                     const T* lambda, double rad, const SpxDest& dest) {
   SPX_REQUIRE(n >= 0 && ngroups >= 0 && nnz >= 0, "negative size");
-  *value = 0.0;
-  if (n == 0) return SPX_OK;
+  if (n == 0) return spx_dest_empty(ctx, dest);
+  spx_dest_zero_host(dest);
   SPX_REQUIRE(y && xk && sj, "NULL vector");
   if (ngroups > 0) SPX_REQUIRE(lambda != nullptr, "lambda_vec is NULL");
   if (index || nnz > 0) SPX_REQUIRE(offsets != nullptr && index != nullptr, "group_ptr or group_index is NULL");
@@ -583,9 +587,9 @@ int run_obj_group(spx_ctx* ctx, const T* y, const T* xk, const T* sj, int64_t n,
       rc = spx_ws_reserve(ctx, pre_off + (offsets ? (size_t)(ngroups + 1) * sizeof(int64_t) : 0) + 256);
       if (rc) return rc;
       ws = reinterpret_cast<ObjWs*>(ctx->ws);
-      ObjFin cfin{nullptr, ctx->value_target, 1.0, 0.0, kRuleGroup};
+      ObjFin cfin{nullptr, dest.dev, 1.0, 0.0, kRuleGroup};
       if (!offsets && ngroups <= kObjFuseGroups && kmax <= kObjFuseChunks) {  // few uniform groups: one launch (k_obj_chunks)
-        rc = obj_fin_prepare(ctx, kRuleGroup, 1.0, 0.0, &cfin);
+        rc = obj_fin_prepare(ctx, kRuleGroup, 1.0, 0.0, dest, &cfin);
         if (rc) return rc;
         ws = reinterpret_cast<ObjWs*>(ctx->ws);
       }
@@ -603,7 +607,7 @@ int run_obj_group(spx_ctx* ctx, const T* y, const T* xk, const T* sj, int64_t n,
       if (cfin.hdr) {
         SPX_LAUNCH_CHECK();
         int bad_;
-        return obj_finish(ctx, ws, 0, kRuleGroup, 1.0, 0.0, value, &bad_, true);
+        return obj_finish(ctx, ws, 0, kRuleGroup, 1.0, 0.0, dest, &bad_, true);
       }
       int64_t gb = ngroups < kObjBlocks ? ngroups : kObjBlocks;
       hipLaunchKernelGGL(k_obj_chunk_groups, dim3((unsigned)gb), dim3(256), 0, ctx->stream, (const double*)chunk_ss,
@@ -613,7 +617,7 @@ int run_obj_group(spx_ctx* ctx, const T* y, const T* xk, const T* sj, int64_t n,
                            ngroups, rad, ws);
       SPX_LAUNCH_CHECK();
       int bad_;
-      rc = obj_finish(ctx, ws, (int)gb, kRuleGroup, 1.0, 0.0, value, &bad_);
+      rc = obj_finish(ctx, ws, (int)gb, kRuleGroup, 1.0, 0.0, dest, &bad_);
       if (rc) return rc;
       if (bad_ & 2) {  // (with a device value target the value is NaN instead: nothing is read back)
         spx_set_error("invalid argument: group offsets decreasing or outside [0, n]");
@@ -630,9 +634,9 @@ int run_obj_group(spx_ctx* ctx, const T* y, const T* xk, const T* sj, int64_t n,
   if (blocks > kObjBlocks) blocks = kObjBlocks;
   if (blocks < 1) blocks = 1;
   // one launch unless the trust-region scan of a ragged layout (below) raises bits after this kernel
-  ObjFin fin{nullptr, ctx->value_target, 1.0, 0.0, kRuleGroup};
+  ObjFin fin{nullptr, dest.dev, 1.0, 0.0, kRuleGroup};
   if (!(MODE == 2 && offsets)) {
-    rc = obj_fin_prepare(ctx, kRuleGroup, 1.0, 0.0, &fin);
+    rc = obj_fin_prepare(ctx, kRuleGroup, 1.0, 0.0, dest, &fin);
     if (rc) return rc;
     ws = reinterpret_cast<ObjWs*>(ctx->ws);
   }
@@ -658,7 +662,7 @@ int run_obj_group(spx_ctx* ctx, const T* y, const T* xk, const T* sj, int64_t n,
   }
   SPX_LAUNCH_CHECK();
   int bad;
-  rc = obj_finish(ctx, ws, (int)blocks, kRuleGroup, 1.0, 0.0, value, &bad, fin.hdr != nullptr);
+  rc = obj_finish(ctx, ws, (int)blocks, kRuleGroup, 1.0, 0.0, dest, &bad, fin.hdr != nullptr);
   if (rc) return rc;
   if (bad & 2) {  // (with a device value target the value is NaN instead: nothing is read back)
     spx_set_error(index ? "invalid argument: group index outside [0, n) (BoundsError)"
@@ -667,10 +671,26 @@ int run_obj_group(spx_ctx* ctx, const T* y, const T* xk, const T* sj, int64_t n,
   }
   return SPX_OK;
 }
+// the entry points' form: the destination from (ctx, value)
+template <class T, int MODE>
+int run_obj_group(spx_ctx* ctx, const T* y, const T* xk, const T* sj, int64_t n, const int64_t* offsets, int64_t gsize,
+                  int64_t ngroups, const int64_t* index, int64_t nnz, const T* lambda, double rad, double* value) {
+  SPX_REQUIRE(ctx != nullptr && value != nullptr, "ctx or value is NULL");
+  const SpxDest dest = spx_value_dest(ctx, value);
+  *value = 0.0;
+  const int rc = run_obj_group_to<T, MODE>(ctx, y, xk, sj, n, offsets, gsize, ngroups, index, nnz, lambda, rad, dest);
+  spx_value_nan_on_device(rc, dest, n == 0, value);
+  return rc;
+}
 
 const double kInf = std::numeric_limits<double>::infinity();
 
 }  // namespace
+
+int spx_obj_group_l2_to(spx_ctx* ctx, const double* y, const double* xk, const double* sj, int64_t n, const int64_t* group_offsets,
+                        int64_t group_size, int64_t ngroups, const double* lambda_vec, const SpxDest& dest) {
+  return run_obj_group_to<double, 0>(ctx, y, xk, sj, n, group_offsets, group_size, ngroups, nullptr, 0, lambda_vec, 0.0, dest);
+}
 
 // ---- generic forms: h(xk + sj + y) ---------------------------------------------------------------
 #define SPX_OBJ_PLAIN(NAME, T, TERM)                                                                               \

@@ -414,7 +414,7 @@ struct WithValue : Base {
   // adds the partials itself and the k_value_reduce launch is not queued (fin_hdr != NULL)
   SpxSyncHeader* fin_hdr = nullptr;
   double* fin_result = nullptr;  // the library's result slots (read back by the host forms)
-  double* fin_target = nullptr;  // the caller's device slots: spx_ctx::value_target / stats_dev (may be NULL)
+  double* fin_target = nullptr;  // the caller's device slots (SpxDest::dev, may be NULL)
   double fin_scale = 1.0;        // both receive fin_scale * (sum of the h terms)
   __device__ __forceinline__ double operator()(double q, double x, double s, double l, double u, bool sel) const {
     return Base::operator()(qscale * q, x, s, l, u, sel);
@@ -916,13 +916,13 @@ constexpr size_t kSepFlagOffset = 128;
 static int64_t sep_plane(const spx_ctx* ctx, int64_t n) { return ((n / 2) / (256 * 3) + 2) * 4 + 2 * (int64_t)ctx->num_cu * 8 + 16; }
 static size_t sep_ws_bytes(const spx_ctx* ctx, int64_t n, int ns) { return 256 + (size_t)ns * (size_t)sep_plane(ctx, n) * sizeof(double); }
 // kSumsOf<Op> > 0: the sums {value_scale * h, <q, y>, <y, y>} (WithValue: the first of them; WithIstep: the four) go to the library's result slots,
-// to result_dev (device doubles, or NULL) and, when result_host != NULL, back to the host -- that form synchronises and is
+// to dest.dev (device doubles, or NULL) and, when dest.host != NULL, back to the host -- that form synchronises and is
 // refused under a capture; those callers answer n == 0 themselves.
 template <class Op>
 static int run_separable(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
                          const double* l, const double* u, double ls, double us, const uint8_t* mask, Op op,
-                         const double* d = nullptr, double* result_host = nullptr, double* result_dev = nullptr,
-                         double value_scale = 1.0, double* xkn = nullptr /* WithStep: (xk + sj) + y, or NULL */) {
+                         const double* d = nullptr, const SpxDest& dest = {nullptr, nullptr, 0}, double value_scale = 1.0,
+                         double* xkn = nullptr /* WithStep: (xk + sj) + y, or NULL */) {
   constexpr int NS = kSumsOf<Op>;
   if (n == 0) return SPX_OK;
   SPX_ON_DEVICE(ctx);
@@ -982,7 +982,7 @@ static int run_separable(spx_ctx* ctx, double* y, const double* q, const double*
       if (ctx->tune_fewer_launches && head == 0 && 2 * n2 == n) {
         fh = spx_sync_header(ctx);
         op.fin_result = reinterpret_cast<double*>(ctx->ws);
-        op.fin_target = result_dev;
+        op.fin_target = dest.dev;
         op.fin_scale = value_scale;
       }
     }
@@ -1009,17 +1009,13 @@ static int run_separable(spx_ctx* ctx, double* y, const double* q, const double*
     double* result = reinterpret_cast<double*>(ctx->ws);
     if (!fused) {
       hipLaunchKernelGGL(k_value_reduce<NS>, dim3(NS), dim3(1024), 0, ctx->stream, (const double*)partials, plane, used, result,
-                         value_scale, result_dev);
+                         value_scale, dest.dev);
       SPX_LAUNCH_CHECK();
     }
-    if (result_host == nullptr) return SPX_OK;  // device results only: nothing is read back, the call returns after enqueueing
-    {
-      const int rcc = spx_require_not_capturing(ctx, NS == 1 ? "returning the value of prox_value to the host"
-                                                             : "returning the step statistics to the host (pass stats = NULL)");
-      if (rcc) return rcc;
-    }
-    SPX_HIP(hipMemcpyAsync(result_host, result, NS * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    SPX_HIP(hipStreamSynchronize(ctx->stream));
+    const int rcc = spx_dest_check_capture(ctx, dest, NS == 1 ? "returning the value of prox_value to the host"
+                                                              : "returning the step statistics to the host (pass stats = NULL)");
+    if (rcc) return rcc;
+    return spx_dest_return(ctx, dest, result, NS * sizeof(double));
   }
   return SPX_OK;
 }
@@ -1103,11 +1099,11 @@ static int run_proxval(spx_ctx* ctx, double* y, const double* q, const double* x
   if (rc) return rc;
   SPX_REQUIRE(value != nullptr, "value is NULL");
   WithValue<Base, Term> op{base, nullptr, q_scale};
-  double h = lambda * 0.0;  // (n == 0, or an error)
-  double* const target = ctx->value_target;  // device-resident value: nothing is read back, the call returns after enqueueing
-  rc = run_separable(ctx, y, q, xk, sj, n, l, u, ls, us, mask, op, nullptr, target ? nullptr : &h, target, lambda);
-  if (rc == SPX_OK && n > 0 && target) h = std::numeric_limits<double>::quiet_NaN();
-  *value = h;
+  *value = lambda * 0.0;  // (n == 0, or an error: -0.0 for a negative lambda, NaN for a non-finite one)
+  const SpxDest dest = spx_value_dest(ctx, value);
+  if (n == 0) return spx_dest_empty(ctx, {nullptr, dest.dev, 1});  // (the device side only: the host keeps lambda * 0)
+  rc = run_separable(ctx, y, q, xk, sj, n, l, u, ls, us, mask, op, nullptr, dest, lambda);
+  spx_value_nan_on_device(rc, dest, false, value);
   return rc;
 }
 
@@ -1160,25 +1156,14 @@ static int run_proxstep(spx_ctx* ctx, double* y, const double* q, const double* 
                         double lambda, double q_scale, double* xkn, double* stats, double* stats_dev) {
   int rc = spx_check_common(ctx, y, q, xk, sj, n);
   if (rc) return rc;
-  SPX_REQUIRE(stats != nullptr || stats_dev != nullptr, "stats and stats_dev are both NULL");
-  SPX_REQUIRE(y == nullptr || y != q, "y aliases q (<q, y> of an overwritten q)");
-  if (xkn != nullptr) {
-    const void* x = xkn;
-    SPX_REQUIRE(x != y && x != q && x != xk && x != sj && x != l && x != u && x != mask, "xkn is one of the other vectors");
-  }
-  // the host copy synchronises: refused under a capture before anything is enqueued
-  if (stats != nullptr) { rc = spx_require_not_capturing(ctx, "returning the step statistics to the host (pass stats = NULL)"); if (rc) return rc; }
-  if (stats) stats[0] = stats[1] = stats[2] = 0.0;
-  if (n == 0) {
-    if (stats_dev == nullptr) return SPX_OK;
-    SPX_ON_DEVICE(ctx);
-    return spx_zero_async(ctx, stats_dev, 3 * sizeof(double));  // (a kernel, not a memset node)
-  }
+  const SpxDest dest{stats, stats_dev, 3};
+  rc = spx_step_begin(ctx, dest, false, y, {q}, kSpxYAliasesQ, xkn, {y, q, xk, sj, l, u, mask});
+  if (rc) return rc;
+  if (n == 0) return spx_dest_empty(ctx, dest);
   WithStep<Base, Term> op{};
   static_cast<Base&>(op) = base;
   op.qscale = q_scale;
-  // (the context's value target applies to prox_value only)
-  return run_separable(ctx, y, q, xk, sj, n, l, u, ls, us, mask, op, nullptr, stats, stats_dev, lambda, xkn);
+  return run_separable(ctx, y, q, xk, sj, n, l, u, ls, us, mask, op, nullptr, dest, lambda, xkn);
 }
 
 SPX_EXPORT int spx_proxstep_l1(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
@@ -1416,6 +1401,17 @@ static int run_unboxed(spx_ctx* ctx, float* y, const float* g, const float* d, c
                        Op op) {
   return run_f32(ctx, y, g, xk, sj, n, nullptr, nullptr, 0.0f, 0.0f, nullptr, op, d);
 }
+// The d > 0 flag word of the unboxed forms, read back (the stream is synchronised): the reference's assertion.
+static int iprox_check_flag(spx_ctx* ctx, const int* flag) {
+  int bad = 0;
+  SPX_HIP(hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  SPX_HIP(hipStreamSynchronize(ctx->stream));
+  if (bad) {
+    spx_set_error("AssertionError: d[i] > 0");
+    return SPX_ERR_ASSERT;
+  }
+  return SPX_OK;
+}
 // check_d: the d > 0 flag is read back, which synchronises the stream -- refused under a capture before anything is enqueued
 template <class Op, class T>
 static int run_iprox_unboxed(spx_ctx* ctx, T* y, const T* g, const T* d, const T* xk, const T* sj, int64_t n, T lambda,
@@ -1432,14 +1428,7 @@ static int run_iprox_unboxed(spx_ctx* ctx, T* y, const T* g, const T* d, const T
   { const int rz = spx_zero_async(ctx, flag, sizeof(int)); if (rz) return rz; }
   rc = run_unboxed(ctx, y, g, d, xk, sj, n, Op{lambda, flag});
   if (rc || !check_d) return rc;
-  int bad = 0;
-  SPX_HIP(hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-  SPX_HIP(hipStreamSynchronize(ctx->stream));
-  if (bad) {
-    spx_set_error("AssertionError: d[i] > 0");
-    return SPX_ERR_ASSERT;
-  }
-  return SPX_OK;
+  return iprox_check_flag(ctx, flag);
 }
 
 SPX_EXPORT int spx_iprox_l1(spx_ctx* ctx, double* y, const double* g, const double* d, const double* xk,
@@ -1480,21 +1469,11 @@ static int run_iproxstep(spx_ctx* ctx, double* y, const double* g, const double*
   int rc = spx_check_common(ctx, y, g, xk, sj, n);
   if (rc) return rc;
   SPX_REQUIRE(n == 0 || d != nullptr, "d is NULL");
-  SPX_REQUIRE(stats != nullptr || stats_dev != nullptr, "stats and stats_dev are both NULL");
-  SPX_REQUIRE(!check_d || stats != nullptr, "check_d needs the host form of the statistics (stats != NULL): it synchronises");
-  SPX_REQUIRE(y == nullptr || (y != g && y != d), "y aliases g or d (the sums would read an overwritten input)");
-  if (xkn != nullptr) {
-    const void* x = xkn;
-    SPX_REQUIRE(x != y && x != g && x != d && x != xk && x != sj && x != l && x != u && x != mask, "xkn is one of the other vectors");
-  }
-  // the host copy synchronises: refused under a capture before anything is enqueued
-  if (stats != nullptr) { rc = spx_require_not_capturing(ctx, "returning the step statistics to the host (pass stats = NULL)"); if (rc) return rc; }
-  if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0.0;
-  if (n == 0) {
-    if (stats_dev == nullptr) return SPX_OK;
-    SPX_ON_DEVICE(ctx);
-    return spx_zero_async(ctx, stats_dev, 4 * sizeof(double));  // (a kernel, not a memset node)
-  }
+  const SpxDest dest{stats, stats_dev, 4};
+  rc = spx_step_begin(ctx, dest, check_d != 0, y, {g, d}, "y aliases g or d (the sums would read an overwritten input)", xkn,
+                      {y, g, d, xk, sj, l, u, mask});
+  if (rc) return rc;
+  if (n == 0) return spx_dest_empty(ctx, dest);
   WithIstep<Base, Term> op{};
   op.lambda = lambda;
   int* flag = nullptr;
@@ -1507,18 +1486,9 @@ static int run_iproxstep(spx_ctx* ctx, double* y, const double* g, const double*
     { const int rz = spx_zero_async(ctx, flag, sizeof(int)); if (rz) return rz; }
     op.flag = flag;
   }
-  // (the context's value target applies to prox_value only)
-  rc = run_separable(ctx, y, g, xk, sj, n, l, u, ls, us, mask, op, d, stats, stats_dev, lambda, xkn);
+  rc = run_separable(ctx, y, g, xk, sj, n, l, u, ls, us, mask, op, d, dest, lambda, xkn);
   if (rc || !check_d) return rc;
-  if constexpr (FLAGGED) {
-    int bad = 0;  // (the stream has been synchronised by the copy of the statistics)
-    SPX_HIP(hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    SPX_HIP(hipStreamSynchronize(ctx->stream));
-    if (bad) {
-      spx_set_error("AssertionError: d[i] > 0");
-      return SPX_ERR_ASSERT;
-    }
-  }
+  if constexpr (FLAGGED) return iprox_check_flag(ctx, flag);  // (the stream has been synchronised by the copy of the statistics)
   return SPX_OK;
 }
 
