@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <array>
 #include <cstdarg>
 #include <cstdio>
 #include <initializer_list>
@@ -265,9 +266,11 @@ static inline int spx_dest_return(spx_ctx* ctx, const SpxDest& d, const void* wo
 // What every spx_proxstep_* / spx_iproxstep_* entry point checks before it enqueues anything, in this order: a destination at
 // all; check_d only with a host destination; y none of `inputs` (the sums read them after y is stored; y_msg names them); xkn
 // none of `others`; no host destination under a capture.  Then the host destination is zeroed.
+// (Others: a braced list, or SepCall::others() below)
+template <class Others = std::initializer_list<const void*>>
 static inline int spx_step_begin(spx_ctx* ctx, const SpxDest& d, bool check_d, const void* y,
                                  std::initializer_list<const void*> inputs, const char* y_msg, const void* xkn,
-                                 std::initializer_list<const void*> others) {
+                                 const Others& others) {
   SPX_REQUIRE(d.host != nullptr || d.dev != nullptr, "stats and stats_dev are both NULL");
   SPX_REQUIRE(!check_d || d.host != nullptr, "check_d needs the host form of the statistics (stats != NULL): it synchronises");
   for (const void* p : inputs) SPX_REQUIRE(y == nullptr || y != p, y_msg);
@@ -283,6 +286,52 @@ constexpr const char* kSpxYAliasesQ = "y aliases q (<q, y> of an overwritten q)"
 // runs, and what the composed routes of spx_proxval_group_* / spx_proxstep_group_* end in.
 int spx_obj_group_l2_to(spx_ctx* ctx, const double* y, const double* xk, const double* sj, int64_t n, const int64_t* group_offsets,
                         int64_t group_size, int64_t ngroups, const double* lambda_vec, const SpxDest& dest);
+
+// ---------------------------------------------------------------------------------------------
+// The operands of a separable call (spx_separable.hip; the Box tail also in spx_objective.hip), built once, at the entry point,
+// and passed down by reference: only a kernel launch spells the fields out, in the kernel's parameter order.
+// ---------------------------------------------------------------------------------------------
+// The Box tail: the bounds as vectors (NULL: the scalar) and the selection mask (NULL: every index).  Value-initialised: no box.
+template <class T>
+struct SpxBox {
+  const T *l, *u;
+  T ls, us;
+  const uint8_t* mask;
+};
+// q holds g in the iprox forms; d and xkn are NULL where the call has none.  Each member below states the vectors of a call once.
+template <class T>
+struct SepCall {
+  spx_ctx* ctx;
+  T* y;
+  const T *q, *d, *xk, *sj;
+  int64_t n;
+  SpxBox<T> box;
+  T* xkn;
+
+  // the same call `head` elements further on (the mask: bytes); a NULL stays NULL
+  SepCall shifted(int64_t head) const {
+    auto sh = [head](auto* p) { return p ? p + head : p; };
+    return {ctx, sh(y), sh(q), sh(d), sh(xk), sh(sj), n, {sh(box.l), sh(box.u), box.ls, box.us, sh(box.mask)}, sh(xkn)};
+  }
+  // Float64 vector skeletons: is every vector 16-byte aligned at element h, and the mask 2-byte aligned there?
+  bool aligned16_at(int64_t h) const {
+    auto a16 = [h](const T* p) { return !p || spx_aligned16(p + h); };
+    return a16(y) && a16(q) && a16(d) && a16(xk) && a16(sj) && a16(box.l) && a16(box.u) && a16(xkn) &&
+           (!box.mask || ((reinterpret_cast<uintptr_t>(box.mask) + (uintptr_t)h) & 1u) == 0);
+  }
+  // Float32 vector skeleton: do y, q, xk, sj, d and -- for a Box operator -- l and u start equally far, a whole number of
+  // elements, from a 16-byte boundary?  (The mask is read by bytes; there is no Float32 form with xkn.)
+  bool same_misalignment(bool bounds_count) const {
+    auto mis = [](const void* p) { return (unsigned)(reinterpret_cast<uintptr_t>(p) & 15u); };
+    const unsigned m = mis(y);
+    auto eq = [&](const T* p) { return !p || mis(p) == m; };
+    return m % 4 == 0 && mis(q) == m && mis(xk) == m && mis(sj) == m && eq(d) && (!bounds_count || (eq(box.l) && eq(box.u)));
+  }
+  // what xkn must be none of (spx_step_begin)
+  std::array<const void*, 8> others() const { return {{y, q, d, xk, sj, box.l, box.u, box.mask}}; }
+};
+template <class T>
+static inline int spx_check_common(const SepCall<T>& c) { return spx_check_common(c.ctx, c.y, c.q, c.xk, c.sj, c.n); }
 
 // ---------------------------------------------------------------------------------------------
 // device math with the reference's (Julia Base) semantics

@@ -525,9 +525,8 @@ int obj_fin_prepare(spx_ctx* ctx, int rule, double scale, double limit, const Sp
 }
 
 template <class T, class Term, int MODE>
-int run_obj_to(spx_ctx* ctx, const T* y, const T* xk, const T* sj, int64_t n, const T* lv,
-               const T* uv, T ls, T us, const uint8_t* mask, double rad, int rule, double scale, double limit,
-               const SpxDest& dest) {
+int run_obj_to(spx_ctx* ctx, const T* y, const T* xk, const T* sj, int64_t n, const SpxBox<T>& box, double rad, int rule,
+               double scale, double limit, const SpxDest& dest) {
   SPX_REQUIRE(ctx != nullptr, "ctx is NULL");
   SPX_REQUIRE(n >= 0, "n < 0");
   SPX_REQUIRE(n == 0 || (y && xk && sj), "NULL vector with n > 0");
@@ -543,19 +542,19 @@ int run_obj_to(spx_ctx* ctx, const T* y, const T* xk, const T* sj, int64_t n, co
   if (!fin.hdr) { const int rz = spx_zero_async(ctx, &ws->infeasible, sizeof(int)); if (rz) return rz; }
   int64_t blocks = (n + 256 * 8 - 1) / (256 * 8);
   if (blocks > kObjBlocks) blocks = kObjBlocks;
-  hipLaunchKernelGGL((k_obj<T, Term, MODE>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, y, xk, sj, lv, uv, mask, ls,
-                     us, rad, n, Term{}, ws, fin);
+  hipLaunchKernelGGL((k_obj<T, Term, MODE>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, y, xk, sj, box.l, box.u, box.mask,
+                     box.ls, box.us, rad, n, Term{}, ws, fin);
   SPX_LAUNCH_CHECK();
   int flags;
   return obj_finish(ctx, ws, (int)blocks, rule, scale, limit, dest, &flags, fin.hdr != nullptr);
 }
 // the entry points' form: the destination from (ctx, value)
 template <class T, class Term, int MODE>
-int run_obj(spx_ctx* ctx, const T* y, const T* xk, const T* sj, int64_t n, const T* lv, const T* uv, T ls, T us,
-            const uint8_t* mask, double rad, int rule, double scale, double limit, double* value) {
+int run_obj(spx_ctx* ctx, const T* y, const T* xk, const T* sj, int64_t n, const SpxBox<T>& box, double rad, int rule,
+            double scale, double limit, double* value) {
   const SpxDest dest = spx_value_dest(ctx, value);
   *value = 0.0;
-  const int rc = run_obj_to<T, Term, MODE>(ctx, y, xk, sj, n, lv, uv, ls, us, mask, rad, rule, scale, limit, dest);
+  const int rc = run_obj_to<T, Term, MODE>(ctx, y, xk, sj, n, box, rad, rule, scale, limit, dest);
   spx_value_nan_on_device(rc, dest, n == 0, value);
   return rc;
 }
@@ -696,8 +695,7 @@ int spx_obj_group_l2_to(spx_ctx* ctx, const double* y, const double* xk, const d
 #define SPX_OBJ_PLAIN(NAME, T, TERM)                                                                               \
   SPX_EXPORT int NAME(spx_ctx* ctx, const T* y, const T* xk, const T* sj, int64_t n, T lambda, double* value) {   \
     SPX_REQUIRE(value != nullptr, "value is NULL");                                                                \
-    return run_obj<T, TERM, 0>(ctx, y, xk, sj, n, nullptr, nullptr, (T)0, (T)0, nullptr, 0.0, kRuleScaled,         \
-                               (double)lambda, 0.0, value);                                                        \
+    return run_obj<T, TERM, 0>(ctx, y, xk, sj, n, SpxBox<T>{}, 0.0, kRuleScaled, (double)lambda, 0.0, value);      \
   }
 SPX_OBJ_PLAIN(spx_obj_l1, double, TermL1)
 SPX_OBJ_PLAIN(spx_obj_l0, double, TermL0)
@@ -708,8 +706,8 @@ SPX_OBJ_PLAIN(spx_obj_lhalf, double, TermLhalf)
   SPX_EXPORT int NAME(spx_ctx* ctx, const T* y, const T* xk, const T* sj, int64_t n, T lambda, const T* l_vec,    \
                       const T* u_vec, T l_scalar, T u_scalar, const uint8_t* sel_mask, double* value) {            \
     SPX_REQUIRE(value != nullptr, "value is NULL");                                                                \
-    return run_obj<T, TERM, 1>(ctx, y, xk, sj, n, l_vec, u_vec, l_scalar, u_scalar, sel_mask, 0.0, kRuleBox,       \
-                               (double)lambda, 0.0, value);                                                        \
+    const SpxBox<T> box{l_vec, u_vec, l_scalar, u_scalar, sel_mask};                                               \
+    return run_obj<T, TERM, 1>(ctx, y, xk, sj, n, box, 0.0, kRuleBox, (double)lambda, 0.0, value);                 \
   }
 SPX_OBJ_BOX(spx_obj_l1_box, double, TermL1)
 SPX_OBJ_BOX(spx_obj_l0_box, double, TermL0)
@@ -719,13 +717,12 @@ SPX_OBJ_BOX(spx_obj_lhalf_box, double, TermLhalf)
 SPX_EXPORT int spx_obj_indball_l0(spx_ctx* ctx, const double* y, const double* xk, const double* sj, int64_t n,
                                   int64_t r, double* value) {
   SPX_REQUIRE(value != nullptr, "value is NULL");
-  return run_obj<double, TermL0, 0>(ctx, y, xk, sj, n, nullptr, nullptr, 0.0, 0.0, nullptr, 0.0, kRuleCount, 1.0, (double)r, value);
+  return run_obj<double, TermL0, 0>(ctx, y, xk, sj, n, SpxBox<double>{}, 0.0, kRuleCount, 1.0, (double)r, value);
 }
 SPX_EXPORT int spx_obj_indball_l0_binf(spx_ctx* ctx, const double* y, const double* xk, const double* sj, int64_t n,
                                        int64_t r, double delta, double* value) {
   SPX_REQUIRE(value != nullptr, "value is NULL");
-  return run_obj<double, TermL0, 2>(ctx, y, xk, sj, n, nullptr, nullptr, 0.0, 0.0, nullptr, 1.1 * delta, kRuleCount, 1.0, (double)r,
-                            value);
+  return run_obj<double, TermL0, 2>(ctx, y, xk, sj, n, SpxBox<double>{}, 1.1 * delta, kRuleCount, 1.0, (double)r, value);
 }
 
 // ---- GroupNormL2 ---------------------------------------------------------------------------------------
@@ -768,13 +765,12 @@ SPX_OBJ_BOX(spx_obj_lhalf_box_f32, float, TermLhalf)
 SPX_EXPORT int spx_obj_indball_l0_f32(spx_ctx* ctx, const float* y, const float* xk, const float* sj, int64_t n, int64_t r,
                                       double* value) {
   SPX_REQUIRE(value != nullptr, "value is NULL");
-  return run_obj<float, TermL0, 0>(ctx, y, xk, sj, n, nullptr, nullptr, 0.0f, 0.0f, nullptr, 0.0, kRuleCount, 1.0, (double)r, value);
+  return run_obj<float, TermL0, 0>(ctx, y, xk, sj, n, SpxBox<float>{}, 0.0, kRuleCount, 1.0, (double)r, value);
 }
 SPX_EXPORT int spx_obj_indball_l0_binf_f32(spx_ctx* ctx, const float* y, const float* xk, const float* sj, int64_t n,
                                            int64_t r, float delta, double* value) {
   SPX_REQUIRE(value != nullptr, "value is NULL");
-  return run_obj<float, TermL0, 2>(ctx, y, xk, sj, n, nullptr, nullptr, 0.0f, 0.0f, nullptr, 1.1 * (double)delta, kRuleCount, 1.0,
-                                   (double)r, value);
+  return run_obj<float, TermL0, 2>(ctx, y, xk, sj, n, SpxBox<float>{}, 1.1 * (double)delta, kRuleCount, 1.0, (double)r, value);
 }
 SPX_EXPORT int spx_obj_group_l2_f32(spx_ctx* ctx, const float* y, const float* xk, const float* sj, int64_t n,
                                     const int64_t* group_offsets, int64_t group_size, int64_t ngroups,

@@ -14,6 +14,7 @@
 #include <cmath>
 
 #include <limits>
+#include <type_traits>
 
 #include "spx_common.hpp"
 
@@ -863,11 +864,12 @@ __global__ __launch_bounds__(256) void k_sep_scalar(double* y, const double* q, 
 #define SPX_VECB_KIB 3  // KiB per wave and vector with vector bounds (5 vectors); measured at n = 1e8 (tools/bench_vecb.py): 2 -> 0.81 ms, 3 -> 0.76 ms, 4 -> 0.775 ms
 #endif
 template <class Op, bool VECB, bool MASK>
-static int launch_vec(spx_ctx* ctx, double* y, const double* q, const double* d, const double* xk, const double* sj,
-                      const double* l, const double* u, const uint8_t* mask, double ls, double us, int64_t n2, Op op,
+static int launch_vec(const SepCall<double>& c /* at its 16-byte aligned body */, int64_t n2, Op op,
                       int64_t* value_slots /* out: partial slots written (kSumsOf<Op> > 0) */,
                       const SpxSyncHeader* fuse_hdr = nullptr /* kSumsOf<Op> > 0: this launch is the whole call -- it may finish the sums itself */,
                       bool* fused = nullptr) {
+  spx_ctx* const ctx = c.ctx;
+  const SpxBox<double>& b = c.box;
   // (kSumsOf<Op> > 0) the one-launch form: the grid is the list of slots, short enough for one workgroup to add
   auto try_fuse = [&](int64_t blocks) {
     if constexpr (kSumsOf<Op> > 0) {
@@ -888,8 +890,8 @@ static int launch_vec(spx_ctx* ctx, double* y, const double* q, const double* d,
     }
     *value_slots = blocks;  // one per workgroup (idle workgroups of the XCD-contiguous experiment write a zero)
     try_fuse(blocks);
-    hipLaunchKernelGGL((k_sep_lds<Op, U, VECB, MASK>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, y, q, d, xk,
-                       sj, l, u, mask, ls, us, n2, op, xcd_chunk);
+    hipLaunchKernelGGL((k_sep_lds<Op, U, VECB, MASK>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, c.y, c.q, c.d, c.xk,
+                       c.sj, b.l, b.u, b.mask, b.ls, b.us, n2, op, xcd_chunk);
     SPX_LAUNCH_CHECK();
     return SPX_OK;
   }
@@ -901,11 +903,11 @@ static int launch_vec(spx_ctx* ctx, double* y, const double* q, const double* d,
   *value_slots = blocks;  // one per workgroup
   try_fuse(blocks);
   if (ctx->tune_sep_nt)
-    hipLaunchKernelGGL((k_sep_vec<Op, UNROLL, VECB, MASK, true>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, y,
-                       q, d, xk, sj, l, u, mask, ls, us, n2, op);
+    hipLaunchKernelGGL((k_sep_vec<Op, UNROLL, VECB, MASK, true>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, c.y,
+                       c.q, c.d, c.xk, c.sj, b.l, b.u, b.mask, b.ls, b.us, n2, op);
   else
     hipLaunchKernelGGL((k_sep_vec<Op, UNROLL, VECB, MASK, false>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream,
-                       y, q, d, xk, sj, l, u, mask, ls, us, n2, op);
+                       c.y, c.q, c.d, c.xk, c.sj, b.l, b.u, b.mask, b.ls, b.us, n2, op);
   SPX_LAUNCH_CHECK();
   return SPX_OK;
 }
@@ -919,11 +921,10 @@ static size_t sep_ws_bytes(const spx_ctx* ctx, int64_t n, int ns) { return 256 +
 // to dest.dev (device doubles, or NULL) and, when dest.host != NULL, back to the host -- that form synchronises and is
 // refused under a capture; those callers answer n == 0 themselves.
 template <class Op>
-static int run_separable(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
-                         const double* l, const double* u, double ls, double us, const uint8_t* mask, Op op,
-                         const double* d = nullptr, const SpxDest& dest = {nullptr, nullptr, 0}, double value_scale = 1.0,
-                         double* xkn = nullptr /* WithStep: (xk + sj) + y, or NULL */) {
+static int run_separable(const SepCall<double>& c, Op op, const SpxDest& dest = {nullptr, nullptr, 0}, double value_scale = 1.0) {
   constexpr int NS = kSumsOf<Op>;
+  spx_ctx* const ctx = c.ctx;
+  const int64_t n = c.n;
   if (n == 0) return SPX_OK;
   SPX_ON_DEVICE(ctx);
   double* partials = nullptr;  // ws: [results | pad to 256 B | NS planes of partial slots]
@@ -940,39 +941,31 @@ static int run_separable(spx_ctx* ctx, double* y, const double* q, const double*
     }
   }
   bool fused = false;
-  // The vector skeletons need 16-byte aligned vectors (and a 2-byte aligned mask).  Views that all start 8 bytes off
-  // (e.g. view(x, 2:n) of aligned arrays) are peeled: element 0 through the scalar kernel, the rest aligned again.
-  auto vec_ok_at = [&](int64_t h) {
-    auto a16 = [&](const double* p) { return !p || spx_aligned16(p + h); };
-    return a16(y) && a16(q) && a16(xk) && a16(sj) && a16(d) && a16(l) && a16(u) && a16(xkn) &&
-           (!mask || ((reinterpret_cast<uintptr_t>(mask) + (uintptr_t)h) & 1u) == 0);
-  };
   auto launch_scalar = [&](int64_t begin, int64_t end) -> int {
     int64_t blocks = (end - begin + 255) / 256;
     const int64_t cap = (int64_t)ctx->num_cu * 8;
     if (blocks > cap) blocks = cap;
     if constexpr (NS > 0) op.partials = partials + used;
-    if constexpr (NS >= 3) op.xkn = xkn;  // (indexed from element 0)
-    hipLaunchKernelGGL((k_sep_scalar<Op>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, y, q, d, xk, sj, l, u,
-                       mask, ls, us, begin, end, op);
+    if constexpr (NS >= 3) op.xkn = c.xkn;  // (indexed from element 0)
+    hipLaunchKernelGGL((k_sep_scalar<Op>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, c.y, c.q, c.d, c.xk, c.sj, c.box.l,
+                       c.box.u, c.box.mask, c.box.ls, c.box.us, begin, end, op);
     SPX_LAUNCH_CHECK();
     used += blocks;
     return SPX_OK;
   };
+  // The vector skeletons need 16-byte aligned vectors (and a 2-byte aligned mask).  Views that all start 8 bytes off
+  // (e.g. view(x, 2:n) of aligned arrays) are peeled: element 0 through the scalar kernel, the rest aligned again.
   int64_t head = 0;
-  if (!vec_ok_at(0) && n >= 3 && vec_ok_at(1)) head = 1;
+  if (!c.aligned16_at(0) && n >= 3 && c.aligned16_at(1)) head = 1;
   int64_t done = 0;
   if (head) {
     int rch = launch_scalar(0, head);
     if (rch) return rch;
     done = head;
   }
-  if (vec_ok_at(head) && n - head >= 2) {
+  if (c.aligned16_at(head) && n - head >= 2) {
     const int64_t n2 = (n - head) / 2;
-    auto sh = [&](const double* p) { return p ? p + head : p; };
-    double* yv = y + head;
-    const double *qv = sh(q), *dv = sh(d), *xv = sh(xk), *sv = sh(sj), *lv = sh(l), *uv = sh(u);
-    const uint8_t* mv = mask ? mask + head : mask;
+    const SepCall<double> v = c.shifted(head);
     int rc;
     int64_t slots = 0;
     const SpxSyncHeader* fh = nullptr;
@@ -986,16 +979,16 @@ static int run_separable(spx_ctx* ctx, double* y, const double* q, const double*
         op.fin_scale = value_scale;
       }
     }
-    if constexpr (NS >= 3) op.xkn = xkn ? xkn + head : nullptr;
+    if constexpr (NS >= 3) op.xkn = v.xkn;
     if constexpr (Op::kBox) {
-      const bool vecb = (l || u);
-      const bool msk = (mask != nullptr);
-      if (vecb && msk) rc = launch_vec<Op, true, true>(ctx, yv, qv, dv, xv, sv, lv, uv, mv, ls, us, n2, op, &slots, fh, &fused);
-      else if (vecb) rc = launch_vec<Op, true, false>(ctx, yv, qv, dv, xv, sv, lv, uv, mv, ls, us, n2, op, &slots, fh, &fused);
-      else if (msk) rc = launch_vec<Op, false, true>(ctx, yv, qv, dv, xv, sv, lv, uv, mv, ls, us, n2, op, &slots, fh, &fused);
-      else rc = launch_vec<Op, false, false>(ctx, yv, qv, dv, xv, sv, lv, uv, mv, ls, us, n2, op, &slots, fh, &fused);
+      const bool vecb = (v.box.l || v.box.u);
+      const bool msk = (v.box.mask != nullptr);
+      if (vecb && msk) rc = launch_vec<Op, true, true>(v, n2, op, &slots, fh, &fused);
+      else if (vecb) rc = launch_vec<Op, true, false>(v, n2, op, &slots, fh, &fused);
+      else if (msk) rc = launch_vec<Op, false, true>(v, n2, op, &slots, fh, &fused);
+      else rc = launch_vec<Op, false, false>(v, n2, op, &slots, fh, &fused);
     } else {
-      rc = launch_vec<Op, false, false>(ctx, yv, qv, dv, xv, sv, lv, uv, mv, ls, us, n2, op, &slots, fh, &fused);
+      rc = launch_vec<Op, false, false>(v, n2, op, &slots, fh, &fused);
     }
     if (rc) return rc;
     used += slots;
@@ -1021,188 +1014,163 @@ static int run_separable(spx_ctx* ctx, double* y, const double* q, const double*
 }
 
 // ---------------------------------------------------------------------------------------------
-// C entry points
+// The operator table and the C entry points
 // ---------------------------------------------------------------------------------------------
-// The operators' constants from (lambda, sigma), stated once: y of spx_prox_X, spx_proxval_X and spx_proxstep_X has the
-// same bits because the three build the same functor.  Op: the Float64 or the Float32 struct of the operator.
-template <class Op, class T>
-static Op make_l1(T lambda, T sigma) { return Op{lambda * sigma}; }
-template <class Op, class T>
-static Op make_l0(T lambda, T sigma) { return Op{std::sqrt(2 * lambda * sigma)}; }
-template <class Op, class T>
-static Op make_l1_box(T lambda, T sigma) { return Op{sigma * lambda}; }
-template <class Op, class T>
-static Op make_l0_box(T lambda, T sigma) { return Op{2 * lambda * sigma}; }
-static OpLhalf make_lhalf(double lambda, double sigma) {
-  const double nl = sigma * lambda;
-  const double p = std::pow(54.0, 1.0 / 3.0) * std::pow(2 * nl, 2.0 / 3.0) / 4;  // shiftedRootNormLhalf.jl:49
-  return OpLhalf{nl / 4, p};
-}
-static OpLhalfBox make_lhalf_box(double lambda, double sigma) { return OpLhalfBox{sigma * lambda / 4, lambda, 0.5 / sigma}; }
+// One row per operator names its Float64 functor (Op), its Float32 functor (F32, where there is one), its
+// h term and make<O>: the functor O's constants from (lambda, sigma).  Every entry point of an operator is run_...<Row>, so
+// y of spx_prox_X, spx_proxval_X and spx_proxstep_X has the same bits: the three take the functor from the same row.
+namespace {
+struct F32L1 : ProxL1<float> {};
+struct F32L1Aliased : ProxL1Aliased<float> {};
+struct F32L0 : ProxL0<float> {};
+struct F32L1Box : ProxL1Box<float> {};
+struct F32L0Box : ProxL0Box<float> {};
+struct F32IproxL1 : IproxL1<float> {};
+struct F32IproxL0 : IproxL0<float> {};
+struct F32IproxL1Box : IproxL1Box<float> {};
+struct F32IproxL0Box : IproxL0Box<float> {};
 
-SPX_EXPORT int spx_prox_l1(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
-                           double lambda, double sigma) {
-  int rc = spx_check_common(ctx, y, q, xk, sj, n);
-  if (rc) return rc;
-  if (y == q && lambda * sigma >= 0.0)  // the reference's two-pass body with y === q (see OpL1Aliased)
-    return run_separable(ctx, y, q, xk, sj, n, nullptr, nullptr, 0.0, 0.0, nullptr, OpL1Aliased{});
-  return run_separable(ctx, y, q, xk, sj, n, nullptr, nullptr, 0.0, 0.0, nullptr, make_l1<OpL1>(lambda, sigma));
-}
+struct RowL1 {
+  using Op = OpL1; using F32 = F32L1; using Term = HTermL1;
+  template <class O, class T> static O make(T lambda, T sigma) { return O{lambda * sigma}; }
+};
+struct RowL1Aliased {  // NormL1 with y === q: the reference's two-pass body overwrites q before it reads it
+  using Op = OpL1Aliased; using F32 = F32L1Aliased; using Term = HTermL1;
+  template <class O, class T> static O make(T, T) { return O{}; }
+};
+// ... which holds for lambda * sigma >= 0 (see ProxL1Aliased).  The Float32 form takes it for any lambda, and not at n == 0.
+bool l1_aliased(const SepCall<double>& c, double lambda, double sigma) { return c.y == c.q && lambda * sigma >= 0.0; }
+bool l1_aliased(const SepCall<float>& c, float, float) { return c.y == c.q && c.n > 0; }
+struct RowL0 {
+  using Op = OpL0; using F32 = F32L0; using Term = HTermL0;
+  template <class O, class T> static O make(T lambda, T sigma) { return O{std::sqrt(2 * lambda * sigma)}; }
+};
+struct RowLhalf {
+  using Op = OpLhalf; using Term = HTermLhalf;
+  template <class O> static O make(double lambda, double sigma) {
+    const double nl = sigma * lambda;
+    const double p = std::pow(54.0, 1.0 / 3.0) * std::pow(2 * nl, 2.0 / 3.0) / 4;  // shiftedRootNormLhalf.jl:49
+    return O{nl / 4, p};
+  }
+};
+struct RowL1Box {
+  using Op = OpL1Box; using F32 = F32L1Box; using Term = HTermL1;
+  template <class O, class T> static O make(T lambda, T sigma) { return O{sigma * lambda}; }
+};
+struct RowL0Box {
+  using Op = OpL0Box; using F32 = F32L0Box; using Term = HTermL0;
+  template <class O, class T> static O make(T lambda, T sigma) { return O{2 * lambda * sigma}; }
+};
+struct RowLhalfBox {
+  using Op = OpLhalfBox; using Term = HTermLhalf;
+  template <class O> static O make(double lambda, double sigma) { return O{sigma * lambda / 4, lambda, 0.5 / sigma}; }
+};
+// iprox!: the functors are {lambda} -- kFlagged: {lambda, flag}, the word they raise where d[i] <= 0
+struct RowIproxL1 { using Op = OpIproxL1; using F32 = F32IproxL1; using Term = HTermL1; static constexpr bool kFlagged = true; };
+struct RowIproxL0 { using Op = OpIproxL0; using F32 = F32IproxL0; using Term = HTermL0; static constexpr bool kFlagged = true; };
+struct RowIproxL1Box { using Op = OpIproxL1Box; using F32 = F32IproxL1Box; using Term = HTermL1; static constexpr bool kFlagged = false; };
+struct RowIproxL0Box { using Op = OpIproxL0Box; using F32 = F32IproxL0Box; using Term = HTermL0; static constexpr bool kFlagged = false; };
+template <class Row, class T>
+using RowOp = std::conditional_t<std::is_same<T, double>::value, typename Row::Op, typename Row::F32>;  // (rows with both)
+}  // namespace
 
-SPX_EXPORT int spx_prox_l0(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
-                           double lambda, double sigma) {
-  int rc = spx_check_common(ctx, y, q, xk, sj, n);
+template <class Row>
+static int run_prox(const SepCall<double>& c, double lambda, double sigma) {
+  const int rc = spx_check_common(c);
   if (rc) return rc;
-  return run_separable(ctx, y, q, xk, sj, n, nullptr, nullptr, 0.0, 0.0, nullptr, make_l0<OpL0>(lambda, sigma));
-}
-
-SPX_EXPORT int spx_prox_lhalf(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
-                              double lambda, double sigma) {
-  int rc = spx_check_common(ctx, y, q, xk, sj, n);
-  if (rc) return rc;
-  return run_separable(ctx, y, q, xk, sj, n, nullptr, nullptr, 0.0, 0.0, nullptr, make_lhalf(lambda, sigma));
-}
-
-SPX_EXPORT int spx_prox_l1_box(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
-                               double lambda, double sigma, const double* l_vec, const double* u_vec, double l_scalar,
-                               double u_scalar, const uint8_t* sel_mask) {
-  int rc = spx_check_common(ctx, y, q, xk, sj, n);
-  if (rc) return rc;
-  return run_separable(ctx, y, q, xk, sj, n, l_vec, u_vec, l_scalar, u_scalar, sel_mask, make_l1_box<OpL1Box>(lambda, sigma));
-}
-
-SPX_EXPORT int spx_prox_l0_box(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
-                               double lambda, double sigma, const double* l_vec, const double* u_vec, double l_scalar,
-                               double u_scalar, const uint8_t* sel_mask) {
-  int rc = spx_check_common(ctx, y, q, xk, sj, n);
-  if (rc) return rc;
-  return run_separable(ctx, y, q, xk, sj, n, l_vec, u_vec, l_scalar, u_scalar, sel_mask, make_l0_box<OpL0Box>(lambda, sigma));
-}
-
-SPX_EXPORT int spx_prox_lhalf_box(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj,
-                                  int64_t n, double lambda, double sigma, const double* l_vec, const double* u_vec,
-                                  double l_scalar, double u_scalar, const uint8_t* sel_mask) {
-  int rc = spx_check_common(ctx, y, q, xk, sj, n);
-  if (rc) return rc;
-  return run_separable(ctx, y, q, xk, sj, n, l_vec, u_vec, l_scalar, u_scalar, sel_mask,
-                       make_lhalf_box(lambda, sigma));
+  return run_separable(c, Row::template make<typename Row::Op>(lambda, sigma));
 }
 
 // ---------------------------------------------------------------------------------------------
 // prox! + value of h at the result, in one pass (synchronous: *value is written on the host)
 // ---------------------------------------------------------------------------------------------
-template <class Base, class Term>
-static int run_proxval(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
-                       const double* l, const double* u, double ls, double us, const uint8_t* mask, Base base,
-                       double lambda, double q_scale, double* value) {
-  int rc = spx_check_common(ctx, y, q, xk, sj, n);
+template <class Row>
+static int run_proxval(const SepCall<double>& c, double lambda, double sigma, double q_scale, double* value) {
+  int rc = spx_check_common(c);
   if (rc) return rc;
   SPX_REQUIRE(value != nullptr, "value is NULL");
-  WithValue<Base, Term> op{base, nullptr, q_scale};
+  WithValue<typename Row::Op, typename Row::Term> op{Row::template make<typename Row::Op>(lambda, sigma), nullptr, q_scale};
   *value = lambda * 0.0;  // (n == 0, or an error: -0.0 for a negative lambda, NaN for a non-finite one)
-  const SpxDest dest = spx_value_dest(ctx, value);
-  if (n == 0) return spx_dest_empty(ctx, {nullptr, dest.dev, 1});  // (the device side only: the host keeps lambda * 0)
-  rc = run_separable(ctx, y, q, xk, sj, n, l, u, ls, us, mask, op, nullptr, dest, lambda);
+  const SpxDest dest = spx_value_dest(c.ctx, value);
+  if (c.n == 0) return spx_dest_empty(c.ctx, {nullptr, dest.dev, 1});  // (the device side only: the host keeps lambda * 0)
+  rc = run_separable(c, op, dest, lambda);
   spx_value_nan_on_device(rc, dest, false, value);
   return rc;
-}
-
-SPX_EXPORT int spx_proxval_l1(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
-                              double lambda, double sigma, double q_scale, double* value) {
-  if (y == q && lambda * sigma >= 0.0) {  // the reference's two-pass body with y === q (see OpL1Aliased)
-    SPX_REQUIRE(q_scale == 1.0, "q_scale != 1 with y aliasing q");
-    return run_proxval<OpL1Aliased, HTermL1>(ctx, y, q, xk, sj, n, nullptr, nullptr, 0.0, 0.0, nullptr, OpL1Aliased{},
-                                             lambda, 1.0, value);
-  }
-  return run_proxval<OpL1, HTermL1>(ctx, y, q, xk, sj, n, nullptr, nullptr, 0.0, 0.0, nullptr,
-                                    make_l1<OpL1>(lambda, sigma), lambda, q_scale, value);
-}
-SPX_EXPORT int spx_proxval_l0(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
-                              double lambda, double sigma, double q_scale, double* value) {
-  return run_proxval<OpL0, HTermL0>(ctx, y, q, xk, sj, n, nullptr, nullptr, 0.0, 0.0, nullptr,
-                                    make_l0<OpL0>(lambda, sigma), lambda, q_scale, value);
-}
-SPX_EXPORT int spx_proxval_lhalf(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
-                                 double lambda, double sigma, double q_scale, double* value) {
-  return run_proxval<OpLhalf, HTermLhalf>(ctx, y, q, xk, sj, n, nullptr, nullptr, 0.0, 0.0, nullptr,
-                                          make_lhalf(lambda, sigma), lambda, q_scale, value);
-}
-SPX_EXPORT int spx_proxval_l1_box(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
-                                  double lambda, double sigma, const double* l_vec, const double* u_vec,
-                                  double l_scalar, double u_scalar, const uint8_t* sel_mask, double q_scale, double* value) {
-  return run_proxval<OpL1Box, HTermL1>(ctx, y, q, xk, sj, n, l_vec, u_vec, l_scalar, u_scalar, sel_mask,
-                                       make_l1_box<OpL1Box>(lambda, sigma), lambda, q_scale, value);
-}
-SPX_EXPORT int spx_proxval_l0_box(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
-                                  double lambda, double sigma, const double* l_vec, const double* u_vec,
-                                  double l_scalar, double u_scalar, const uint8_t* sel_mask, double q_scale, double* value) {
-  return run_proxval<OpL0Box, HTermL0>(ctx, y, q, xk, sj, n, l_vec, u_vec, l_scalar, u_scalar, sel_mask,
-                                       make_l0_box<OpL0Box>(lambda, sigma), lambda, q_scale, value);
-}
-SPX_EXPORT int spx_proxval_lhalf_box(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj,
-                                     int64_t n, double lambda, double sigma, const double* l_vec, const double* u_vec,
-                                     double l_scalar, double u_scalar, const uint8_t* sel_mask, double q_scale, double* value) {
-  return run_proxval<OpLhalfBox, HTermLhalf>(ctx, y, q, xk, sj, n, l_vec, u_vec, l_scalar, u_scalar, sel_mask,
-                                             make_lhalf_box(lambda, sigma), lambda, q_scale, value);
 }
 
 // ---------------------------------------------------------------------------------------------
 // prox! + step statistics in one pass (spx_proxstep_*): y, xkn = (xk + sj) + y, and {h, <q, y>, <y, y>} to a host double[3]
 // (synchronous) and / or a device double[3] (enqueue only).  Float64, device pointers, the six separable operators.
 // ---------------------------------------------------------------------------------------------
-template <class Base, class Term>
-static int run_proxstep(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
-                        const double* l, const double* u, double ls, double us, const uint8_t* mask, Base base,
-                        double lambda, double q_scale, double* xkn, double* stats, double* stats_dev) {
-  int rc = spx_check_common(ctx, y, q, xk, sj, n);
+template <class Row>
+static int run_proxstep(const SepCall<double>& c, double lambda, double sigma, double q_scale, const SpxDest& dest) {
+  int rc = spx_check_common(c);
   if (rc) return rc;
-  const SpxDest dest{stats, stats_dev, 3};
-  rc = spx_step_begin(ctx, dest, false, y, {q}, kSpxYAliasesQ, xkn, {y, q, xk, sj, l, u, mask});
+  rc = spx_step_begin(c.ctx, dest, false, c.y, {c.q}, kSpxYAliasesQ, c.xkn, c.others());
   if (rc) return rc;
-  if (n == 0) return spx_dest_empty(ctx, dest);
-  WithStep<Base, Term> op{};
-  static_cast<Base&>(op) = base;
+  if (c.n == 0) return spx_dest_empty(c.ctx, dest);
+  WithStep<typename Row::Op, typename Row::Term> op{};
+  static_cast<typename Row::Op&>(op) = Row::template make<typename Row::Op>(lambda, sigma);
   op.qscale = q_scale;
-  return run_separable(ctx, y, q, xk, sj, n, l, u, ls, us, mask, op, nullptr, dest, lambda, xkn);
+  return run_separable(c, op, dest, lambda);
 }
 
+// ---------------------------------------------------------------------------------------------
+// C entry points (Float64 prox!): each builds the call {ctx, y, q, d, xk, sj, n, box, xkn} from its arguments
+// ---------------------------------------------------------------------------------------------
+#define SPX_BOX_OF(T) SpxBox<T>{l_vec, u_vec, l_scalar, u_scalar, sel_mask}
+SPX_EXPORT int spx_prox_l1(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
+                           double lambda, double sigma) {
+  const SepCall<double> c{ctx, y, q, nullptr, xk, sj, n, {}, nullptr};
+  return l1_aliased(c, lambda, sigma) ? run_prox<RowL1Aliased>(c, lambda, sigma) : run_prox<RowL1>(c, lambda, sigma);
+}
+SPX_EXPORT int spx_proxval_l1(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
+                              double lambda, double sigma, double q_scale, double* value) {
+  const SepCall<double> c{ctx, y, q, nullptr, xk, sj, n, {}, nullptr};
+  if (!l1_aliased(c, lambda, sigma)) return run_proxval<RowL1>(c, lambda, sigma, q_scale, value);
+  SPX_REQUIRE(q_scale == 1.0, "q_scale != 1 with y aliasing q");  // (ahead of every other check)
+  return run_proxval<RowL1Aliased>(c, lambda, sigma, 1.0, value);
+}
 SPX_EXPORT int spx_proxstep_l1(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
                                double lambda, double sigma, double q_scale, double* xkn, double* stats, double* stats_dev) {
-  return run_proxstep<OpL1, HTermL1>(ctx, y, q, xk, sj, n, nullptr, nullptr, 0.0, 0.0, nullptr,
-                                     make_l1<OpL1>(lambda, sigma), lambda, q_scale, xkn, stats, stats_dev);
+  return run_proxstep<RowL1>({ctx, y, q, nullptr, xk, sj, n, {}, xkn}, lambda, sigma, q_scale, {stats, stats_dev, 3});
 }
-SPX_EXPORT int spx_proxstep_l0(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
-                               double lambda, double sigma, double q_scale, double* xkn, double* stats, double* stats_dev) {
-  return run_proxstep<OpL0, HTermL0>(ctx, y, q, xk, sj, n, nullptr, nullptr, 0.0, 0.0, nullptr,
-                                     make_l0<OpL0>(lambda, sigma), lambda, q_scale, xkn, stats, stats_dev);
-}
-SPX_EXPORT int spx_proxstep_lhalf(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
-                                  double lambda, double sigma, double q_scale, double* xkn, double* stats,
-                                  double* stats_dev) {
-  return run_proxstep<OpLhalf, HTermLhalf>(ctx, y, q, xk, sj, n, nullptr, nullptr, 0.0, 0.0, nullptr,
-                                           make_lhalf(lambda, sigma), lambda, q_scale, xkn, stats, stats_dev);
-}
-SPX_EXPORT int spx_proxstep_l1_box(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
-                                   double lambda, double sigma, const double* l_vec, const double* u_vec, double l_scalar,
-                                   double u_scalar, const uint8_t* sel_mask, double q_scale, double* xkn, double* stats,
-                                   double* stats_dev) {
-  return run_proxstep<OpL1Box, HTermL1>(ctx, y, q, xk, sj, n, l_vec, u_vec, l_scalar, u_scalar, sel_mask,
-                                        make_l1_box<OpL1Box>(lambda, sigma), lambda, q_scale, xkn, stats, stats_dev);
-}
-SPX_EXPORT int spx_proxstep_l0_box(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
-                                   double lambda, double sigma, const double* l_vec, const double* u_vec, double l_scalar,
-                                   double u_scalar, const uint8_t* sel_mask, double q_scale, double* xkn, double* stats,
-                                   double* stats_dev) {
-  return run_proxstep<OpL0Box, HTermL0>(ctx, y, q, xk, sj, n, l_vec, u_vec, l_scalar, u_scalar, sel_mask,
-                                        make_l0_box<OpL0Box>(lambda, sigma), lambda, q_scale, xkn, stats, stats_dev);
-}
-SPX_EXPORT int spx_proxstep_lhalf_box(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj,
-                                      int64_t n, double lambda, double sigma, const double* l_vec, const double* u_vec,
-                                      double l_scalar, double u_scalar, const uint8_t* sel_mask, double q_scale,
-                                      double* xkn, double* stats, double* stats_dev) {
-  return run_proxstep<OpLhalfBox, HTermLhalf>(ctx, y, q, xk, sj, n, l_vec, u_vec, l_scalar, u_scalar, sel_mask,
-                                              make_lhalf_box(lambda, sigma), lambda, q_scale, xkn, stats, stats_dev);
-}
+#define SPX_PROX3(PROX, PROXVAL, PROXSTEP, ROW)                                                                                \
+  SPX_EXPORT int PROX(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n, double lambda, \
+                      double sigma) {                                                                                         \
+    return run_prox<ROW>({ctx, y, q, nullptr, xk, sj, n, {}, nullptr}, lambda, sigma);                                         \
+  }                                                                                                                            \
+  SPX_EXPORT int PROXVAL(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,             \
+                         double lambda, double sigma, double q_scale, double* value) {                                        \
+    return run_proxval<ROW>({ctx, y, q, nullptr, xk, sj, n, {}, nullptr}, lambda, sigma, q_scale, value);                      \
+  }                                                                                                                            \
+  SPX_EXPORT int PROXSTEP(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,            \
+                          double lambda, double sigma, double q_scale, double* xkn, double* stats, double* stats_dev) {       \
+    return run_proxstep<ROW>({ctx, y, q, nullptr, xk, sj, n, {}, xkn}, lambda, sigma, q_scale, {stats, stats_dev, 3});         \
+  }
+SPX_PROX3(spx_prox_l0, spx_proxval_l0, spx_proxstep_l0, RowL0)
+SPX_PROX3(spx_prox_lhalf, spx_proxval_lhalf, spx_proxstep_lhalf, RowLhalf)
+#define SPX_PROX3_BOX(PROX, PROXVAL, PROXSTEP, ROW)                                                                            \
+  SPX_EXPORT int PROX(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n, double lambda, \
+                      double sigma, const double* l_vec, const double* u_vec, double l_scalar, double u_scalar,              \
+                      const uint8_t* sel_mask) {                                                                              \
+    return run_prox<ROW>({ctx, y, q, nullptr, xk, sj, n, SPX_BOX_OF(double), nullptr}, lambda, sigma);                         \
+  }                                                                                                                            \
+  SPX_EXPORT int PROXVAL(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,             \
+                         double lambda, double sigma, const double* l_vec, const double* u_vec, double l_scalar,             \
+                         double u_scalar, const uint8_t* sel_mask, double q_scale, double* value) {                           \
+    return run_proxval<ROW>({ctx, y, q, nullptr, xk, sj, n, SPX_BOX_OF(double), nullptr}, lambda, sigma, q_scale, value);      \
+  }                                                                                                                            \
+  SPX_EXPORT int PROXSTEP(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,            \
+                          double lambda, double sigma, const double* l_vec, const double* u_vec, double l_scalar,            \
+                          double u_scalar, const uint8_t* sel_mask, double q_scale, double* xkn, double* stats,               \
+                          double* stats_dev) {                                                                                \
+    return run_proxstep<ROW>({ctx, y, q, nullptr, xk, sj, n, SPX_BOX_OF(double), xkn}, lambda, sigma, q_scale,                 \
+                             {stats, stats_dev, 3});                                                                          \
+  }
+SPX_PROX3_BOX(spx_prox_l1_box, spx_proxval_l1_box, spx_proxstep_l1_box, RowL1Box)
+SPX_PROX3_BOX(spx_prox_l0_box, spx_proxval_l0_box, spx_proxstep_l0_box, RowL0Box)
+SPX_PROX3_BOX(spx_prox_lhalf_box, spx_proxval_lhalf_box, spx_proxstep_lhalf_box, RowLhalfBox)
 
 // ---------------------------------------------------------------------------------------------
 // Float32 vectors.  The reference's structs and prox! / iprox! methods are generic in R <: Real (src/shiftedNormL1Box.jl:89-94:
@@ -1217,17 +1185,7 @@ SPX_EXPORT int spx_proxstep_lhalf_box(spx_ctx* ctx, double* y, const double* q, 
 // peeled to a 16-byte boundary when all vectors share the misalignment; mixed alignments take 4-byte accesses.
 // y === q is safe (a lane reads q[i] before it writes y[i]; lanes own disjoint indices).
 // ---------------------------------------------------------------------------------------------
-namespace {
-
-struct F32L1 : ProxL1<float> {};
-struct F32L1Aliased : ProxL1Aliased<float> {};
-struct F32L0 : ProxL0<float> {};
-struct F32L1Box : ProxL1Box<float> {};
-struct F32L0Box : ProxL0Box<float> {};
-struct F32IproxL1 : IproxL1<float> {};
-struct F32IproxL0 : IproxL0<float> {};
-struct F32IproxL1Box : IproxL1Box<float> {};
-struct F32IproxL0Box : IproxL0Box<float> {};
+namespace {  // (the Float32 functors F32*: next to the operator table above)
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int kF32U = 4;                       // 16-byte groups per lane and vector
@@ -1316,74 +1274,72 @@ __global__ __launch_bounds__(256) void k_sep_f32_scalar(float* y, const float* q
   }
 }
 
+// v: the call at its aligned body
+template <class Op, bool VECB, bool MK>
+void launch_f32(const SepCall<float>& v, dim3 grid, int64_t n4, int head, int tail, Op op) {
+  hipLaunchKernelGGL((k_sep_f32<Op, VECB, MK>), grid, dim3(256), 0, v.ctx->stream, v.y, v.q, v.d, v.xk, v.sj, v.box.l, v.box.u,
+                     v.box.mask, v.box.ls, v.box.us, n4, head, tail, op);
+}
 template <class Op>
-int run_f32(spx_ctx* ctx, float* y, const float* q, const float* xk, const float* sj, int64_t n, const float* l,
-            const float* u, float ls, float us, const uint8_t* mask, Op op, const float* d = nullptr) {
-  int rc = spx_check_common(ctx, y, q, xk, sj, n);
+int run_f32(const SepCall<float>& c, Op op) {
+  int rc = spx_check_common(c);
   if (rc) return rc;
+  spx_ctx* const ctx = c.ctx;
+  const int64_t n = c.n;
   if (n == 0) return SPX_OK;
   SPX_ON_DEVICE(ctx);
-  auto mis = [](const void* p) { return (unsigned)(reinterpret_cast<uintptr_t>(p) & 15u); };
-  const unsigned m = mis(y);
-  bool same = (m % 4 == 0) && mis(q) == m && mis(xk) == m && mis(sj) == m && (!d || mis(d) == m);
-  if (Op::kBox) same = same && (!l || mis(l) == m) && (!u || mis(u) == m);
-  if (!same) {
+  if (!c.same_misalignment(Op::kBox)) {
     int64_t blocks = (n + 255) / 256;
     const int64_t cap = (int64_t)ctx->num_cu * 16;
     if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL((k_sep_f32_scalar<Op>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, y, q, d, xk, sj, l, u, mask, ls,
-                       us, n, op);
+    hipLaunchKernelGGL((k_sep_f32_scalar<Op>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, c.y, c.q, c.d, c.xk, c.sj,
+                       c.box.l, c.box.u, c.box.mask, c.box.ls, c.box.us, n, op);
     SPX_LAUNCH_CHECK();
     return SPX_OK;
   }
+  const unsigned m = (unsigned)(reinterpret_cast<uintptr_t>(c.y) & 15u);
   int head = (int)(((16u - m) / 4u) & 3u);
   if (head > n) head = (int)n;
   const int64_t n4 = (n - head) / 4;
   const int tail = (int)(n - head - 4 * n4);
   int64_t blocks = (n4 + kF32Tile - 1) / kF32Tile;
   if (blocks < 1) blocks = 1;
-  const dim3 grid((unsigned)blocks), block(256);
-  const bool vecb = Op::kBox && (l || u);
-  const bool msk = Op::kBox && mask != nullptr;
-  const uint8_t* mk = mask ? mask + head : nullptr;
-  const float* lp = l ? l + head : nullptr;
-  const float* up = u ? u + head : nullptr;
-  const float* dp = d ? d + head : nullptr;
-#define SPX_F32_LAUNCH(VB, MK)                                                                                         \
-  hipLaunchKernelGGL((k_sep_f32<Op, VB, MK>), grid, block, 0, ctx->stream, y + head, q + head, dp, xk + head, sj + head, lp, \
-                     up, mk, ls, us, n4, head, tail, op)
-  if (vecb && msk) SPX_F32_LAUNCH(true, true);
-  else if (vecb) SPX_F32_LAUNCH(true, false);
-  else if (msk) SPX_F32_LAUNCH(false, true);
-  else SPX_F32_LAUNCH(false, false);
-#undef SPX_F32_LAUNCH
+  const dim3 grid((unsigned)blocks);
+  const bool vecb = Op::kBox && (c.box.l || c.box.u);
+  const bool msk = Op::kBox && c.box.mask != nullptr;
+  const SepCall<float> v = c.shifted(head);
+  if (vecb && msk) launch_f32<Op, true, true>(v, grid, n4, head, tail, op);
+  else if (vecb) launch_f32<Op, true, false>(v, grid, n4, head, tail, op);
+  else if (msk) launch_f32<Op, false, true>(v, grid, n4, head, tail, op);
+  else launch_f32<Op, false, false>(v, grid, n4, head, tail, op);
   SPX_LAUNCH_CHECK();
   return SPX_OK;
+}
+template <class Row>
+int run_prox(const SepCall<float>& c, float lambda, float sigma) {
+  return run_f32(c, Row::template make<typename Row::F32>(lambda, sigma));
 }
 
 }  // namespace
 
 SPX_EXPORT int spx_prox_l1_f32(spx_ctx* ctx, float* y, const float* q, const float* xk, const float* sj, int64_t n,
                                float lambda, float sigma) {
-  if (y == q && n > 0) return run_f32(ctx, y, q, xk, sj, n, nullptr, nullptr, 0.0f, 0.0f, nullptr, F32L1Aliased{});
-  return run_f32(ctx, y, q, xk, sj, n, nullptr, nullptr, 0.0f, 0.0f, nullptr, make_l1<F32L1>(lambda, sigma));
+  const SepCall<float> c{ctx, y, q, nullptr, xk, sj, n, {}, nullptr};
+  return l1_aliased(c, lambda, sigma) ? run_prox<RowL1Aliased>(c, lambda, sigma) : run_prox<RowL1>(c, lambda, sigma);
 }
-
 SPX_EXPORT int spx_prox_l0_f32(spx_ctx* ctx, float* y, const float* q, const float* xk, const float* sj, int64_t n,
                                float lambda, float sigma) {
-  return run_f32(ctx, y, q, xk, sj, n, nullptr, nullptr, 0.0f, 0.0f, nullptr, make_l0<F32L0>(lambda, sigma));
+  return run_prox<RowL0>(SepCall<float>{ctx, y, q, nullptr, xk, sj, n, {}, nullptr}, lambda, sigma);
 }
-
 SPX_EXPORT int spx_prox_l1_box_f32(spx_ctx* ctx, float* y, const float* q, const float* xk, const float* sj, int64_t n,
                                    float lambda, float sigma, const float* l_vec, const float* u_vec, float l_scalar,
                                    float u_scalar, const uint8_t* sel_mask) {
-  return run_f32(ctx, y, q, xk, sj, n, l_vec, u_vec, l_scalar, u_scalar, sel_mask, make_l1_box<F32L1Box>(lambda, sigma));
+  return run_prox<RowL1Box>(SepCall<float>{ctx, y, q, nullptr, xk, sj, n, SPX_BOX_OF(float), nullptr}, lambda, sigma);
 }
-
 SPX_EXPORT int spx_prox_l0_box_f32(spx_ctx* ctx, float* y, const float* q, const float* xk, const float* sj, int64_t n,
                                    float lambda, float sigma, const float* l_vec, const float* u_vec, float l_scalar,
                                    float u_scalar, const uint8_t* sel_mask) {
-  return run_f32(ctx, y, q, xk, sj, n, l_vec, u_vec, l_scalar, u_scalar, sel_mask, make_l0_box<F32L0Box>(lambda, sigma));
+  return run_prox<RowL0Box>(SepCall<float>{ctx, y, q, nullptr, xk, sj, n, SPX_BOX_OF(float), nullptr}, lambda, sigma);
 }
 
 
@@ -1392,15 +1348,9 @@ SPX_EXPORT int spx_prox_l0_box_f32(spx_ctx* ctx, float* y, const float* q, const
 // ---------------------------------------------------------------------------------------------
 // the skeleton of each precision
 template <class Op>
-static int run_unboxed(spx_ctx* ctx, double* y, const double* g, const double* d, const double* xk, const double* sj,
-                       int64_t n, Op op) {
-  return run_separable(ctx, y, g, xk, sj, n, nullptr, nullptr, 0.0, 0.0, nullptr, op, d);
-}
+static int run_skeleton(const SepCall<double>& c, Op op) { return run_separable(c, op); }
 template <class Op>
-static int run_unboxed(spx_ctx* ctx, float* y, const float* g, const float* d, const float* xk, const float* sj, int64_t n,
-                       Op op) {
-  return run_f32(ctx, y, g, xk, sj, n, nullptr, nullptr, 0.0f, 0.0f, nullptr, op, d);
-}
+static int run_skeleton(const SepCall<float>& c, Op op) { return run_f32(c, op); }
 // The d > 0 flag word of the unboxed forms, read back (the stream is synchronised): the reference's assertion.
 static int iprox_check_flag(spx_ctx* ctx, const int* flag) {
   int bad = 0;
@@ -1412,48 +1362,28 @@ static int iprox_check_flag(spx_ctx* ctx, const int* flag) {
   }
   return SPX_OK;
 }
-// check_d: the d > 0 flag is read back, which synchronises the stream -- refused under a capture before anything is enqueued
-template <class Op, class T>
-static int run_iprox_unboxed(spx_ctx* ctx, T* y, const T* g, const T* d, const T* xk, const T* sj, int64_t n, T lambda,
-                             int check_d) {
-  int rc = spx_check_common(ctx, y, g, xk, sj, n);
+// check_d (the flagged rows): the d > 0 flag is read back, which synchronises the stream -- refused under a capture before
+// anything is enqueued
+template <class Row, class T>
+static int run_iprox(const SepCall<T>& c, T lambda, int check_d) {
+  int rc = spx_check_common(c);
   if (rc) return rc;
-  SPX_REQUIRE(n == 0 || d != nullptr, "d is NULL");
-  if (n == 0) return SPX_OK;
-  if (check_d) { rc = spx_require_not_capturing(ctx, "the d > 0 check of iprox! (pass check = 0)"); if (rc) return rc; }
-  rc = spx_ws_reserve(ctx, 256);
-  if (rc) return rc;
-  SPX_ON_DEVICE(ctx);
-  int* flag = reinterpret_cast<int*>(ctx->ws);
-  { const int rz = spx_zero_async(ctx, flag, sizeof(int)); if (rz) return rz; }
-  rc = run_unboxed(ctx, y, g, d, xk, sj, n, Op{lambda, flag});
-  if (rc || !check_d) return rc;
-  return iprox_check_flag(ctx, flag);
-}
-
-SPX_EXPORT int spx_iprox_l1(spx_ctx* ctx, double* y, const double* g, const double* d, const double* xk,
-                            const double* sj, int64_t n, double lambda, int check_d) {
-  return run_iprox_unboxed<OpIproxL1>(ctx, y, g, d, xk, sj, n, lambda, check_d);
-}
-SPX_EXPORT int spx_iprox_l0(spx_ctx* ctx, double* y, const double* g, const double* d, const double* xk,
-                            const double* sj, int64_t n, double lambda, int check_d) {
-  return run_iprox_unboxed<OpIproxL0>(ctx, y, g, d, xk, sj, n, lambda, check_d);
-}
-SPX_EXPORT int spx_iprox_l1_box(spx_ctx* ctx, double* y, const double* g, const double* d, const double* xk,
-                                const double* sj, int64_t n, double lambda, const double* l_vec, const double* u_vec,
-                                double l_scalar, double u_scalar, const uint8_t* sel_mask) {
-  int rc = spx_check_common(ctx, y, g, xk, sj, n);
-  if (rc) return rc;
-  SPX_REQUIRE(n == 0 || d != nullptr, "d is NULL");
-  return run_separable(ctx, y, g, xk, sj, n, l_vec, u_vec, l_scalar, u_scalar, sel_mask, OpIproxL1Box{lambda}, d);
-}
-SPX_EXPORT int spx_iprox_l0_box(spx_ctx* ctx, double* y, const double* g, const double* d, const double* xk,
-                                const double* sj, int64_t n, double lambda, const double* l_vec, const double* u_vec,
-                                double l_scalar, double u_scalar, const uint8_t* sel_mask) {
-  int rc = spx_check_common(ctx, y, g, xk, sj, n);
-  if (rc) return rc;
-  SPX_REQUIRE(n == 0 || d != nullptr, "d is NULL");
-  return run_separable(ctx, y, g, xk, sj, n, l_vec, u_vec, l_scalar, u_scalar, sel_mask, OpIproxL0Box{lambda}, d);
+  SPX_REQUIRE(c.n == 0 || c.d != nullptr, "d is NULL");
+  if constexpr (!Row::kFlagged) {
+    return run_skeleton(c, RowOp<Row, T>{lambda});
+  } else {
+    spx_ctx* const ctx = c.ctx;
+    if (c.n == 0) return SPX_OK;
+    if (check_d) { rc = spx_require_not_capturing(ctx, "the d > 0 check of iprox! (pass check = 0)"); if (rc) return rc; }
+    rc = spx_ws_reserve(ctx, 256);
+    if (rc) return rc;
+    SPX_ON_DEVICE(ctx);
+    int* flag = reinterpret_cast<int*>(ctx->ws);
+    { const int rz = spx_zero_async(ctx, flag, sizeof(int)); if (rz) return rz; }
+    rc = run_skeleton(c, RowOp<Row, T>{lambda, flag});
+    if (rc || !check_d) return rc;
+    return iprox_check_flag(ctx, flag);
+  }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1461,85 +1391,65 @@ SPX_EXPORT int spx_iprox_l0_box(spx_ctx* ctx, double* y, const double* g, const 
 // double[4] (synchronous) and / or a device double[4] (enqueue only).  Float64, device pointers.  All four operators take the
 // fused route, each on the skeleton of its plain iprox! (profiles/iproxstep_kres.txt).
 // ---------------------------------------------------------------------------------------------
-// flagged: the unboxed forms, whose functor raises a flag word where d[i] <= 0
-template <class Base, class Term, bool FLAGGED>
-static int run_iproxstep(spx_ctx* ctx, double* y, const double* g, const double* d, const double* xk, const double* sj,
-                         int64_t n, double lambda, int check_d, const double* l, const double* u, double ls, double us,
-                         const uint8_t* mask, double* xkn, double* stats, double* stats_dev) {
-  int rc = spx_check_common(ctx, y, g, xk, sj, n);
+template <class Row>
+static int run_iproxstep(const SepCall<double>& c, double lambda, int check_d, const SpxDest& dest) {
+  spx_ctx* const ctx = c.ctx;
+  int rc = spx_check_common(c);
   if (rc) return rc;
-  SPX_REQUIRE(n == 0 || d != nullptr, "d is NULL");
-  const SpxDest dest{stats, stats_dev, 4};
-  rc = spx_step_begin(ctx, dest, check_d != 0, y, {g, d}, "y aliases g or d (the sums would read an overwritten input)", xkn,
-                      {y, g, d, xk, sj, l, u, mask});
+  SPX_REQUIRE(c.n == 0 || c.d != nullptr, "d is NULL");
+  rc = spx_step_begin(ctx, dest, check_d != 0, c.y, {c.q, c.d}, "y aliases g or d (the sums would read an overwritten input)", c.xkn,
+                      c.others());
   if (rc) return rc;
-  if (n == 0) return spx_dest_empty(ctx, dest);
-  WithIstep<Base, Term> op{};
+  if (c.n == 0) return spx_dest_empty(ctx, dest);
+  WithIstep<typename Row::Op, typename Row::Term> op{};
   op.lambda = lambda;
   int* flag = nullptr;
-  if constexpr (FLAGGED) {
+  if constexpr (Row::kFlagged) {
     // the whole workspace of the call is reserved here, so that the flag word keeps its address through run_separable
-    rc = spx_ws_reserve(ctx, sep_ws_bytes(ctx, n, 4));
+    rc = spx_ws_reserve(ctx, sep_ws_bytes(ctx, c.n, 4));
     if (rc) return rc;
     SPX_ON_DEVICE(ctx);
     flag = reinterpret_cast<int*>(static_cast<char*>(ctx->ws) + kSepFlagOffset);  // (clear of the four result doubles)
     { const int rz = spx_zero_async(ctx, flag, sizeof(int)); if (rz) return rz; }
     op.flag = flag;
   }
-  rc = run_separable(ctx, y, g, xk, sj, n, l, u, ls, us, mask, op, d, dest, lambda, xkn);
+  rc = run_separable(c, op, dest, lambda);
   if (rc || !check_d) return rc;
-  if constexpr (FLAGGED) return iprox_check_flag(ctx, flag);  // (the stream has been synchronised by the copy of the statistics)
+  if constexpr (Row::kFlagged) return iprox_check_flag(ctx, flag);  // (the stream has been synchronised by the copy of the statistics)
   return SPX_OK;
 }
 
-SPX_EXPORT int spx_iproxstep_l1(spx_ctx* ctx, double* y, const double* g, const double* d, const double* xk,
-                                const double* sj, int64_t n, double lambda, int check_d, double* xkn, double* stats,
-                                double* stats_dev) {
-  return run_iproxstep<OpIproxL1, HTermL1, true>(ctx, y, g, d, xk, sj, n, lambda, check_d, nullptr, nullptr, 0.0, 0.0, nullptr,
-                                                 xkn, stats, stats_dev);
-}
-SPX_EXPORT int spx_iproxstep_l0(spx_ctx* ctx, double* y, const double* g, const double* d, const double* xk,
-                                const double* sj, int64_t n, double lambda, int check_d, double* xkn, double* stats,
-                                double* stats_dev) {
-  return run_iproxstep<OpIproxL0, HTermL0, true>(ctx, y, g, d, xk, sj, n, lambda, check_d, nullptr, nullptr, 0.0, 0.0, nullptr,
-                                                 xkn, stats, stats_dev);
-}
-SPX_EXPORT int spx_iproxstep_l1_box(spx_ctx* ctx, double* y, const double* g, const double* d, const double* xk,
-                                    const double* sj, int64_t n, double lambda, const double* l_vec, const double* u_vec,
-                                    double l_scalar, double u_scalar, const uint8_t* sel_mask, double* xkn, double* stats,
-                                    double* stats_dev) {
-  return run_iproxstep<OpIproxL1Box, HTermL1, false>(ctx, y, g, d, xk, sj, n, lambda, 0, l_vec, u_vec, l_scalar, u_scalar,
-                                                     sel_mask, xkn, stats, stats_dev);
-}
-SPX_EXPORT int spx_iproxstep_l0_box(spx_ctx* ctx, double* y, const double* g, const double* d, const double* xk,
-                                    const double* sj, int64_t n, double lambda, const double* l_vec, const double* u_vec,
-                                    double l_scalar, double u_scalar, const uint8_t* sel_mask, double* xkn, double* stats,
-                                    double* stats_dev) {
-  return run_iproxstep<OpIproxL0Box, HTermL0, false>(ctx, y, g, d, xk, sj, n, lambda, 0, l_vec, u_vec, l_scalar, u_scalar,
-                                                     sel_mask, xkn, stats, stats_dev);
-}
-
-SPX_EXPORT int spx_iprox_l1_f32(spx_ctx* ctx, float* y, const float* g, const float* d, const float* xk, const float* sj,
-                                int64_t n, float lambda, int check_d) {
-  return run_iprox_unboxed<F32IproxL1>(ctx, y, g, d, xk, sj, n, lambda, check_d);
-}
-SPX_EXPORT int spx_iprox_l0_f32(spx_ctx* ctx, float* y, const float* g, const float* d, const float* xk, const float* sj,
-                                int64_t n, float lambda, int check_d) {
-  return run_iprox_unboxed<F32IproxL0>(ctx, y, g, d, xk, sj, n, lambda, check_d);
-}
-SPX_EXPORT int spx_iprox_l1_box_f32(spx_ctx* ctx, float* y, const float* g, const float* d, const float* xk, const float* sj,
-                                    int64_t n, float lambda, const float* l_vec, const float* u_vec, float l_scalar,
-                                    float u_scalar, const uint8_t* sel_mask) {
-  int rc = spx_check_common(ctx, y, g, xk, sj, n);
-  if (rc) return rc;
-  SPX_REQUIRE(n == 0 || d != nullptr, "d is NULL");
-  return run_f32(ctx, y, g, xk, sj, n, l_vec, u_vec, l_scalar, u_scalar, sel_mask, F32IproxL1Box{lambda}, d);
-}
-SPX_EXPORT int spx_iprox_l0_box_f32(spx_ctx* ctx, float* y, const float* g, const float* d, const float* xk, const float* sj,
-                                    int64_t n, float lambda, const float* l_vec, const float* u_vec, float l_scalar,
-                                    float u_scalar, const uint8_t* sel_mask) {
-  int rc = spx_check_common(ctx, y, g, xk, sj, n);
-  if (rc) return rc;
-  SPX_REQUIRE(n == 0 || d != nullptr, "d is NULL");
-  return run_f32(ctx, y, g, xk, sj, n, l_vec, u_vec, l_scalar, u_scalar, sel_mask, F32IproxL0Box{lambda}, d);
-}
+// the entry points: q of the call holds g; the Box forms have no check_d
+#define SPX_IPROX3(IPROX, IPROXSTEP, IPROX_F32, ROW)                                                                           \
+  SPX_EXPORT int IPROX(spx_ctx* ctx, double* y, const double* g, const double* d, const double* xk, const double* sj,         \
+                       int64_t n, double lambda, int check_d) {                                                               \
+    return run_iprox<ROW>(SepCall<double>{ctx, y, g, d, xk, sj, n, {}, nullptr}, lambda, check_d);                             \
+  }                                                                                                                            \
+  SPX_EXPORT int IPROXSTEP(spx_ctx* ctx, double* y, const double* g, const double* d, const double* xk, const double* sj,     \
+                           int64_t n, double lambda, int check_d, double* xkn, double* stats, double* stats_dev) {            \
+    return run_iproxstep<ROW>({ctx, y, g, d, xk, sj, n, {}, xkn}, lambda, check_d, {stats, stats_dev, 4});                     \
+  }                                                                                                                            \
+  SPX_EXPORT int IPROX_F32(spx_ctx* ctx, float* y, const float* g, const float* d, const float* xk, const float* sj,          \
+                           int64_t n, float lambda, int check_d) {                                                            \
+    return run_iprox<ROW>(SepCall<float>{ctx, y, g, d, xk, sj, n, {}, nullptr}, lambda, check_d);                              \
+  }
+SPX_IPROX3(spx_iprox_l1, spx_iproxstep_l1, spx_iprox_l1_f32, RowIproxL1)
+SPX_IPROX3(spx_iprox_l0, spx_iproxstep_l0, spx_iprox_l0_f32, RowIproxL0)
+#define SPX_IPROX3_BOX(IPROX, IPROXSTEP, IPROX_F32, ROW)                                                                       \
+  SPX_EXPORT int IPROX(spx_ctx* ctx, double* y, const double* g, const double* d, const double* xk, const double* sj,         \
+                       int64_t n, double lambda, const double* l_vec, const double* u_vec, double l_scalar,                   \
+                       double u_scalar, const uint8_t* sel_mask) {                                                            \
+    return run_iprox<ROW>(SepCall<double>{ctx, y, g, d, xk, sj, n, SPX_BOX_OF(double), nullptr}, lambda, 0);                   \
+  }                                                                                                                            \
+  SPX_EXPORT int IPROXSTEP(spx_ctx* ctx, double* y, const double* g, const double* d, const double* xk, const double* sj,     \
+                           int64_t n, double lambda, const double* l_vec, const double* u_vec, double l_scalar,               \
+                           double u_scalar, const uint8_t* sel_mask, double* xkn, double* stats, double* stats_dev) {         \
+    return run_iproxstep<ROW>({ctx, y, g, d, xk, sj, n, SPX_BOX_OF(double), xkn}, lambda, 0, {stats, stats_dev, 4});           \
+  }                                                                                                                            \
+  SPX_EXPORT int IPROX_F32(spx_ctx* ctx, float* y, const float* g, const float* d, const float* xk, const float* sj,          \
+                           int64_t n, float lambda, const float* l_vec, const float* u_vec, float l_scalar, float u_scalar,   \
+                           const uint8_t* sel_mask) {                                                                         \
+    return run_iprox<ROW>(SepCall<float>{ctx, y, g, d, xk, sj, n, SPX_BOX_OF(float), nullptr}, lambda, 0);                     \
+  }
+SPX_IPROX3_BOX(spx_iprox_l1_box, spx_iproxstep_l1_box, spx_iprox_l1_box_f32, RowIproxL1Box)
+SPX_IPROX3_BOX(spx_iprox_l0_box, spx_iproxstep_l0_box, spx_iprox_l0_box_f32, RowIproxL0Box)
