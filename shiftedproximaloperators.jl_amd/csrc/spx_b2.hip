@@ -20,6 +20,7 @@
 #include <type_traits>
 
 #include "spx_common.hpp"
+#include "spx_plan.hpp"  // the constants the decision shares with the kernels; b2_plan
 
 namespace {
 
@@ -107,12 +108,7 @@ __global__ __launch_bounds__(256) void k_b2_obj(const double* __restrict__ y, co
 // REG: n <= 8 Ki x number of resident workgroups -- xk, sj and sj + q stay in registers, the vectors are read once.
 // !REG: two streaming passes (see the head of this file); VEC = 16-byte accesses, else 8-byte (views of mixed alignment).
 // =============================================================================================
-// register-resident form: 512 lanes x 16 elements per workgroup (256 VGPRs per lane).  1024 lanes x 8 spill under their 128
-// VGPRs (loop invariants the compiler keeps per element: the box ends, the store addresses), and the first touch of a wave's
-// scratch memory costs microseconds at the start of every launch; 1024 x 16 spill 120 registers and run 2x slower.
-constexpr int kB2Epl = 16;
-constexpr int kB2RegThreads = 512;
-constexpr int kB2RegBlock = kB2Epl * kB2RegThreads;  // elements per workgroup of the register-resident form
+// (the register-resident form, 512 lanes x 16 elements per workgroup: kB2Epl, kB2RegThreads, kB2RegBlock -- spx_plan.hpp)
 constexpr int kB2MaxPass = 64;
 // One workgroup's partial sums of a reduction: 8 words in spx_ctx::sync, at a FIXED place (set, reduction number, workgroup),
 // written once per launch.  A word is its own "ready" flag: the sync area starts out zero, a sum v is stored as
@@ -120,7 +116,7 @@ constexpr int kB2MaxPass = 64;
 // rendezvous, one memory round trip per reduction instead of four (store + wait, arrive, poll, load: 2.6-3.6 -> ~1.x us,
 // which is most of a call at n <= 1e6).  Launches alternate between two sets; a launch zeroes what the launch before the
 // previous one left in the other set (the host knows how many workgroups that was).
-constexpr int kB2Cols = 256;   // workgroups at most
+// (kB2Cols workgroups at most: spx_plan.hpp)
 constexpr int kB2Words = 8;
 constexpr size_t kB2SetWords = (size_t)kB2MaxPass * kB2Cols * kB2Words;
 constexpr size_t kB2SyncBytes = 2 * kB2SetWords * sizeof(unsigned long long);   // 2 MiB, behind the select state
@@ -1083,7 +1079,7 @@ constexpr auto b2_kernel() {
 
 // spx_proxstep_l1_b2: which forms have a fused STEP kernel (profiles/b2_proxstep_kres.txt: the rule is "no more scratch than the
 // VALUE twin of the form"); the others -- and every form under tuning key 18 = 1 -- take the composed route of the same call.
-enum B2Form { kB2FormReg = 0, kB2FormLds = 1, kB2FormVec = 2, kB2Form8 = 3 };
+// (B2Form: spx_plan.hpp)
 #ifndef SPX_B2_STEP_FUSED  // (tools/kres.sh compiles all four STEP kernels for the table: -DSPX_B2_STEP_FUSED=1,1,1,1)
 #define SPX_B2_STEP_FUSED 1, 1, 1, 0
 #endif
@@ -1129,37 +1125,18 @@ int run_b2(spx_ctx* ctx, double* y, const double* q, const double* xk, const dou
   SPX_ON_DEVICE(ctx);
   const double ls = lambda * sigma;  // `psi.lambda * sigma`, :56
   const bool vec = n >= 2 && spx_aligned16(y) && spx_aligned16(q) && spx_aligned16(xk) && spx_aligned16(sj);
-  // Residency (spx_resident_cap): the grid of a launch that synchronises inside itself never exceeds what can be resident
-  // at once; the streaming form works with any grid >= 1, the register-resident one needs ceil(n / 8192) workgroups.
-  const int64_t cap_reg = spx_resident_cap(ctx, reinterpret_cast<const void*>(b2_kernel<true, kB2Epl, kB2RegThreads, true, false, false>()), kB2RegThreads, 0);
-  const int64_t cap_mem = vec ? spx_resident_cap(ctx, reinterpret_cast<const void*>(b2_kernel<false, 1, 1024, true, false, false>()), 1024, 0)
-                              : spx_resident_cap(ctx, reinterpret_cast<const void*>(b2_kernel<false, 1, 1024, false, false, false>()), 1024, 0);
-  if (cap_mem < 1) return SPX_ERR_INTERNAL;  // (message set by spx_resident_cap)
-  const int64_t gmax_reg = cap_reg < kB2Cols ? cap_reg : kB2Cols;
-  const int64_t gmax_mem = cap_mem < kB2Cols ? cap_mem : kB2Cols;
-  const bool reg = n <= (int64_t)kB2RegBlock * gmax_reg;
-  // xk parked in LDS, 16 Ki elements per workgroup: between what the register form holds and 4 Mi (256 CUs); tuning key 12 = 0
-  // sends those sizes to the streaming form as in round 2 (n = 4e6: 111 us per call against 61)
-  bool ldsx = false;
-  int64_t gmax_lds = 0;
-  if (!reg && ctx->tune_b2_lds) {
-    const int64_t cap_lds = spx_resident_cap(ctx, reinterpret_cast<const void*>(b2_kernel<true, kB2Epl, 1024, true, true, false>()), 1024, 0);
-    gmax_lds = cap_lds < kB2Cols ? cap_lds : kB2Cols;
-    ldsx = n <= (int64_t)kB2Epl * 1024 * gmax_lds;
-  }
-  int64_t g = reg ? (n + kB2RegBlock - 1) / kB2RegBlock : gmax_mem;
-  if (ldsx) g = gmax_lds;  // (n > 2 Mi here unless the grid is capped: every resident workgroup, <= 16 elements per lane)
-  if (reg) {
-    // the register form: 4 / 8 / 16 elements per lane by n -- more workgroups sweep fewer elements each, until their exchange
-    // costs more than the sweep saves (us per call, Delta = 1, 16 / 8 / 4 / 2 per lane: n = 1e4 22.2 / 21.3 / 20.5 / 20.5;
-    // n = 1e5 25.4 / 23.3 / 22.5 / 23.4; n = 3e5 26.6 / 24.8 / 25.4 / 28.3; n = 1e6 30.4 / 31.9 / 31.1 / 31.4 -- tools/r3/b2_midn.py)
-    const int64_t epl = n <= 131072 ? 4 : n <= 524288 ? 8 : kB2Epl;
-    int64_t gg = (n + epl * kB2RegThreads - 1) / (epl * kB2RegThreads);
-    if (gg > gmax_reg) gg = gmax_reg;
-    if (gg > g) g = gg;
-  }
-  if (g < 1) g = 1;
-  const B2Form form = ldsx ? kB2FormLds : reg ? kB2FormReg : vec ? kB2FormVec : kB2Form8;
+  // form, grid and the streaming form's candidate regions: b2_plan (spx_plan.hpp), from the residency of the PLAIN kernels
+  const B2Plan plan = b2_plan(B2In{n, vec, ctx->tune_b2_lds}, sizeof(f64x2), [&](B2Form f) {
+    int64_t c = 0;
+    b2_with_form(f, [&](auto fc) {
+      constexpr int F = decltype(fc)::value;
+      c = spx_resident_cap(ctx, reinterpret_cast<const void*>(b2_form_kernel<F, false, false>()), b2_form_threads(F), 0);
+    });
+    return c;
+  });
+  if (!plan.ok) return SPX_ERR_INTERNAL;  // (message set by spx_resident_cap)
+  const B2Form form = plan.form;
+  const int64_t g = plan.g;
   if constexpr (STEP) {
     if (ctx->tune_b2_step_compose || !kB2StepFused[form])
       return b2_step_composed(ctx, y, q, xk, sj, n, lambda, sigma, delta, chi_lambda, q_scale, xkn, dest);
@@ -1181,17 +1158,10 @@ int run_b2(spx_ctx* ctx, double* y, const double* q, const double* xk, const dou
       return SPX_ERR_INTERNAL;
     }
   }
-  // streaming form: candidate regions, one per wavefront of the grid -- room for 8 % of its share of the vector (the bracket
-  // of +-1.5 % around the sample's root holds the breakpoints of 1-2 % on ordinary data; a full region = plain iteration)
   f64x2* cand = nullptr;
-  unsigned int cand_cap = 0;
-  if (!reg && !ldsx) {
-    const int64_t waves = g * 16;
-    const int64_t share = (n + waves - 1) / waves;
-    int64_t cap = share / 12 + 64;
-    if (cap > 0x7fffffff) cap = 0x7fffffff;
-    cand_cap = (unsigned int)cap;
-    rc = spx_ws_reserve(ctx, (size_t)waves * (size_t)cap * sizeof(f64x2) + 256);
+  const unsigned int cand_cap = plan.cand_cap;
+  if (plan.ws_bytes) {  // streaming form: the candidate regions
+    rc = spx_ws_reserve(ctx, plan.ws_bytes);
     if (rc) return rc;
     cand = reinterpret_cast<f64x2*>(ctx->ws);
   }

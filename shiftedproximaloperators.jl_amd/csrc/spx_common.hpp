@@ -7,6 +7,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <initializer_list>
+#include <type_traits>
 
 #include "spx.h"
 
@@ -222,6 +223,13 @@ static inline int spx_check_common(spx_ctx* ctx, const void* y, const void* q, c
 }
 
 static inline bool spx_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// f(std::integral_constant<int, W>{}) for the W among WS... that equals v: a runtime value (lanes per group, samples per lane,
+// a flag) as a template argument.  False when v is none of them (f is not called).
+template <int... WS, class F>
+static inline bool spx_with_lanes(int v, F&& f) {
+  return ((v == WS ? (f(std::integral_constant<int, WS>{}), true) : false) || ...);
+}
 
 // ---------------------------------------------------------------------------------------------
 // Where the `count` doubles that a call returns next to y go.  Built once, at the entry point, and passed down as an argument:

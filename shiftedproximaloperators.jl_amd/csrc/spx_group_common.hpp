@@ -8,6 +8,7 @@
 #include <type_traits>
 
 #include "spx_common.hpp"
+#include "spx_plan.hpp"  // kGtCols
 
 // ---------------------------------------------------------------------------------------------
 // team reductions: TEAM lanes (8, 16, 32, 64: aligned lane ranges of one wave; 256: the workgroup)
@@ -37,7 +38,6 @@ __device__ __forceinline__ double lanes_sum(double v) {
 // ---------------------------------------------------------------------------------------------
 constexpr int kTeamGrid = 1024;
 constexpr int kGtRows = 8;      // exchange rows, reused cyclically
-constexpr int kGtCols = 256;    // workgroups of a launch at most
 constexpr int kGtWords = 16;    // words per workgroup and row (one 128-byte line)
 constexpr int kGtVals = 10;     // values per reduction at most
 constexpr size_t kGtSetWords = (size_t)kGtRows * kGtCols * kGtWords;
@@ -1027,9 +1027,4 @@ static inline int spx_group_lanes_by_typical(int64_t typical) {
   int lanes = 1;
   while (lanes < 64 && (int64_t)lanes * 4 < typical) lanes *= 2;
   return lanes;
-}
-// f(std::integral_constant<int, W>{}) for the W among WS... that equals lanes: the runtime width as a template argument.
-template <int... WS, class F>
-static inline bool spx_with_lanes(int lanes, F&& f) {
-  return ((lanes == WS ? (f(std::integral_constant<int, WS>{}), true) : false) || ...);
 }

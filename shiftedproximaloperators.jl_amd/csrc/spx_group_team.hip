@@ -31,13 +31,12 @@
 
 namespace {
 
-constexpr int kTmThreads = 1024;
+// (kTmThreads lanes per workgroup, kTmMaxJobs large groups in a device-side plan at most: spx_plan.hpp, with team_layout)
 constexpr int kTmDmaKiB = 3;                                           // KiB per wavefront, vector and tile
 constexpr int kTmLdsBytes = (kTmThreads / 64) * 3 * kTmDmaKiB * 1024;  // 144 KiB
 constexpr int kTmChipElems = kTmLdsBytes / 16;                         // S and X of 9216 elements per workgroup
 constexpr int64_t kTmTilePairs = (int64_t)(kTmThreads / 64) * 64 * kTmDmaKiB;  // 3072 pairs = 6144 elements per tile
 constexpr int kTmMaxSpl = 4;                                           // samples per lane at most
-constexpr int kTmMaxJobs = 65536;                                      // large groups a device-side plan holds at most
 enum { kFormChip = 0, kFormStream = 1, kFormFast = 2 };               // the three kernels (k_group_team)
 
 // Device-side plan of a ragged layout (CSR offsets): which groups are large, and which workgroups own them.
@@ -910,70 +909,31 @@ extern "C" __attribute__((visibility("default"))) int spx_debug_team_stamps(unsi
 //   kernel, then spx_group_team_launch -- nothing in between may touch ctx->ws.
 // ---------------------------------------------------------------------------------------------
 namespace {
-struct TeamLayout {
-  bool vec;
-  int par, G, Wu;
-  int64_t grid;
-  size_t plan_bytes, status_bytes, cand_bytes;
-  unsigned int cand_cap;
-};
-int team_layout(spx_ctx* ctx, bool binf, const double* y, const double* q, const double* xk, const double* sj, int64_t n,
-                const int64_t* offsets, int64_t gsize, int64_t ngroups, TeamLayout* L) {
-  const auto bit3 = [](const void* p) { return (int)((reinterpret_cast<uintptr_t>(p) >> 3) & 1u); };
-  L->par = bit3(q);
-  L->vec = bit3(xk) == L->par && bit3(sj) == L->par && bit3(y) == L->par;
+// team_layout (spx_plan.hpp) for a call: the alignment of its vectors, then the residency of the kernel that alignment picks
+int team_layout_of(spx_ctx* ctx, bool binf, const double* y, const double* q, const double* xk, const double* sj, int64_t n,
+                   const int64_t* offsets, int64_t gsize, int64_t ngroups, TeamLayout* L) {
+  const auto addr = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
+  team_alignment(addr(y), addr(q), addr(xk), addr(sj), L);
   // (every form is a 1024-lane workgroup holding 144 KiB of LDS: one per CU whatever the registers; asked of the largest)
   const void* fn = binf ? (L->vec ? reinterpret_cast<const void*>(&k_group_team<true, true, kFormFast>) : reinterpret_cast<const void*>(&k_group_team<true, false, kFormFast>))
                         : (L->vec ? reinterpret_cast<const void*>(&k_group_team<false, true, kFormStream>) : reinterpret_cast<const void*>(&k_group_team<false, false, kFormStream>));
-  int64_t cap = spx_resident_cap(ctx, fn, kTmThreads, 0);
-  if (cap > kGtCols) cap = kGtCols;
-  if (cap < 1) return SPX_ERR_INTERNAL;  // (message set by spx_resident_cap)
-  L->G = (int)cap;
-  L->Wu = 1;
-  L->grid = L->G;
-  int64_t per_wg = 2 * ((n + L->G - 1) / L->G);  // elements of one job per workgroup (a device-side plan: at most about that)
-  if (!offsets) {
-    if (ngroups < L->G) {
-      int64_t w = L->G / ngroups;
-      const int64_t wmax = (gsize + 2047) / 2048;  // no fewer than ~2048 elements per workgroup
-      if (w > wmax) w = wmax;
-      if (w < 1) w = 1;
-      L->Wu = (int)w;
-      L->grid = ngroups * w;
-    }
-    per_wg = (gsize + L->Wu - 1) / L->Wu;
-  }
-  L->plan_bytes = offsets ? ((sizeof(TeamPlanHdr) + (size_t)kTmMaxJobs * sizeof(TeamJob) + 255) & ~(size_t)255) : 0;
-  {  // one word per job: at most kTmMaxJobs jobs in a device-side plan, ngroups jobs for uniform groups
-    size_t jobs_max = (size_t)kTmMaxJobs;
-    if (!offsets && (size_t)ngroups > jobs_max) jobs_max = (size_t)ngroups;
-    L->status_bytes = (jobs_max * sizeof(int) + 255) & ~(size_t)255;
-  }
-  L->cand_cap = 0;
-  L->cand_bytes = 0;
-  if (binf && ctx->tune_team_fast) {
-    // one candidate region per wavefront of the grid: a quarter of the wavefront's share of a job (the breakpoints inside a
-    // bracket of +-hw around the sample's root are a few times hw of the elements on ordinary data; a full region = the
-    // generic body decides)
-    int64_t c = per_wg / (kTmThreads / 64) / 4 + 64;
-    if (c > 0x7fffffff) c = 0x7fffffff;
-    L->cand_cap = (unsigned int)c;
-    L->cand_bytes = (size_t)L->grid * (kTmThreads / 64) * (size_t)c * sizeof(f64x2);
-  }
+  if (team_layout(spx_resident_cap(ctx, fn, kTmThreads, 0), ctx->tune_team_fast, binf, n, offsets != nullptr, gsize, ngroups,
+                  sizeof(TeamPlanHdr), sizeof(TeamJob), sizeof(f64x2), L))
+    return SPX_ERR_INTERNAL;  // (message set by spx_resident_cap)
   return SPX_OK;
 }
 }  // namespace
 
 int spx_group_team_max_grid(spx_ctx* ctx, bool binf) {  // workgroups a team launch can have at most (<= kGtCols)
   TeamLayout L;
-  if (team_layout(ctx, binf, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 1, 1, &L)) return 0;
+  if (team_layout_of(ctx, binf, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 1, 1, &L)) return 0;
   return L.G;
 }
 
 int spx_group_team_plan(spx_ctx* ctx, bool binf, const double* y, const double* q, const double* xk, const double* sj,
                         int64_t n, const int64_t* offsets, int64_t ngroups, int64_t big_min, const int** active_dev) {
   TeamLayout L;
-  int rc = team_layout(ctx, binf, y, q, xk, sj, n, offsets, 0, ngroups, &L);
+  int rc = team_layout_of(ctx, binf, y, q, xk, sj, n, offsets, 0, ngroups, &L);
   if (rc) return rc;
   rc = spx_ws_reserve(ctx, L.plan_bytes + L.status_bytes + L.cand_bytes + 256);
   if (rc) return rc;
@@ -991,7 +951,7 @@ int spx_group_team_launch(spx_ctx* ctx, bool binf, double* y, const double* q, c
                           const int64_t* offsets, int64_t gsize, int64_t ngroups, const double* lambda, double sigma,
                           double delta) {
   TeamLayout L;
-  int rc = team_layout(ctx, binf, y, q, xk, sj, n, offsets, gsize, ngroups, &L);
+  int rc = team_layout_of(ctx, binf, y, q, xk, sj, n, offsets, gsize, ngroups, &L);
   if (rc) return rc;
   rc = spx_ws_reserve(ctx, L.plan_bytes + L.status_bytes + L.cand_bytes + 256);  // (after spx_group_team_plan: the same size, nothing moves)
   if (rc) return rc;

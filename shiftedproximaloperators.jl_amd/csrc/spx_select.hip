@@ -15,6 +15,7 @@
 #include <type_traits>
 
 #include "spx_common.hpp"
+#include "spx_plan.hpp"  // the constants the decisions share with the kernels; sel_plan, sel_fast_ws
 
 namespace {
 
@@ -160,7 +161,6 @@ struct SelWs {
 // Candidates of the main pass: every WAVEFRONT of its grid owns a fixed region of kWaveSlots entries and one count
 // word {candidates, elements above the band}: no atomics, no barrier, nothing a wave has to wait for before it exits,
 // and a candidate order that is the same run to run.
-constexpr int kWaveSlots = 64;
 struct WaveCount {
   unsigned int cand, above;
 };
@@ -177,10 +177,6 @@ struct Cand {
   int64_t idx;
   double val;
 };
-
-constexpr int kMainUnroll = 6;        // KiB per wave and vector in the main pass (as k_sep_lds)
-constexpr int kMainTilePairs = 256 * kMainUnroll;  // 16-byte pairs per workgroup of the main pass
-constexpr int kShortList = 4096;      // candidates left after the first digit that k_s2_finish resolves in LDS
 
 // bits(|v|): ordered like |v| for finite values and Inf.  Every NaN maps to ONE key above Inf: the reference's sort
 // compares with isless, where NaN is the largest value and all NaNs are equal (ties -> ascending index).
@@ -396,7 +392,6 @@ __device__ __forceinline__ T sel_out(T v, int64_t i, T x, T s, const SelState& s
 // exponent bins for the LDS atomics), index digits for ties, final pass.  Lane t owns elements t, t + 1024, ... in
 // every pass, so y needs no fence between passes.
 // =============================================================================================
-constexpr int64_t kSmallNCoop = 1 << 13;  // k_sel_coop serves the sizes above (see run_select)
 template <bool BINF, class T = double>
 __global__ __launch_bounds__(1024) void k_sel_small(T* y, const T* q, const T* xk, const T* sj, int64_t n,
                                                      int64_t r, T delta) {
@@ -1070,7 +1065,6 @@ constexpr int kSelStatSlot = kCoopMaxPass - 1;
 #define SPX_COOP_FOLD 1
 #endif
 constexpr bool kCoopFold = SPX_COOP_FOLD != 0;
-constexpr int kCoopEpl = 8;       // REG: elements per lane at most (16 spill: 1024-lane workgroups leave 128 VGPRs per lane)
 struct SelSync {
   SpxSyncHeader hdr;  // grid-barrier counters (a launch uses hdr.bar[parity] and clears hdr.bar[parity ^ 1])
   // One global histogram per pass.  k_sel_coop alternates between sets 0 and 1: a launch uses the clean one and clears
@@ -1435,9 +1429,6 @@ __global__ __launch_bounds__(1024) void k_sel_coop(T* y, const T* q, const T* xk
 // xk + sj, but not what the unrolled digit code of 16 elements wants on top: 492 B of scratch per lane); from LDS the digit
 // loop stays rolled.  Passes, rendezvous and scan are those of coop_select.
 // ---------------------------------------------------------------------------------------------
-constexpr int kLdsEpl = 16;      // Float64: elements per lane (128 KiB of LDS per 1024-lane workgroup)
-constexpr int kLdsEpl32 = 32;    // Float32
-constexpr int64_t kLdsMinN = (int64_t)1 << 20;  // k_sel_lds serves the sizes above this (and below what the resident grid holds: run_select)
 template <class T> struct SelVec;   // a 16-byte vector of T
 template <> struct SelVec<double> { typedef f64x2 type; };
 template <> struct SelVec<float> { typedef float type __attribute__((ext_vector_type(4))); };
@@ -1451,7 +1442,6 @@ template <> struct SelVec<float> { typedef float type __attribute__((ext_vector_
 // workgroup, 6 Mi on 256 CUs.  The registers come from xk + sj, which this form does not keep (32 of them for 16 elements): the
 // storing phase re-reads xk and sj -- 16 B per element more, from the memory-side cache the load phase has just filled -- and
 // forms xk + sj again (the same addition: the same bits).  48 B per element moved instead of 32, in one launch.
-constexpr int kLdsRegX = 8;
 template <bool BINF, bool VEC, class T = double, int REGX = 0>
 __global__ __launch_bounds__(1024) void k_sel_lds(T* y, const T* q, const T* xk, const T* sj, int64_t n,
                                                    int64_t r, T delta, SelSync* ss, int parity, int use_set, int clear_set) {
@@ -2048,7 +2038,6 @@ __global__ __launch_bounds__(1024) void k_s2_tail(double* y, const double* q, co
 // of the main pass (n = 1e8: r = n/2 670 -> 619 us, r = n/100 575 -> 568 us) for ~2 us more here -- and costs more than it
 // saves while the sample is a sizeable part of the vector (n = 3e6: 63 -> 70 us): 1 below 2^23, 2 below 2^25, 4 from there on
 // (tools/r2/topr_big.py).
-constexpr int kFrontBlocks = 64;
 constexpr int kFrontMaxDigits = 6;      // the sample ranks are bracketed to 2-3 x 12 key bits; to all 64 in tie mode
 constexpr unsigned int kPickFine = 16;  // samples per selected bucket below which no further digit is resolved
 template <int kFrontSpl>
@@ -2377,14 +2366,8 @@ __global__ __launch_bounds__(1024) void k_s2_front(const double* q, const double
   SEL_STAMP(15);
 }
 
-#ifndef SPX_SEL_REG_MAX_LOG2
-#define SPX_SEL_REG_MAX_LOG2 21  // largest n (log2) on the register-resident one-launch select = what 256 CUs hold at 8 elements per lane (n = 2e6: 37 us vs 57 us for the sample-predicted pipeline; beyond it the one-launch form parks v in y and is no faster: tools/r2/topr_midn.py)
-#endif
-
-// The exact select in ONE launch, for both precisions: k_sel_coop (v in registers: kCoopReg; v parked in y: kCoopMem) or
-// k_sel_lds (v parked in LDS; kLdsRegX: and 8 more elements per lane in registers, Float64 and 16-byte aligned vectors only)
-// on the grid the caller's precision chose (run_select), with the histogram-set / parity state around it.
-enum class SelForm { kCoopReg, kCoopMem, kLds, kLdsRegX };
+// The exact select in ONE launch, for both precisions: the kernel of the plan's form (SelForm, spx_plan.hpp) on the plan's
+// grid (sel_plan), with the histogram-set / parity state around it.
 template <bool BINF, class T>
 int launch_sel_exact(spx_ctx* ctx, SelForm form, bool vec, int64_t g, T* y, const T* q, const T* xk, const T* sj, int64_t n,
                      int64_t r, T delta) {
@@ -2430,45 +2413,32 @@ int launch_sel_exact(spx_ctx* ctx, SelForm form, bool vec, int64_t g, T* y, cons
 // with the exact select queued behind it as the fallback (k_s2_tail)
 template <bool BINF>
 int run_select_fast(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n, int64_t r,
-                    double delta, int ioff, int spl) {
+                    double delta, const SelPlan& plan) {
   int rc = spx_sync_ready(ctx);
   if (rc) return rc;
   SelSync* ss = reinterpret_cast<SelSync*>(ctx->sync);
   const bool graph_safe = spx_graph_safe(ctx);
-  const int64_t cap_tail = spx_resident_cap(ctx, reinterpret_cast<const void*>(&k_s2_tail<BINF>), 1024, 0);
-  if (cap_tail < 1) return SPX_ERR_INTERNAL;
-  const int64_t g_tail = cap_tail < 256 ? (cap_tail < ctx->num_cu ? cap_tail : ctx->num_cu) : (ctx->num_cu < 256 ? ctx->num_cu : 256);  // (<= 256: SelSync::tie_part)
+  const int ioff = plan.ioff;
   int tail_hook = 0;
 #ifdef SPX_TEST_HOOKS  // the planted fault of tests/test_gpu_robustness.py (key 101): the last workgroup of the tail kernel leaves
   tail_hook = ctx->tune_force_tail > 0 ? 2 : 0;  // without arriving anywhere, as if it had never been placed -- the others give up waiting
 #endif
-  // fast path scratch: one candidate region + count word per wavefront of the main pass
-  const int64_t n2 = (n - ioff) >> 1;
-  const int64_t mblocks = (n2 + kMainTilePairs - 1) / kMainTilePairs;
-  const int64_t nregions = mblocks * 4;
-  const int64_t ccap = nregions * kWaveSlots;
-  // the shared overflow list behind the per-wave regions: room for a band that is contiguous in the vector (sorted input)
-  const int64_t ovf_cap64 = (n / 64 > 65536) ? n / 64 : 65536;
-  const unsigned int ovf_cap = (unsigned int)(ovf_cap64 > 0x7fffffff ? 0x7fffffff : ovf_cap64);
-  const size_t off_cnt = 256;
-  const size_t off_cls = (off_cnt + (size_t)nregions * sizeof(WaveCount) + 255) & ~(size_t)255;   // tie mode: class members per slot
-  const size_t off_ckey = (off_cls + (size_t)(nregions + 2) * sizeof(ClassCount) + 255) & ~(size_t)255;
-  const size_t off_lkey = off_ckey + ((size_t)ccap + (size_t)ovf_cap) * sizeof(Cand);
-  const size_t off_lidx = off_lkey + (size_t)kShortList * sizeof(uint64_t);
-  const size_t off_lval = off_lidx + (size_t)kShortList * sizeof(int64_t);
-  rc = spx_ws_reserve(ctx, off_lval + (size_t)kShortList * sizeof(double) + 256);
+  const SelFastWs w = sel_fast_ws(n, ioff, sizeof(WaveCount), sizeof(ClassCount), sizeof(Cand));
+  rc = spx_ws_reserve(ctx, w.bytes);
   if (rc) return rc;
   char* wsb = reinterpret_cast<char*>(ctx->ws);
-  WaveCount* counts = reinterpret_cast<WaveCount*>(wsb + off_cnt);
-  ClassCount* cls = reinterpret_cast<ClassCount*>(wsb + off_cls);
-  Cand* cand = reinterpret_cast<Cand*>(wsb + off_ckey);
+  WaveCount* counts = reinterpret_cast<WaveCount*>(wsb + w.off_cnt);
+  ClassCount* cls = reinterpret_cast<ClassCount*>(wsb + w.off_cls);
+  Cand* cand = reinterpret_cast<Cand*>(wsb + w.off_ckey);
+  const int64_t nregions = w.nregions, ccap = w.ccap;
+  const unsigned int ovf_cap = w.ovf_cap;
   // single-pass form when y overlaps none of the inputs (a failed prediction recomputes everything from them)
   auto disjoint = [&](const double* a) { return (y + n <= a) || (a + n <= y); };
   const bool write = ctx->tune_sel_spec && disjoint(q) && disjoint(xk) && disjoint(sj);
-  uint64_t* lkey = reinterpret_cast<uint64_t*>(wsb + off_lkey);
-  int64_t* lidx = reinterpret_cast<int64_t*>(wsb + off_lidx);
-  double* lval = reinterpret_cast<double*>(wsb + off_lval);
-  const dim3 mgrid((unsigned)mblocks);
+  uint64_t* lkey = reinterpret_cast<uint64_t*>(wsb + w.off_lkey);
+  int64_t* lidx = reinterpret_cast<int64_t*>(wsb + w.off_lidx);
+  double* lval = reinterpret_cast<double*>(wsb + w.off_lval);
+  const dim3 mgrid((unsigned)w.mblocks);
   // front (sample + band, one in-launch synchronised kernel) -> main pass -> verdict / candidates -> fallback (exact
   // select; returns at once when the verdict is positive).  Nothing is read back.
   SelWs* sws = &ss->ws;
@@ -2483,156 +2453,95 @@ int run_select_fast(spx_ctx* ctx, double* y, const double* q, const double* xk, 
   }
   {
     SpxCoopLaunchGuard guard(ctx);
-    if (spl == 16)
-      hipLaunchKernelGGL(k_s2_front<16>, dim3(kFrontBlocks), dim3(1024), 0, ctx->stream, q + ioff, xk + ioff, sj + ioff,
-                         n - ioff, r, ss, ctx->track.coop_parity);
-    else if (spl == 4)
-      hipLaunchKernelGGL(k_s2_front<4>, dim3(kFrontBlocks), dim3(1024), 0, ctx->stream, q + ioff, xk + ioff, sj + ioff,
-                         n - ioff, r, ss, ctx->track.coop_parity);
-    else if (spl == 2)
-      hipLaunchKernelGGL(k_s2_front<2>, dim3(kFrontBlocks), dim3(1024), 0, ctx->stream, q + ioff, xk + ioff, sj + ioff,
-                         n - ioff, r, ss, ctx->track.coop_parity);
-    else
-      hipLaunchKernelGGL(k_s2_front<1>, dim3(kFrontBlocks), dim3(1024), 0, ctx->stream, q + ioff, xk + ioff, sj + ioff,
-                         n - ioff, r, ss, ctx->track.coop_parity);
+    spx_with_lanes<16, 4, 2, 1>(plan.spl, [&](auto spl) {
+      hipLaunchKernelGGL(k_s2_front<decltype(spl)::value>, dim3(kFrontBlocks), dim3(1024), 0, ctx->stream, q + ioff, xk + ioff,
+                         sj + ioff, n - ioff, r, ss, ctx->track.coop_parity);
+    });
     ctx->track.coop_parity ^= 1;
-    if (write)
-      hipLaunchKernelGGL((k_s2_main<BINF, true>), mgrid, dim3(256), 0, ctx->stream, y + ioff, q + ioff, xk + ioff,
-                         sj + ioff, n - ioff, sws, cand, counts, delta, ioff, ccap, ovf_cap, cls, nregions);
-    else
-      hipLaunchKernelGGL((k_s2_main<BINF, false>), mgrid, dim3(256), 0, ctx->stream, y + ioff, q + ioff, xk + ioff,
-                         sj + ioff, n - ioff, sws, cand, counts, delta, ioff, ccap, ovf_cap, cls, nregions);
-    // (tried: verdict + first digit redone by every workgroup of the candidate walk instead of the one-workgroup launch in
-    //  front of it -- 598 vs 571 us per call at n = 1e8: 512 workgroups x 64 KiB of L2 reads and the scan chain cost more
-    //  than the launch they save)
-    hipLaunchKernelGGL(k_s2_scan_verify, dim3(1), dim3(256), 0, ctx->stream, sws, r);
-    if (write) {
-      hipLaunchKernelGGL((k_s2_compact<true, BINF>), dim3(512), dim3(256), 0, ctx->stream, y, (const Cand*)cand, sws, lkey, lidx,
+    spx_with_lanes<1, 0>(write ? 1 : 0, [&](auto wr) {
+      constexpr bool W = decltype(wr)::value != 0;
+      hipLaunchKernelGGL((k_s2_main<BINF, W>), mgrid, dim3(256), 0, ctx->stream, y + ioff, q + ioff, xk + ioff, sj + ioff,
+                         n - ioff, sws, cand, counts, delta, ioff, ccap, ovf_cap, cls, nregions);
+      // (tried: verdict + first digit redone by every workgroup of the candidate walk instead of the one-workgroup launch in
+      //  front of it -- 598 vs 571 us per call at n = 1e8: 512 workgroups x 64 KiB of L2 reads and the scan chain cost more
+      //  than the launch they save)
+      hipLaunchKernelGGL(k_s2_scan_verify, dim3(1), dim3(256), 0, ctx->stream, sws, r);
+      hipLaunchKernelGGL((k_s2_compact<W, BINF>), dim3(512), dim3(256), 0, ctx->stream, y, (const Cand*)cand, sws, lkey, lidx,
                          lval, (const WaveCount*)counts, nregions, ovf_cap, xk, sj, delta);
-      hipLaunchKernelGGL((k_s2_finish<true, BINF>), dim3(1), dim3(1024), 0, ctx->stream, y, sws, (const uint64_t*)lkey,
+      hipLaunchKernelGGL((k_s2_finish<W, BINF>), dim3(1), dim3(1024), 0, ctx->stream, y, sws, (const uint64_t*)lkey,
                          (const int64_t*)lidx, (const double*)lval, xk, sj, delta);
-    } else {
-      hipLaunchKernelGGL((k_s2_compact<false, BINF>), dim3(512), dim3(256), 0, ctx->stream, y, (const Cand*)cand, sws, lkey, lidx,
-                         lval, (const WaveCount*)counts, nregions, ovf_cap, xk, sj, delta);
-      hipLaunchKernelGGL((k_s2_finish<false, BINF>), dim3(1), dim3(1024), 0, ctx->stream, y, sws, (const uint64_t*)lkey,
-                         (const int64_t*)lidx, (const double*)lval, xk, sj, delta);
-    }
-    hipLaunchKernelGGL((k_s2_tail<BINF>), dim3((unsigned)g_tail), dim3(1024), 0, ctx->stream, y, q, xk, sj, n, r, delta, ss,
+    });
+    hipLaunchKernelGGL((k_s2_tail<BINF>), dim3((unsigned)plan.g_tail), dim3(1024), 0, ctx->stream, y, q, xk, sj, n, r, delta, ss,
                        ctx->track.coop_parity, (const Cand*)cand, (const WaveCount*)counts, nregions, ovf_cap,
                        (const ClassCount*)cls, ioff, (write ? 1 : 0) | tail_hook);
     ctx->track.coop_parity ^= 1;
   }
   if (!write)
-    hipLaunchKernelGGL((k_sel_final_q<BINF>), dim3((unsigned)((n2 + 1535) / 1536)), dim3(256), 0, ctx->stream,
+    hipLaunchKernelGGL((k_sel_final_q<BINF>), dim3((unsigned)((w.n2 + 1535) / 1536)), dim3(256), 0, ctx->stream,
                        y + ioff, q + ioff, xk + ioff, sj + ioff, n - ioff, (const SelWs*)sws, delta, ioff);
   SPX_LAUNCH_CHECK();
   return SPX_OK;
 }
 
+// the kernel of a SelKernel (spx_plan.hpp); nullptr where the precision has none (the pipeline and the hybrid form: Float64)
+template <bool BINF, class T>
+const void* sel_kernel_fn(SelKernel k) {
+  if constexpr (std::is_same<T, double>::value) {
+    switch (k) {
+      case SelKernel::kLdsRegX: return reinterpret_cast<const void*>(&k_sel_lds<BINF, true, double, kLdsRegX>);
+      case SelKernel::kFront1: return reinterpret_cast<const void*>(&k_s2_front<1>);
+      case SelKernel::kFront2: return reinterpret_cast<const void*>(&k_s2_front<2>);
+      case SelKernel::kFront4: return reinterpret_cast<const void*>(&k_s2_front<4>);
+      case SelKernel::kFront16: return reinterpret_cast<const void*>(&k_s2_front<16>);
+      case SelKernel::kTail: return reinterpret_cast<const void*>(&k_s2_tail<BINF>);
+      default: break;
+    }
+  }
+  switch (k) {
+    case SelKernel::kCoopReg: return reinterpret_cast<const void*>(&k_sel_coop<BINF, true, T>);
+    case SelKernel::kCoopMem: return reinterpret_cast<const void*>(&k_sel_coop<BINF, false, T>);
+    case SelKernel::kLdsVec: return reinterpret_cast<const void*>(&k_sel_lds<BINF, true, T>);
+    case SelKernel::kLdsScalar: return reinterpret_cast<const void*>(&k_sel_lds<BINF, false, T>);
+    default: return nullptr;
+  }
+}
+
+// Three forms, by size: which one, on which grid, is sel_plan's (spx_plan.hpp), from the alignment of the vectors, the tuning
+// keys and the residency of the kernels it asks about.
 template <bool BINF, class T>
 int run_select(spx_ctx* ctx, T* y, const T* q, const T* xk, const T* sj, int64_t n, int64_t r, T delta) {
   int rc = spx_check_common(ctx, y, q, xk, sj, n);
   if (rc) return rc;
   if (n == 0) return SPX_OK;
   SPX_ON_DEVICE(ctx);
-  // one workgroup, one launch, no scratch -- up to 8192 elements (n = 16 384: 32 us in one workgroup, 21 us on two;
-  // n = 65 536: 84 vs 19 us -- tools/r2/topr_small.py)
-  if (n <= kSmallNCoop && ctx->tune_sel_small) {
-    hipLaunchKernelGGL((k_sel_small<BINF, T>), dim3(1), dim3(1024), 0, ctx->stream, y, q, xk, sj, n, r, delta);
-    SPX_LAUNCH_CHECK();
-    return SPX_OK;
-  }
-  const bool vec = spx_aligned16(y) && spx_aligned16(q) && spx_aligned16(xk) && spx_aligned16(sj);
-  // Residency of the kernels that synchronise inside one launch: a grid never exceeds what the occupancy query says can be
-  // resident at once (spx_resident_cap); a form whose grid does not fit hands over to the one that works with any grid.
-  const int64_t cap_reg = spx_resident_cap(ctx, reinterpret_cast<const void*>(&k_sel_coop<BINF, true, T>), 1024, 0);
-  const int64_t cap_mem = spx_resident_cap(ctx, reinterpret_cast<const void*>(&k_sel_coop<BINF, false, T>), 1024, 0);
-  if (cap_mem < 1) return SPX_ERR_INTERNAL;  // (message set by spx_resident_cap)
-  const int64_t reg_cap = (int64_t)kCoopEpl * 1024 * (cap_reg < ctx->num_cu ? cap_reg : ctx->num_cu);  // (2 Mi elements on 256 CUs)
-  // ... and with v parked in LDS (k_sel_lds: 16 Ki Float64 / 32 Ki Float32 elements per resident workgroup, 4 Mi / 8 Mi on 256
-  // CUs).  y must not overlap the inputs elsewhere than element for element (a lane reads all its inputs before it writes:
-  // aliasing q, xk or sj exactly is fine, as in the other one-launch forms).
-  constexpr int kLdsSlots = std::is_same<T, double>::value ? kLdsEpl : kLdsEpl32;
-  int64_t lds_cap = 0;
-  if (ctx->tune_sel_reg16) {
-    const int64_t capl = vec ? spx_resident_cap(ctx, reinterpret_cast<const void*>(&k_sel_lds<BINF, true, T>), 1024, 0)
-                             : spx_resident_cap(ctx, reinterpret_cast<const void*>(&k_sel_lds<BINF, false, T>), 1024, 0);
-    lds_cap = (int64_t)kLdsSlots * 1024 * (capl < ctx->num_cu ? capl : ctx->num_cu);
-  }
-  const int64_t g_mem = cap_mem < ctx->num_cu ? cap_mem : ctx->num_cu;  // grid of the form that parks v in y: any size >= 1 works
-  // (k_sel_lds: every CU the grid may have -- the load phase is most of the kernel and wants all of them pulling; a rendezvous
-  //  costs 1.4 us with 256 workgroups since the arrivals are spread over eight counters)
-  const int64_t g_lds = lds_cap / ((int64_t)kLdsSlots * 1024);
-  SelForm form;
-  int64_t g;
-  if constexpr (std::is_same<T, float>::value) {
-    // Float32: k_sel_lds above what the register form holds (2 Mi; below, registers win: n = 2e6 39 / 41 us against 43 / 45 --
-    // the Float32 first digit is not folded and the LDS form's third pass costs more), 8 elements per lane in registers;
-    // beyond what the grid holds: the form that parks v in y (n = 8e6: 97 -> 64 us, tools/r3/topr_f32_midn.py).  The
-    // sample-predicted single pass is Float64 only (~44 B/element here instead of 16, 0.7 ms at n = 1e8).
-    const bool lds = n <= lds_cap && n > reg_cap;
-    const bool reg = !lds && n <= reg_cap;
-    form = lds ? SelForm::kLds : reg ? SelForm::kCoopReg : SelForm::kCoopMem;
-    g = lds ? g_lds : reg ? (n + (int64_t)kCoopEpl * 1024 - 1) / ((int64_t)kCoopEpl * 1024) : g_mem;
-  } else {
-    // Float64: the sample-predicted pipeline above what the one-launch forms hold, k_sel_lds from 1 Mi elements on, the
-    // hybrid LDS + register form up to 6 Mi, elements per lane graded by n on the register form.
-    // all four vectors 8 bytes off a 16-byte boundary (a view that starts at an odd element): the sample-predicted path
-    // runs on the aligned rest and its wave 0 takes element 0 along (ioff = 1)
-    auto off8 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 8u; };
-    const int ioff = (!vec && off8(y) && off8(q) && off8(xk) && off8(sj)) ? 1 : 0;
-    // samples per lane of the front kernel: 1 / 2 / 4 by n (see k_s2_front); 16 for a cut in the bulk of a large vector -- the band
-    // is +-6 sigma of the SAMPLE rank, sigma^2 = M p (1 - p): its share of the vector shrinks with sqrt(M), and at r = n/2 the band
-    // of the 4-sample form holds 1.2 % of the vector as candidates (main pass +40 us, compaction +20 us; tuning key 10 overrides)
-    const double pcut = (double)r / (double)n;
-    int spl = n >= ((int64_t)1 << 25) ? 4 : (n >= ((int64_t)1 << 23) ? 2 : 1);
-    if (n >= ((int64_t)1 << 26) && pcut * (1.0 - pcut) > 0.04) spl = 16;
-    if (ctx->tune_front_spl == 1 || ctx->tune_front_spl == 2 || ctx->tune_front_spl == 4 || ctx->tune_front_spl == 16) spl = ctx->tune_front_spl;
-    const void* front_fn = spl == 16 ? reinterpret_cast<const void*>(&k_s2_front<16>)
-                         : spl == 4 ? reinterpret_cast<const void*>(&k_s2_front<4>)
-                         : spl == 2 ? reinterpret_cast<const void*>(&k_s2_front<2>)
-                                    : reinterpret_cast<const void*>(&k_s2_front<1>);
-    const int64_t cap_front = spx_resident_cap(ctx, front_fn, 1024, 0);
-    // ... and 6 Mi with 8 more elements per lane in registers (k_sel_lds<.., REGX>: 16-byte aligned vectors only; tuning key 11 = 2
-    // keeps the pipeline from 4 Mi on).  The sample-predicted pipeline (six launches, ~50 us of them fixed cost) takes over above
-    // what the resident grid holds on chip.
-    int64_t hyb_cap = 0;
-    if (ctx->tune_sel_reg16 == 1 && vec && lds_cap > 0) {
-      const int64_t caph = spx_resident_cap(ctx, reinterpret_cast<const void*>(&k_sel_lds<BINF, true, double, kLdsRegX>), 1024, 0);
-      hyb_cap = (int64_t)(kLdsEpl + kLdsRegX) * 1024 * (caph < ctx->num_cu ? caph : ctx->num_cu);
-      if (hyb_cap > 0x7fffffff) hyb_cap = 0;  // (the form indexes with 32-bit integers)
-    }
-    int64_t fast_min = ((int64_t)1 << SPX_SEL_REG_MAX_LOG2) + 1;
-    if (lds_cap >= fast_min) fast_min = lds_cap + 1;
-    if (hyb_cap >= fast_min) fast_min = hyb_cap + 1;
-    const bool try_fast = ctx->tune_sel_fast && (vec || ioff) && (n - ioff) >= fast_min && r > 0 && r < n &&
-                          cap_front >= kFrontBlocks;  // (the front kernel's sample layout is tied to its grid)
-    if (try_fast) return run_select_fast<BINF>(ctx, y, q, xk, sj, n, r, delta, ioff, spl);
-    // exact select in ONE launch: register-resident up to 8 Ki elements per resident workgroup, v parked in y beyond that
-    // k_sel_lds from 1 Mi elements on (n = 2e6: 34 / 42 us at r = n/100 / n/2 against 39 / 45 with v in registers; n = 1e6:
-    // 36 / 30 against 35 / 29 -- tools/r3/topr_small_grid.py), and wherever the register form's grid does not fit
-    const bool lds = n <= lds_cap && (n > kLdsMinN || n > reg_cap);
-    const bool hyb = !lds && n > lds_cap && n <= hyb_cap;  // (vec: hyb_cap is 0 otherwise)
-    const bool reg = !lds && !hyb && n <= reg_cap;
-    // Register form: 1 / 2 / 4 / 8 elements per lane by n -- the fewer elements a lane walks per pass the better, until the
-    // workgroups are so many that their histogram flushes and arrivals cost more (us per call at r = n/100, 1 / 2 / 4 / 8 per
-    // lane: n = 3e4 17.4 / 18.4 / 20.7 / 24.1; n = 1e5 19.8 / 19.3 / 20.8 / 24.4; n = 3e5 26.8 / 22.8 / 22.1 / 24.9; n = 1e6
-    // 35.6 / 35.7 / 36.6 / 34.7 -- tools/r3/topr_small_grid.py)
-    const int64_t epl = n <= 65536 ? 1 : n <= 196608 ? 2 : n <= 655360 ? 4 : kCoopEpl;
-    form = lds ? SelForm::kLds : hyb ? SelForm::kLdsRegX : reg ? SelForm::kCoopReg : SelForm::kCoopMem;
-    g = g_mem;
-    if (reg) {
-      const int64_t gmax = cap_reg < ctx->num_cu ? cap_reg : ctx->num_cu;
-      g = (n + epl * 1024 - 1) / (epl * 1024);
-      if (g > gmax) g = gmax;  // (n <= reg_cap: 8 elements per lane always fit)
-    }
-    if (lds) g = g_lds;
-    if (hyb) g = hyb_cap / ((int64_t)(kLdsEpl + kLdsRegX) * 1024);
+  auto off8 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 8u; };
+  SelIn in{};
+  in.f64 = std::is_same<T, double>::value;
+  in.n = n;
+  in.r = r;
+  in.vec = spx_aligned16(y) && spx_aligned16(q) && spx_aligned16(xk) && spx_aligned16(sj);
+  in.all_off8 = off8(y) && off8(q) && off8(xk) && off8(sj);
+  in.num_cu = ctx->num_cu;
+  in.sel_fast = ctx->tune_sel_fast;
+  in.sel_small = ctx->tune_sel_small;
+  in.front_spl = ctx->tune_front_spl;
+  in.sel_reg16 = ctx->tune_sel_reg16;
 #ifdef SPX_TEST_HOOKS  // the planted fault of tests/test_gpu_robustness.py: a grid that cannot be resident
-    if (!reg && !lds && !hyb && ctx->tune_force_grid > 0) g = ctx->tune_force_grid;
+  in.force_grid = ctx->tune_force_grid;
 #endif
+  const SelPlan plan = sel_plan(in, [&](SelKernel k) { return spx_resident_cap(ctx, sel_kernel_fn<BINF, T>(k), 1024, 0); });
+  switch (plan.route) {
+    case SelRoute::kSmall:
+      hipLaunchKernelGGL((k_sel_small<BINF, T>), dim3(1), dim3(1024), 0, ctx->stream, y, q, xk, sj, n, r, delta);
+      SPX_LAUNCH_CHECK();
+      return SPX_OK;
+    case SelRoute::kExact: return launch_sel_exact<BINF>(ctx, plan.form, plan.vec, plan.g, y, q, xk, sj, n, r, delta);
+    case SelRoute::kFast:
+      if constexpr (std::is_same<T, double>::value) return run_select_fast<BINF>(ctx, y, q, xk, sj, n, r, delta, plan);
+      break;
+    case SelRoute::kError: break;  // (message set by spx_resident_cap)
   }
-  return launch_sel_exact<BINF>(ctx, form, vec, g, y, q, xk, sj, n, r, delta);
+  return SPX_ERR_INTERNAL;
 }
 
 }  // namespace
