@@ -255,6 +255,56 @@ function prox_step!(y::DVec, ψ::ShiftedNormL1{Float64, <:DVec, <:DVec, <:DVec},
 end
 
 # ---------------------------------------------------------------------------------------------
+# The same for `batch` problems in ONE call, every per-problem scalar read from DEVICE memory (spx_proxstep_{l1,l0}[_box]_batch;
+# no counterpart in the reference): a regularisation path, folds, multi-start, one trust region per problem.  Problem b is
+# column b of the n × batch device matrices Y, Q, XK, SJ (and xkn): Julia's column-major layout with leading dimension
+# ld = stride(Y, 2) >= n is the library's row layout.  λ, σ, q_scale (and l, u: one scalar per problem, l = -Δ, u = Δ for a
+# trust region) are ROCVector{Float64} of length batch: the kernel reads them, nothing is read back, and a captured call
+# follows the values a solver leaves there (R2's ν update stays on the device).  `selected`: ONE byte mask of length n shared
+# by the problems, or nothing.  out: a 3 × batch device matrix; out[:, b] = (h, qy, yy) of problem b as prox_step! returns
+# them.  kind = :l1 or :l0; the box form is taken when l and u are given.  Returns (Y, out); never synchronises.
+# ---------------------------------------------------------------------------------------------
+const DMat = ROCMatrix{Float64}
+const libspx_batch = get(ENV, "LIBSPX_BATCH", "libspx_batch.so")   # include/spx_batch.h: a library of its own, linked against libspx
+dptr(v::DMat) = Ptr{Cdouble}(UInt(pointer(v)))
+for kind in (:l1, :l0)   # (ccall wants its symbol as a literal: one method per operator)
+  plain, boxed = QuoteNode(Symbol(:spx_proxstep_, kind, :_batch)), QuoteNode(Symbol(:spx_proxstep_, kind, :_box_batch))
+  @eval proxstep_batch_call(::Val{$(QuoteNode(kind))}, Y, Q, XK, SJ, n, batch, ld, λ, σ, q_scale, xkn, out) =
+    ccall(($plain, libspx_batch), Cint,
+          (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int64, Int64, Int64,
+           Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+          ctx(), dptr(Y), dptr(Q), dptr(XK), dptr(SJ), n, batch, ld, dptr(λ), dptr(σ), dptr(q_scale), dptr(xkn), dptr(out))
+  @eval proxstep_batch_call(::Val{$(QuoteNode(kind))}, Y, Q, XK, SJ, n, batch, ld, λ, σ, l, u, selected, q_scale, xkn, out) =
+    ccall(($boxed, libspx_batch), Cint,
+          (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int64, Int64, Int64,
+           Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{UInt8}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+          ctx(), dptr(Y), dptr(Q), dptr(XK), dptr(SJ), n, batch, ld, dptr(λ), dptr(σ), dptr(l), dptr(u), mptr(selected),
+          dptr(q_scale), dptr(xkn), dptr(out))
+end
+function prox_step_batch!(Y::DMat, kind::Symbol, Q::DMat, XK::DMat, SJ::DMat, λ::DVec, σ::DVec, q_scale::DVec;
+                          l::Union{Nothing, DVec} = nothing, u::Union{Nothing, DVec} = nothing,
+                          selected::Union{Nothing, ROCVector{UInt8}} = nothing, xkn::Union{Nothing, DMat} = nothing,
+                          out::DMat = ROCMatrix{Float64}(undef, 3, size(Y, 2)))
+  kind in (:l1, :l0) || throw(ArgumentError("kind is :l1 or :l0"))
+  n, batch = size(Y)
+  ld = batch > 1 ? stride(Y, 2) : max(n, 1)
+  for M in (Q, XK, SJ, xkn)
+    M === nothing && continue
+    (size(M) == (n, batch) && (batch <= 1 || stride(M, 2) == ld)) || throw(BoundsError())
+  end
+  (length(λ) == batch && length(σ) == batch && length(q_scale) == batch && size(out) == (3, batch)) || throw(BoundsError())
+  (l === nothing) == (u === nothing) || throw(ArgumentError("l and u are given together"))
+  if l === nothing
+    selected === nothing || throw(ArgumentError("selected needs the box form"))
+    check(proxstep_batch_call(Val(kind), Y, Q, XK, SJ, n, batch, ld, λ, σ, q_scale, xkn, out))
+  else
+    (length(l) == batch && length(u) == batch && (selected === nothing || length(selected) == n)) || throw(BoundsError())
+    check(proxstep_batch_call(Val(kind), Y, Q, XK, SJ, n, batch, ld, λ, σ, l, u, selected, q_scale, xkn, out))
+  end
+  return Y, out
+end
+
+# ---------------------------------------------------------------------------------------------
 # iprox! fused with the step statistics of a diagonal quasi-Newton iteration (spx_iproxstep_*; no counterpart in the
 # reference: what R2DH does around iprox! -- `ψ(s)`, `dot(∇fk, s)`, `dot(s, d .* s)`, `xk + s`, `norm(s)` -- in the pass that
 # stores s).  Returns (y, h, gy, ydy, yy):

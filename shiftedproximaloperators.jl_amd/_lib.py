@@ -104,6 +104,15 @@ SIGNATURES = {
 SIGNATURES.update({"spx_host_" + k[4:]: list(v) for k, v in list(SIGNATURES.items())
                    if k.startswith(("spx_prox_", "spx_iprox_", "spx_obj_")) and not k.endswith("_f32")})
 
+# libspx_batch.so (include/spx_batch.h): the batched separable call, a library of its own that links against libspx.so
+BATCH_LIB_PATH = LIB_PATH[:-3] + "_batch.so"
+BATCH_SIGNATURES = {
+    "spx_proxstep_l1_batch": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p],
+    "spx_proxstep_l0_batch": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p],
+    "spx_proxstep_l1_box_batch": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p],
+    "spx_proxstep_l0_box_batch": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p],
+}
+
 
 class SpxError(RuntimeError):
     """A libspx call returned a non-zero spx_status."""
@@ -131,6 +140,26 @@ def load():
             fn.restype = ctypes.c_char_p if name == "spx_last_error" else _int
         _lib = L
     return _lib
+
+
+_batch = None
+
+
+def load_batch():
+    """Load libspx_batch.so (after libspx.so, whose contexts and error text it shares).  Raises if it is missing."""
+    global _batch
+    if _batch is None:
+        load()
+        if not os.path.exists(BATCH_LIB_PATH):
+            raise ImportError("libspx_batch.so not found at %s -- build it with shiftedproximaloperators.jl_amd/csrc/build.sh; "
+                              "there is no CPU fallback" % BATCH_LIB_PATH)
+        L = ctypes.CDLL(BATCH_LIB_PATH)
+        for name, args in BATCH_SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.argtypes = args
+            fn.restype = _int
+        _batch = L
+    return _batch
 
 
 def check(status):

@@ -2,6 +2,8 @@
 # Builds libspx.so (HIP, gfx950 only) next to the package: shiftedproximaloperators.jl_amd/lib/libspx.so
 # -ffp-contract=off: the reference (Julia) never fuses a*b+c; several kernels decide branches on such sums.
 # One object per source file, compiled in parallel (no cross-file device calls, so no -fgpu-rdc), then one link.
+# spx_batch.hip (the batched separable call, include/spx_batch.h) becomes a library of its own, lib/libspx_batch.so -- for
+# SPX_LIB_NAME=X.so: X_batch.so -- linked against the first one (found next to it: rpath $ORIGIN).
 set -euo pipefail
 HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 ROOT="$(cd "$HERE/../.." && pwd)"
@@ -20,9 +22,15 @@ for s in "${SRCS[@]}"; do
   pids+=($!)
   objs+=("$OBJ/$s.o")
 done
+"$HIPCC" "${FLAGS[@]}" -c "$HERE/spx_batch.hip" -o "$OBJ/spx_batch.o" &
+pids+=($!)
 fail=0
 for p in "${pids[@]}"; do wait "$p" || fail=1; done
 [ "$fail" = 0 ] || { echo "compile failed" >&2; exit 1; }
 "$HIPCC" --offload-arch=gfx950 -shared -fPIC -fvisibility=hidden "${objs[@]}" -o "$OUT/$NAME.tmp"
 mv -f "$OUT/$NAME.tmp" "$OUT/$NAME"
+BATCH="${NAME%.so}_batch.so"
+"$HIPCC" --offload-arch=gfx950 -shared -fPIC -fvisibility=hidden "$OBJ/spx_batch.o" -L"$OUT" -l:"$NAME" '-Wl,-rpath,$ORIGIN' \
+  -o "$OUT/$BATCH.tmp"
+mv -f "$OUT/$BATCH.tmp" "$OUT/$BATCH"
 echo "built $OUT/$NAME"

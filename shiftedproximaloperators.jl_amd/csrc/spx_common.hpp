@@ -104,8 +104,16 @@ struct spx_ctx {
 constexpr int kSpxStatusTimeout = 1;    // an in-launch synchronised kernel gave up waiting for its own workgroups
 constexpr int kSpxStatusCorrupt = 2;    // library-owned device state outside its layout (deferred-group list)
 
-void spx_set_error(const char* fmt, ...);
-int spx_ws_reserve(spx_ctx* ctx, size_t bytes);
+// (SPX_SHARED: also called from libspx_batch.so, which links against this library: csrc/spx_batch.hip.  What the two share --
+//  the layout of spx_ctx and these signatures -- is stamped: kSpxSharedAbi is compiled into both, libspx.so answers with its own
+//  through spx_shared_abi(), and the batched entry points refuse a library that answers otherwise.  Raise the version whenever
+//  spx_ctx or one of the SPX_SHARED functions changes.)
+#define SPX_SHARED __attribute__((visibility("default")))
+constexpr int kSpxSharedVersion = 1;
+constexpr int kSpxSharedAbi = kSpxSharedVersion * 65536 + (int)sizeof(spx_ctx);
+SPX_SHARED int spx_shared_abi();
+SPX_SHARED void spx_set_error(const char* fmt, ...);
+SPX_SHARED int spx_ws_reserve(spx_ctx* ctx, size_t bytes);
 // spx_ctx::sync is there unless the context was created while its stream was being captured: then the first call that needs
 // it allocates it outside a capture and refuses inside one (SPX_ERR_INVALID_ARG, before anything is enqueued)
 int spx_sync_alloc(spx_ctx* ctx);
@@ -117,13 +125,13 @@ int spx_ctx_count(int device);                     // live contexts on a device
 // a workgroup must never wait for one that cannot be placed.  0 with an error set if the kernel cannot run at all.
 int64_t spx_resident_cap(spx_ctx* ctx, const void* fn, int block_threads, size_t dyn_lds);
 int spx_blocks_per_cu(spx_ctx* ctx, const void* fn, int block_threads, size_t dyn_lds);  // workgroups a CU holds at once; -1: error
-int spx_status_report(spx_ctx* ctx);               // SPX_ERR_INTERNAL + message for a non-zero device status word
+SPX_SHARED int spx_status_report(spx_ctx* ctx);    // SPX_ERR_INTERNAL + message for a non-zero device status word
 // Is ctx's stream being captured into a graph?  Sets spx_ctx::graph_safe (sticky) when it is.  Calls that would have to
 // synchronise the stream or (re)allocate refuse to run while capturing (SPX_ERR_INVALID_ARG, spx_require_not_capturing).
 // Zero-fill on the context's stream by a KERNEL (4-byte words): used instead of hipMemsetAsync / hipMemset2DAsync wherever
 // a call may be captured into a graph -- a captured iteration replayed through torch.cuda.CUDAGraph faulted in a way that
 // implicated the runtime's memset nodes (round 2; plain kernel nodes replay fine).  bytes, pitch, width: multiples of 4.
-int spx_zero_async(spx_ctx* ctx, void* ptr, size_t bytes);
+SPX_SHARED int spx_zero_async(spx_ctx* ctx, void* ptr, size_t bytes);
 int spx_zero2d_async(spx_ctx* ctx, void* ptr, size_t pitch_bytes, size_t width_bytes, size_t rows);
 bool spx_capture_check(spx_ctx* ctx);
 int spx_require_not_capturing(spx_ctx* ctx, const char* what);

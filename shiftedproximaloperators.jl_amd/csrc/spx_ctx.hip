@@ -300,6 +300,7 @@ int spx_zero2d_async(spx_ctx* ctx, void* ptr, size_t pitch_bytes, size_t width_b
   return SPX_OK;
 }
 int spx_zero_async(spx_ctx* ctx, void* ptr, size_t bytes) { return spx_zero2d_async(ctx, ptr, bytes, bytes, 1); }
+int spx_shared_abi() { return kSpxSharedAbi; }  // (what this library was built with: spx_common.hpp)
 
 bool spx_capture_check(spx_ctx* ctx) {
   hipStreamCaptureStatus st = hipStreamCaptureStatusNone;

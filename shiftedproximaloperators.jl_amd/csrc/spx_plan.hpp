@@ -1,6 +1,6 @@
 // spx_plan.hpp -- WHICH kernel runs, on WHICH grid, with WHICH workspace: the decisions of the calls whose kernels synchronise
-// inside one launch (top-r: spx_select.hip; ShiftedNormL1B2: spx_b2.hip; large groups on teams: spx_group_team.hip), as plain
-// functions of plain values.  No HIP include, no runtime call, no kernel, no spx_ctx: what a call would do at a given n,
+// inside one launch (top-r: spx_select.hip; ShiftedNormL1B2: spx_b2.hip; large groups on teams: spx_group_team.hip) and of the
+// batched separable call (spx_batch.hip), as plain functions of plain values.  No HIP include, no runtime call, no kernel, no spx_ctx: what a call would do at a given n,
 // alignment, residency and tuning is computable -- and testable, tests/c/plan_driver.hip -- on a CPU.
 //
 // Residency comes in through `cap`: cap(kernel) returns what spx_resident_cap returns for that kernel (0 = it cannot run; the
@@ -318,4 +318,75 @@ inline int team_layout(int64_t cap, int team_fast, bool binf, int64_t n, bool ha
     L->cand_bytes = (size_t)L->grid * (kTmThreads / 64) * (size_t)c * cand_elem_bytes;
   }
   return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// batched separable prox! + step statistics (spx_proxstep_*_batch, spx_batch.hip): `batch` problems of n elements, problem
+// b at elements [b * ld, b * ld + n) of every vector.  The functions the kernels walk a row with are the ones below, so the
+// mapping (workgroup -> problem, tile, head, pairs, tail) is what tests/c/batch_plan_driver.hip enumerates on a CPU.
+// ---------------------------------------------------------------------------------------------
+#if defined(__HIPCC__)
+#define SPX_PLAN_HD __host__ __device__
+#else
+#define SPX_PLAN_HD
+#endif
+constexpr int kBatchTile = 3072;            // elements of a row per tile: 256 lanes x 6 pairs (element-wise: x 12 elements)
+constexpr int64_t kBatchRowMax = 4 * (int64_t)kBatchTile;  // one workgroup owns a whole problem up to here (12288); beyond: one tile per workgroup
+constexpr int kBatchVectors = 5;            // y, q, xk, sj, xkn: one bit each in base_alignment_bits
+constexpr int kBatchAllOff = (1 << kBatchVectors) - 1;
+constexpr int64_t kBatchGridMax = 0x7fffffff;
+
+enum class BatchForm { kRow, kTiled };
+struct BatchPlan {
+  bool ok;          // false: the call needs more than kBatchGridMax workgroups (refused)
+  BatchForm form;   // a function of n alone: a problem's bits do not depend on its neighbours
+  bool pairs;       // 16-byte accesses with per-row peeling; false: element-wise
+  int base_odd;     // pairs: the bases sit 8 bytes off a 16-byte boundary
+  int64_t grid;     // workgroups of the launch that stores y
+  int64_t tiles_per_problem;
+  size_t ws_bytes;  // tiled form: three planes of partials per problem, laid out [problem][plane][tile]
+};
+// A row in the pairs form: `head` (0 or 1) scalar elements up to the row's first 16-byte boundary, npairs pairs, `tail` (0 or 1)
+// scalar elements.  Element-wise form: n units of one element, no head, no tail.
+struct BatchRowMap { int head; int64_t npairs; int tail; };
+SPX_PLAN_HD inline BatchRowMap batch_row_map(int64_t n, int64_t b, int64_t ld, int base_odd) {
+  BatchRowMap m;
+  m.head = (int)((b * ld + base_odd) & 1);
+  if (m.head > n) m.head = (int)n;
+  m.npairs = (n - m.head) >> 1;
+  m.tail = (int)(n - m.head - 2 * m.npairs);
+  return m;
+}
+SPX_PLAN_HD inline int64_t batch_tiles(int64_t n) { return (n + kBatchTile - 1) / kBatchTile; }
+// the units (pairs, or elements in the element-wise form) [*lo, *hi) of `count` that tile `tile` owns, units_per_tile a time
+SPX_PLAN_HD inline void batch_tile_units(int64_t count, int64_t tile, int units_per_tile, int64_t* lo, int64_t* hi) {
+  const int64_t a = tile * units_per_tile;
+  const int64_t e = a + units_per_tile;
+  *lo = a < count ? a : count;
+  *hi = e < count ? e : count;
+}
+// workgroup -> (problem, tile) of the tiled form, and the slot of its partial sum `plane` in the workspace
+SPX_PLAN_HD inline void batch_workgroup(int64_t wg, int64_t tiles, int64_t* problem, int64_t* tile) {
+  *problem = wg / tiles;
+  *tile = wg - *problem * tiles;
+}
+SPX_PLAN_HD inline int64_t batch_slot(int64_t problem, int plane, int64_t tile, int64_t tiles) { return (problem * 3 + plane) * tiles + tile; }
+
+// base_alignment_bits: bit k set = vector k (y, q, xk, sj, xkn; an absent xkn counts as y) starts 8 bytes off a 16-byte boundary
+inline BatchPlan batch_plan(int64_t n, int64_t batch, int64_t ld, int base_alignment_bits) {
+  (void)ld;  // (the rows' parities come from ld in batch_row_map; the launch shape does not depend on it)
+  BatchPlan p{};
+  p.form = n <= kBatchRowMax ? BatchForm::kRow : BatchForm::kTiled;
+  p.pairs = base_alignment_bits == 0 || base_alignment_bits == kBatchAllOff;
+  p.base_odd = (p.pairs && base_alignment_bits != 0) ? 1 : 0;
+  p.tiles_per_problem = batch_tiles(n);
+  if (p.form == BatchForm::kRow) {
+    p.grid = batch;
+  } else {
+    if (batch > kBatchGridMax / p.tiles_per_problem) return p;  // (no overflow: tiles_per_problem >= 5 here)
+    p.grid = batch * p.tiles_per_problem;
+    p.ws_bytes = (size_t)batch * 3 * (size_t)p.tiles_per_problem * sizeof(double);
+  }
+  p.ok = p.grid <= kBatchGridMax;
+  return p;
 }

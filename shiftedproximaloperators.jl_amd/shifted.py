@@ -885,6 +885,97 @@ def prox_step(ψ, q, σ, q_scale=1.0, xkn=None, out=None):
     return prox_step_bang(ψ.sol, ψ, q, σ, q_scale, xkn, out)
 
 
+def _batch_matrix(t, name, like=None):
+    """a 2-D float64 device tensor with unit inner stride (a problem per row); `like`: same shape, row stride and device"""
+    if not (type(t) is _Tensor and t.is_cuda and t.dtype == torch.float64 and t.dim() == 2):
+        raise TypeError("%s must be a 2-D float64 device tensor (batch x n)" % name)
+    if t.shape[1] > 1 and t.stride(1) != 1:
+        raise TypeError("%s must have unit inner stride" % name)
+    if like is not None:
+        if t.shape != like.shape or t.device != like.device:
+            raise IndexError("BoundsError: %s is %s on %s, expected %s on %s" % (name, tuple(t.shape), t.device, tuple(like.shape), like.device))
+        if t.shape[0] > 1 and t.stride(0) != like.stride(0):
+            raise TypeError("%s must share the row stride of Y (%d, got %d)" % (name, like.stride(0), t.stride(0)))
+    return t
+
+
+def _batch_params(t, name, batch, like):
+    if not (type(t) is _Tensor and t.is_cuda and t.dtype == torch.float64 and t.dim() == 1 and t.numel() == batch
+            and (batch <= 1 or t.stride(0) == 1) and t.device == like.device):
+        raise TypeError("%s must be a contiguous 1-D float64 device tensor with one entry per problem (%d) on Y's device" % (name, batch))
+    return t
+
+
+def prox_step_batch_bang(Y, kind, Q, XK, SJ, lam, sigma, q_scale, l=None, u=None, selected=None, xkn=None, out=None):
+    """prox_step_bang for `batch` problems in ONE library call (spx_proxstep_{l1,l0}[_box]_batch, libspx_batch.so), every per-problem scalar read
+    from DEVICE memory.  Row b of the batch × n tensors Y, Q, XK, SJ (and xkn) is one problem: Y[b] = prox!(ψ_b, q_scale[b] .* Q[b],
+    sigma[b]) with ψ_b = shifted(shifted(h, XK[b]), SJ[b]), h = NormL1(lam[b]) (kind = "l1") or NormL0(lam[b]) (kind = "l0"),
+    in the box [l[b], u[b]] when l and u are given (a trust region of radius Δ_b: l = -Δ, u = Δ), and
+
+        out[b, 0] = h  = lam[b] · Σ over the SELECTED indices of Term((XK[b] + SJ[b]) + Y[b])
+        out[b, 1] = qy = Σ over ALL i of Q[b, i] · Y[b, i]   -- with the UNSCALED Q as passed, not q_scale[b] · Q
+        out[b, 2] = yy = Σ over ALL i of Y[b, i]²
+        xkn[b, i] = (XK[b, i] + SJ[b, i]) + Y[b, i] for every i, selected or not (None: not stored)
+
+    The 2-D tensors are float64 device tensors with unit inner stride and a common row stride (the library's ld >= n; the
+    elements between the rows are never touched).  lam, sigma, q_scale, l, u: 1-D float64 device tensors with one entry per
+    problem -- the kernel reads them, so a loop (or a captured graph) that updates them on the device needs no host round trip.
+    selected: ONE selection shared by the problems (Box forms) -- a uint8 device mask of length n, used as it is, or 0-based
+    indices, from which a mask is built on every call (build the mask once for a loop or a capture).  out: a contiguous
+    batch × 3 float64 device tensor (None: allocated).  Returns (Y, out); nothing is read back and the stream is not
+    synchronised.  Y must not be Q; xkn must be none of the other tensors.  Y[b] and xkn[b] have the bits of prox_step_bang on
+    row b alone with the same scalars."""
+    if kind not in ("l1", "l0"):
+        raise TypeError('kind must be "l1" or "l0" (the batched call serves NormL1 / NormL0 and their Box forms)')
+    _batch_matrix(Y, "Y")
+    for t, name in ((Q, "Q"), (XK, "XK"), (SJ, "SJ")):
+        _batch_matrix(t, name, like=Y)
+    if xkn is not None:
+        _batch_matrix(xkn, "xkn", like=Y)
+    if Y is Q:
+        raise TypeError("prox_step_batch: Y must not be Q (qy is taken with the Q that was passed)")
+    batch, n = Y.shape
+    # (one row has no row stride to share: with batch == 1 the strides are not compared and the library gets ld = n)
+    ld = Y.stride(0) if batch > 1 else max(n, 1)
+    if ld < n:
+        raise TypeError("the rows of Y overlap (row stride %d < n = %d)" % (ld, n))
+    box = l is not None or u is not None
+    if box and (l is None or u is None):
+        raise TypeError("l and u are given together (one scalar per problem each)")
+    if selected is not None and not box:
+        raise TypeError("selected needs the box form (give l and u)")
+    for t, name in ((lam, "lam"), (sigma, "sigma"), (q_scale, "q_scale")) + (((l, "l"), (u, "u")) if box else ()):
+        _batch_params(t, name, batch, Y)
+    if out is None:
+        out = torch.empty((batch, 3), dtype=torch.float64, device=Y.device)
+    elif not (type(out) is _Tensor and out.is_cuda and out.dtype == torch.float64 and tuple(out.shape) == (batch, 3)
+              and out.is_contiguous() and out.device == Y.device):
+        raise TypeError("out must be a contiguous batch x 3 float64 device tensor on Y's device")
+    L = _lib.load_batch()
+    head = (_ctx(Y.device), _ptr(Y), _ptr(Q), _ptr(XK), _ptr(SJ), n, batch, ld, _ptr(lam), _ptr(sigma))
+    if not box:
+        _lib.check(getattr(L, "spx_proxstep_%s_batch" % kind)(*head, _ptr(q_scale), _ptr(xkn), _ptr(out)))
+        return Y, out
+    mask = None
+    if selected is not None:
+        if type(selected) is _Tensor and selected.dtype == torch.uint8:
+            if not (selected.is_cuda and selected.dim() == 1 and selected.numel() == n and (n <= 1 or selected.stride(0) == 1)
+                    and selected.device == Y.device):
+                raise TypeError("a selection mask must be a contiguous uint8 device tensor of length n on Y's device")
+            mask = selected
+        else:
+            built = _build_mask(selected, Y[0] if batch else Y.reshape(-1)[:n])
+            mask = built[0] if built is not None else None
+    _lib.check(getattr(L, "spx_proxstep_%s_box_batch" % kind)(*head, _ptr(l), _ptr(u), _ptr(mask), _ptr(q_scale), _ptr(xkn), _ptr(out)))
+    return Y, out
+
+
+def prox_step_batch(kind, Q, XK, SJ, lam, sigma, q_scale, l=None, u=None, selected=None, xkn=None, out=None):
+    """prox_step_batch_bang into a new Y shaped and strided like Q: (Y, out); see prox_step_batch_bang"""
+    return prox_step_batch_bang(torch.empty_strided(Q.shape, Q.stride(), dtype=Q.dtype, device=Q.device), kind, Q, XK, SJ, lam, sigma,
+                                q_scale, l, u, selected, xkn, out)
+
+
 def group_prox_step_bang(y, ψ, q, σ, q_scale=1.0, xkn=None, out=None):
     """prox_step_bang for the group operators, ShiftedGroupNormL2 and ShiftedGroupNormL2Binf (spx_proxstep_group_l2[_binf]):
     prox!(y, ψ, q_scale .* q, σ) and the step statistics of a trust-region iteration in one library call,
