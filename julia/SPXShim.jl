@@ -348,7 +348,62 @@ function iprox_step!(y::DVec, ψ::ShiftedNormL1{Float64, <:DVec, <:DVec, <:DVec}
 end
 
 # ---------------------------------------------------------------------------------------------
-# l1 norm + l2-ball trust region      src/shiftedNormL1B2.jl:50-67   (χ = NormL2(χ.lambda))
+# The same for `batch` problems in ONE call, every per-problem scalar read from DEVICE memory (spx_iproxstep_{l1,l0}[_box]_batch;
+# no counterpart in the reference): a path of R2DH problems in lock step.  Problem b is column b of the n × batch device
+# matrices Y, G, D, XK, SJ (and xkn), as for prox_step_batch!.  λ (and l, u: one scalar per problem) are ROCVector{Float64} of
+# length batch.  d_shift: a ROCVector{Float64} of length batch or nothing -- given, every element site sees D[i, b] + d_shift[b],
+# ONE rounded add formed on the fly, in place of D[i, b]: R2DH's D + σ_b needs no pass of its own and follows the σ_b a solver
+# leaves on the device; nothing: D enters as it is.  out: a 4 × batch device matrix; out[:, b] = (h, gy, ydy, yy) of problem b as
+# iprox_step! returns them (ydy with D + d_shift).  d_flag (unboxed kinds): a ROCVector{Int32} of length batch; after the call
+# d_flag[b] is 1 when some D[i, b] + d_shift[b] <= 0 or NaN occurred in problem b (the reference's `@assert d[i] > 0`, per problem,
+# not read back), else 0.  kind = :l1 or :l0; the box form is taken when l and u are given.  Returns (Y, out); never synchronises.
+# ---------------------------------------------------------------------------------------------
+const libspx_ibatch = get(ENV, "LIBSPX_IBATCH", "libspx_ibatch.so")   # include/spx_ibatch.h: a third library, linked against libspx
+i32ptr(v::ROCVector{Int32}) = Ptr{Int32}(UInt(pointer(v)))
+for kind in (:l1, :l0)   # (ccall wants its symbol as a literal: one method per operator)
+  plain, boxed = QuoteNode(Symbol(:spx_iproxstep_, kind, :_batch)), QuoteNode(Symbol(:spx_iproxstep_, kind, :_box_batch))
+  @eval iproxstep_batch_call(::Val{$(QuoteNode(kind))}, Y, G, D, XK, SJ, n, batch, ld, λ, d_shift, d_flag::ROCVector{Int32}, xkn, out) =
+    ccall(($plain, libspx_ibatch), Cint,
+          (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int64, Int64, Int64,
+           Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}, Ptr{Cdouble}, Ptr{Cdouble}),
+          ctx(), dptr(Y), dptr(G), dptr(D), dptr(XK), dptr(SJ), n, batch, ld, dptr(λ), dptr(d_shift), i32ptr(d_flag), dptr(xkn),
+          dptr(out))
+  @eval iproxstep_batch_call(::Val{$(QuoteNode(kind))}, Y, G, D, XK, SJ, n, batch, ld, λ, d_shift, l::DVec, u::DVec, selected, xkn, out) =
+    ccall(($boxed, libspx_ibatch), Cint,
+          (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int64, Int64, Int64,
+           Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{UInt8}, Ptr{Cdouble}, Ptr{Cdouble}),
+          ctx(), dptr(Y), dptr(G), dptr(D), dptr(XK), dptr(SJ), n, batch, ld, dptr(λ), dptr(d_shift), dptr(l), dptr(u),
+          mptr(selected), dptr(xkn), dptr(out))
+end
+function iprox_step_batch!(Y::DMat, kind::Symbol, G::DMat, D::DMat, XK::DMat, SJ::DMat, λ::DVec;
+                           d_shift::Union{Nothing, DVec} = nothing, l::Union{Nothing, DVec} = nothing,
+                           u::Union{Nothing, DVec} = nothing, selected::Union{Nothing, ROCVector{UInt8}} = nothing,
+                           xkn::Union{Nothing, DMat} = nothing, out::DMat = ROCMatrix{Float64}(undef, 4, size(Y, 2)),
+                           d_flag::Union{Nothing, ROCVector{Int32}} = nothing)
+  kind in (:l1, :l0) || throw(ArgumentError("kind is :l1 or :l0"))
+  n, batch = size(Y)
+  ld = batch > 1 ? stride(Y, 2) : max(n, 1)
+  for M in (G, D, XK, SJ, xkn)
+    M === nothing && continue
+    (size(M) == (n, batch) && (batch <= 1 || stride(M, 2) == ld)) || throw(BoundsError())
+  end
+  (length(λ) == batch && (d_shift === nothing || length(d_shift) == batch) && size(out) == (4, batch)) || throw(BoundsError())
+  (l === nothing) == (u === nothing) || throw(ArgumentError("l and u are given together"))
+  if l === nothing
+    selected === nothing || throw(ArgumentError("selected needs the box form"))
+    flag = d_flag === nothing ? ROCVector{Int32}(undef, max(batch, 1)) : d_flag
+    (d_flag === nothing || length(d_flag) == batch) || throw(BoundsError())
+    check(iproxstep_batch_call(Val(kind), Y, G, D, XK, SJ, n, batch, ld, λ, d_shift, flag, xkn, out))
+  else
+    d_flag === nothing || throw(ArgumentError("d_flag belongs to the unboxed kinds"))
+    (length(l) == batch && length(u) == batch && (selected === nothing || length(selected) == n)) || throw(BoundsError())
+    check(iproxstep_batch_call(Val(kind), Y, G, D, XK, SJ, n, batch, ld, λ, d_shift, l, u, selected, xkn, out))
+  end
+  return Y, out
+end
+
+# ---------------------------------------------------------------------------------------------
+# l1 norm + l2-ball trust region     src/shiftedNormL1B2.jl:50-67   (χ = NormL2(χ.lambda))
 # ---------------------------------------------------------------------------------------------
 function prox!(y::DVec, ψ::ShiftedProximalOperators.ShiftedNormL1B2{Float64, <:DVec, <:DVec, <:DVec}, q::DVec, σ::Float64)
   n = length(ψ.xk)

@@ -10,7 +10,8 @@ from .shifted import (ShiftedGroupNormL2, ShiftedGroupNormL2Binf, ShiftedIndBall
                       ShiftedNormL0, ShiftedNormL0Box, ShiftedNormL1, ShiftedNormL1B2, ShiftedNormL1Box,
                       ShiftedProximableFunction, ShiftedRootNormLhalf, ShiftedRootNormLhalfBox, b2_prox_step, b2_prox_step_bang,
                       context, device_values,
-                      group_prox_step, group_prox_step_bang, iprox, iprox_bang, iprox_step, iprox_step_bang, prox,
+                      group_prox_step, group_prox_step_bang, iprox, iprox_bang, iprox_step, iprox_step_bang,
+                      iprox_step_batch, iprox_step_batch_bang, prox,
                       prox_bang, prox_step, prox_step_bang, prox_step_batch, prox_step_batch_bang, prox_value, prox_value_bang, set_bounds_bang, set_radius_bang, shift_bang, shifted, synchronize, value)
 
 __all__ = [n for n in dir() if not n.startswith("_")]

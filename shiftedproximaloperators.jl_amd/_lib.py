@@ -113,6 +113,15 @@ BATCH_SIGNATURES = {
     "spx_proxstep_l0_box_batch": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p],
 }
 
+# libspx_ibatch.so (include/spx_ibatch.h): the batched iprox! call, a third library that links against libspx.so
+IBATCH_LIB_PATH = LIB_PATH[:-3] + "_ibatch.so"
+IBATCH_SIGNATURES = {
+    "spx_iproxstep_l1_batch": [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p],
+    "spx_iproxstep_l0_batch": [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p],
+    "spx_iproxstep_l1_box_batch": [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _p],
+    "spx_iproxstep_l0_box_batch": [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _p],
+}
+
 
 class SpxError(RuntimeError):
     """A libspx call returned a non-zero spx_status."""
@@ -160,6 +169,26 @@ def load_batch():
             fn.restype = _int
         _batch = L
     return _batch
+
+
+_ibatch = None
+
+
+def load_ibatch():
+    """Load libspx_ibatch.so (after libspx.so, whose contexts and error text it shares).  Raises if it is missing."""
+    global _ibatch
+    if _ibatch is None:
+        load()
+        if not os.path.exists(IBATCH_LIB_PATH):
+            raise ImportError("libspx_ibatch.so not found at %s -- build it with shiftedproximaloperators.jl_amd/csrc/build.sh; "
+                              "there is no CPU fallback" % IBATCH_LIB_PATH)
+        L = ctypes.CDLL(IBATCH_LIB_PATH)
+        for name, args in IBATCH_SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.argtypes = args
+            fn.restype = _int
+        _ibatch = L
+    return _ibatch
 
 
 def check(status):

@@ -3,7 +3,8 @@
 # -ffp-contract=off: the reference (Julia) never fuses a*b+c; several kernels decide branches on such sums.
 # One object per source file, compiled in parallel (no cross-file device calls, so no -fgpu-rdc), then one link.
 # spx_batch.hip (the batched separable call, include/spx_batch.h) becomes a library of its own, lib/libspx_batch.so -- for
-# SPX_LIB_NAME=X.so: X_batch.so -- linked against the first one (found next to it: rpath $ORIGIN).
+# SPX_LIB_NAME=X.so: X_batch.so -- linked against the first one (found next to it: rpath $ORIGIN).  spx_ibatch.hip (the batched
+# iprox! call, include/spx_ibatch.h) becomes a third one in the same way: lib/libspx_ibatch.so, X_ibatch.so.
 set -euo pipefail
 HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 ROOT="$(cd "$HERE/../.." && pwd)"
@@ -24,6 +25,8 @@ for s in "${SRCS[@]}"; do
 done
 "$HIPCC" "${FLAGS[@]}" -c "$HERE/spx_batch.hip" -o "$OBJ/spx_batch.o" &
 pids+=($!)
+"$HIPCC" "${FLAGS[@]}" -c "$HERE/spx_ibatch.hip" -o "$OBJ/spx_ibatch.o" &
+pids+=($!)
 fail=0
 for p in "${pids[@]}"; do wait "$p" || fail=1; done
 [ "$fail" = 0 ] || { echo "compile failed" >&2; exit 1; }
@@ -33,4 +36,8 @@ BATCH="${NAME%.so}_batch.so"
 "$HIPCC" --offload-arch=gfx950 -shared -fPIC -fvisibility=hidden "$OBJ/spx_batch.o" -L"$OUT" -l:"$NAME" '-Wl,-rpath,$ORIGIN' \
   -o "$OUT/$BATCH.tmp"
 mv -f "$OUT/$BATCH.tmp" "$OUT/$BATCH"
+IBATCH="${NAME%.so}_ibatch.so"
+"$HIPCC" --offload-arch=gfx950 -shared -fPIC -fvisibility=hidden "$OBJ/spx_ibatch.o" -L"$OUT" -l:"$NAME" '-Wl,-rpath,$ORIGIN' \
+  -o "$OUT/$IBATCH.tmp"
+mv -f "$OUT/$IBATCH.tmp" "$OUT/$IBATCH"
 echo "built $OUT/$NAME"

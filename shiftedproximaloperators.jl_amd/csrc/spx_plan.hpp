@@ -390,3 +390,34 @@ inline BatchPlan batch_plan(int64_t n, int64_t batch, int64_t ld, int base_align
   p.ok = p.grid <= kBatchGridMax;
   return p;
 }
+
+// ---------------------------------------------------------------------------------------------
+// batched iprox! + step statistics (spx_iproxstep_*_batch, spx_ibatch.hip): the layout of the batched prox! above with six
+// vectors (y, g, d, xk, sj, xkn) and four sums.  The rows, tiles and workgroups are mapped by the functions above, unchanged;
+// only the alignment bits and the planes of the partials differ.  tests/c/ibatch_plan_driver.hip enumerates it on a CPU.
+// ---------------------------------------------------------------------------------------------
+constexpr int kIbatchVectors = 6;           // y, g, d, xk, sj, xkn: one bit each in base_alignment_bits
+constexpr int kIbatchAllOff = (1 << kIbatchVectors) - 1;
+constexpr int kIbatchPlanes = 4;            // h terms, <g, y>, <d .* y, y>, <y, y>
+SPX_PLAN_HD inline int64_t ibatch_slot(int64_t problem, int plane, int64_t tile, int64_t tiles) {
+  return (problem * kIbatchPlanes + plane) * tiles + tile;
+}
+// base_alignment_bits: bit k set = vector k (y, g, d, xk, sj, xkn; an absent xkn counts as y) starts 8 bytes off a 16-byte
+// boundary.  The result is a BatchPlan: ws_bytes holds four planes of partials per problem, [problem][plane][tile].
+inline BatchPlan ibatch_plan(int64_t n, int64_t batch, int64_t ld, int base_alignment_bits) {
+  (void)ld;
+  BatchPlan p{};
+  p.form = n <= kBatchRowMax ? BatchForm::kRow : BatchForm::kTiled;
+  p.pairs = base_alignment_bits == 0 || base_alignment_bits == kIbatchAllOff;
+  p.base_odd = (p.pairs && base_alignment_bits != 0) ? 1 : 0;
+  p.tiles_per_problem = batch_tiles(n);
+  if (p.form == BatchForm::kRow) {
+    p.grid = batch;
+  } else {
+    if (batch > kBatchGridMax / p.tiles_per_problem) return p;  // (no overflow: tiles_per_problem >= 5 here)
+    p.grid = batch * p.tiles_per_problem;
+    p.ws_bytes = (size_t)batch * kIbatchPlanes * (size_t)p.tiles_per_problem * sizeof(double);
+  }
+  p.ok = p.grid <= kBatchGridMax;
+  return p;
+}

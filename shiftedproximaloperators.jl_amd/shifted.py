@@ -1127,6 +1127,89 @@ def iprox_step(ψ, g, d, check=False, xkn=None, out=None):
     return iprox_step_bang(ψ.sol, ψ, g, d, check, xkn, out)
 
 
+def iprox_step_batch_bang(Y, kind, G, D, XK, SJ, lam, d_shift=None, l=None, u=None, selected=None, xkn=None, out=None, d_flag=None):
+    """iprox_step_bang for `batch` problems in ONE library call (spx_iproxstep_{l1,l0}[_box]_batch, libspx_ibatch.so), every
+    per-problem scalar read from DEVICE memory.  Row b of the batch × n tensors Y, G, D, XK, SJ (and xkn) is one problem:
+    Y[b] = iprox!(ψ_b, G[b], D[b] .+ d_shift[b]) with ψ_b = shifted(shifted(h, XK[b]), SJ[b]), h = NormL1(lam[b]) (kind = "l1")
+    or NormL0(lam[b]) (kind = "l0"), in the box [l[b], u[b]] when l and u are given, and with deff = D[b, i] + d_shift[b]
+
+        out[b, 0] = h   = lam[b] · Σ over the SELECTED indices of Term((XK[b] + SJ[b]) + Y[b])
+        out[b, 1] = gy  = Σ over ALL i of G[b, i] · Y[b, i]
+        out[b, 2] = ydy = Σ over ALL i of (deff · Y[b, i]) · Y[b, i]   -- in that association; the model is gy + ydy / 2
+        out[b, 3] = yy  = Σ over ALL i of Y[b, i]²
+        xkn[b, i] = (XK[b, i] + SJ[b, i]) + Y[b, i] for every i, selected or not (None: not stored)
+
+    d_shift: a 1-D float64 device tensor with one entry per problem, or None.  Given, every element site sees
+    D[b, i] + d_shift[b] -- ONE rounded add formed on the fly -- in place of D[b, i]: R2DH's D + σ_b needs no pass of its own and
+    follows the σ_b that a loop (or a captured graph) leaves on the device.  None: D enters as it is.
+
+    The 2-D tensors are float64 device tensors with unit inner stride and a common row stride (the library's ld >= n; the
+    elements between the rows are never touched).  lam, d_shift, l, u: 1-D float64 device tensors with one entry per problem.
+    selected: ONE selection shared by the problems (Box forms) -- a uint8 device mask of length n, used as it is, or 0-based
+    indices, from which a mask is built on every call.  out: a contiguous batch × 4 float64 device tensor (None: allocated).
+    d_flag (unboxed kinds): a contiguous int32 device tensor with one word per problem; after the call d_flag[b] is 1 when some
+    deff <= 0 or NaN occurred in row b (the reference's `@assert d[i] > 0`, per problem, not read back), else 0.  None: allocated
+    and dropped; a caller who wants the check passes the tensor.  Returns (Y, out); nothing is read back and the stream is not
+    synchronised.  Y must be neither G nor D; xkn must be none of the other tensors.  Y[b] and xkn[b] have the bits of
+    iprox_step_bang on row b alone with lam[b] and the vector D[b] + d_shift[b]."""
+    if kind not in ("l1", "l0"):
+        raise TypeError('kind must be "l1" or "l0" (the batched call serves NormL1 / NormL0 and their Box forms)')
+    _batch_matrix(Y, "Y")
+    for t, name in ((G, "G"), (D, "D"), (XK, "XK"), (SJ, "SJ")):
+        _batch_matrix(t, name, like=Y)
+    if xkn is not None:
+        _batch_matrix(xkn, "xkn", like=Y)
+    if Y is G or Y is D:
+        raise TypeError("iprox_step_batch: Y must be neither G nor D (gy and ydy are taken with the G and D that were passed)")
+    batch, n = Y.shape
+    # (one row has no row stride to share: with batch == 1 the strides are not compared and the library gets ld = n)
+    ld = Y.stride(0) if batch > 1 else max(n, 1)
+    if ld < n:
+        raise TypeError("the rows of Y overlap (row stride %d < n = %d)" % (ld, n))
+    box = l is not None or u is not None
+    if box and (l is None or u is None):
+        raise TypeError("l and u are given together (one scalar per problem each)")
+    if selected is not None and not box:
+        raise TypeError("selected needs the box form (give l and u)")
+    if box and d_flag is not None:
+        raise TypeError("d_flag belongs to the unboxed kinds (the Box forms accept any d)")
+    for t, name in ((lam, "lam"),) + (((d_shift, "d_shift"),) if d_shift is not None else ()) + (((l, "l"), (u, "u")) if box else ()):
+        _batch_params(t, name, batch, Y)
+    if out is None:
+        out = torch.empty((batch, 4), dtype=torch.float64, device=Y.device)
+    elif not (type(out) is _Tensor and out.is_cuda and out.dtype == torch.float64 and tuple(out.shape) == (batch, 4)
+              and out.is_contiguous() and out.device == Y.device):
+        raise TypeError("out must be a contiguous batch x 4 float64 device tensor on Y's device")
+    L = _lib.load_ibatch()
+    head = (_ctx(Y.device), _ptr(Y), _ptr(G), _ptr(D), _ptr(XK), _ptr(SJ), n, batch, ld, _ptr(lam), _ptr(d_shift))
+    if not box:
+        if d_flag is None:
+            d_flag = torch.empty((max(batch, 1),), dtype=torch.int32, device=Y.device)
+        elif not (type(d_flag) is _Tensor and d_flag.is_cuda and d_flag.dtype == torch.int32 and d_flag.dim() == 1
+                  and d_flag.numel() == batch and (batch <= 1 or d_flag.stride(0) == 1) and d_flag.device == Y.device):
+            raise TypeError("d_flag must be a contiguous 1-D int32 device tensor with one word per problem (%d) on Y's device" % batch)
+        _lib.check(getattr(L, "spx_iproxstep_%s_batch" % kind)(*head, _ptr(d_flag), _ptr(xkn), _ptr(out)))
+        return Y, out
+    mask = None
+    if selected is not None:
+        if type(selected) is _Tensor and selected.dtype == torch.uint8:
+            if not (selected.is_cuda and selected.dim() == 1 and selected.numel() == n and (n <= 1 or selected.stride(0) == 1)
+                    and selected.device == Y.device):
+                raise TypeError("a selection mask must be a contiguous uint8 device tensor of length n on Y's device")
+            mask = selected
+        else:
+            built = _build_mask(selected, Y[0] if batch else Y.reshape(-1)[:n])
+            mask = built[0] if built is not None else None
+    _lib.check(getattr(L, "spx_iproxstep_%s_box_batch" % kind)(*head, _ptr(l), _ptr(u), _ptr(mask), _ptr(xkn), _ptr(out)))
+    return Y, out
+
+
+def iprox_step_batch(kind, G, D, XK, SJ, lam, d_shift=None, l=None, u=None, selected=None, xkn=None, out=None, d_flag=None):
+    """iprox_step_batch_bang into a new Y shaped and strided like G: (Y, out); see iprox_step_batch_bang"""
+    return iprox_step_batch_bang(torch.empty_strided(G.shape, G.stride(), dtype=G.dtype, device=G.device), kind, G, D, XK, SJ, lam,
+                                 d_shift, l, u, selected, xkn, out, d_flag)
+
+
 def shift_bang(ψ, shift):
     """shift!(ψ, v): in-place copy into ψ.sj (twice shifted) or ψ.xk -- i.e. into the caller's tensor
     (src/ShiftedProximalOperators.jl:72-79)."""
