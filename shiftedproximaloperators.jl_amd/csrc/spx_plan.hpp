@@ -321,9 +321,10 @@ inline int team_layout(int64_t cap, int team_fast, bool binf, int64_t n, bool ha
 }
 
 // ---------------------------------------------------------------------------------------------
-// batched separable prox! + step statistics (spx_proxstep_*_batch, spx_batch.hip): `batch` problems of n elements, problem
-// b at elements [b * ld, b * ld + n) of every vector.  The functions the kernels walk a row with are the ones below, so the
-// mapping (workgroup -> problem, tile, head, pairs, tail) is what tests/c/batch_plan_driver.hip enumerates on a CPU.
+// batched separable calls (spx_batch_device.hpp; prox!: spx_proxstep_*_batch, spx_batch.hip; iprox!: spx_iproxstep_*_batch,
+// spx_ibatch.hip): `batch` problems of n elements, problem b at elements [b * ld, b * ld + n) of every vector.  The functions
+// the kernels walk a row with are the ones below, so the mapping (workgroup -> problem, tile, head, pairs, tail) is what
+// tests/c/batch_plan_driver.hip enumerates on a CPU.  The two kinds of call differ here in two numbers only (BatchKind).
 // ---------------------------------------------------------------------------------------------
 #if defined(__HIPCC__)
 #define SPX_PLAN_HD __host__ __device__
@@ -332,9 +333,14 @@ inline int team_layout(int64_t cap, int team_fast, bool binf, int64_t n, bool ha
 #endif
 constexpr int kBatchTile = 3072;            // elements of a row per tile: 256 lanes x 6 pairs (element-wise: x 12 elements)
 constexpr int64_t kBatchRowMax = 4 * (int64_t)kBatchTile;  // one workgroup owns a whole problem up to here (12288); beyond: one tile per workgroup
-constexpr int kBatchVectors = 5;            // y, q, xk, sj, xkn: one bit each in base_alignment_bits
-constexpr int kBatchAllOff = (1 << kBatchVectors) - 1;
 constexpr int64_t kBatchGridMax = 0x7fffffff;
+struct BatchKind {
+  int vectors;  // one bit each in base_alignment_bits, in this order; an absent xkn counts as y
+  int planes;   // sums per problem = planes of partials in the tiled form's workspace
+  constexpr int all_off() const { return (1 << vectors) - 1; }
+};
+constexpr BatchKind kBatchProx{5, 3};   // y, q, xk, sj, xkn;    h terms, <q, y>, <y, y>
+constexpr BatchKind kBatchIprox{6, 4};  // y, g, d, xk, sj, xkn; h terms, <g, y>, <d .* y, y>, <y, y>
 
 enum class BatchForm { kRow, kTiled };
 struct BatchPlan {
@@ -344,7 +350,7 @@ struct BatchPlan {
   int base_odd;     // pairs: the bases sit 8 bytes off a 16-byte boundary
   int64_t grid;     // workgroups of the launch that stores y
   int64_t tiles_per_problem;
-  size_t ws_bytes;  // tiled form: three planes of partials per problem, laid out [problem][plane][tile]
+  size_t ws_bytes;  // tiled form: the kind's planes of partials per problem, laid out [problem][plane][tile]
 };
 // A row in the pairs form: `head` (0 or 1) scalar elements up to the row's first 16-byte boundary, npairs pairs, `tail` (0 or 1)
 // scalar elements.  Element-wise form: n units of one element, no head, no tail.
@@ -365,19 +371,21 @@ SPX_PLAN_HD inline void batch_tile_units(int64_t count, int64_t tile, int units_
   *lo = a < count ? a : count;
   *hi = e < count ? e : count;
 }
-// workgroup -> (problem, tile) of the tiled form, and the slot of its partial sum `plane` in the workspace
+// workgroup -> (problem, tile) of the tiled form, and the slot of its partial sum `plane` (of `planes`) in the workspace
 SPX_PLAN_HD inline void batch_workgroup(int64_t wg, int64_t tiles, int64_t* problem, int64_t* tile) {
   *problem = wg / tiles;
   *tile = wg - *problem * tiles;
 }
-SPX_PLAN_HD inline int64_t batch_slot(int64_t problem, int plane, int64_t tile, int64_t tiles) { return (problem * 3 + plane) * tiles + tile; }
+SPX_PLAN_HD inline int64_t batch_slot(int64_t problem, int plane, int64_t tile, int64_t tiles, int planes) {
+  return (problem * planes + plane) * tiles + tile;
+}
 
-// base_alignment_bits: bit k set = vector k (y, q, xk, sj, xkn; an absent xkn counts as y) starts 8 bytes off a 16-byte boundary
-inline BatchPlan batch_plan(int64_t n, int64_t batch, int64_t ld, int base_alignment_bits) {
+// base_alignment_bits: bit k set = vector k of the kind starts 8 bytes off a 16-byte boundary
+inline BatchPlan batch_plan(int64_t n, int64_t batch, int64_t ld, int base_alignment_bits, BatchKind kind) {
   (void)ld;  // (the rows' parities come from ld in batch_row_map; the launch shape does not depend on it)
   BatchPlan p{};
   p.form = n <= kBatchRowMax ? BatchForm::kRow : BatchForm::kTiled;
-  p.pairs = base_alignment_bits == 0 || base_alignment_bits == kBatchAllOff;
+  p.pairs = base_alignment_bits == 0 || base_alignment_bits == kind.all_off();
   p.base_odd = (p.pairs && base_alignment_bits != 0) ? 1 : 0;
   p.tiles_per_problem = batch_tiles(n);
   if (p.form == BatchForm::kRow) {
@@ -385,38 +393,7 @@ inline BatchPlan batch_plan(int64_t n, int64_t batch, int64_t ld, int base_align
   } else {
     if (batch > kBatchGridMax / p.tiles_per_problem) return p;  // (no overflow: tiles_per_problem >= 5 here)
     p.grid = batch * p.tiles_per_problem;
-    p.ws_bytes = (size_t)batch * 3 * (size_t)p.tiles_per_problem * sizeof(double);
-  }
-  p.ok = p.grid <= kBatchGridMax;
-  return p;
-}
-
-// ---------------------------------------------------------------------------------------------
-// batched iprox! + step statistics (spx_iproxstep_*_batch, spx_ibatch.hip): the layout of the batched prox! above with six
-// vectors (y, g, d, xk, sj, xkn) and four sums.  The rows, tiles and workgroups are mapped by the functions above, unchanged;
-// only the alignment bits and the planes of the partials differ.  tests/c/ibatch_plan_driver.hip enumerates it on a CPU.
-// ---------------------------------------------------------------------------------------------
-constexpr int kIbatchVectors = 6;           // y, g, d, xk, sj, xkn: one bit each in base_alignment_bits
-constexpr int kIbatchAllOff = (1 << kIbatchVectors) - 1;
-constexpr int kIbatchPlanes = 4;            // h terms, <g, y>, <d .* y, y>, <y, y>
-SPX_PLAN_HD inline int64_t ibatch_slot(int64_t problem, int plane, int64_t tile, int64_t tiles) {
-  return (problem * kIbatchPlanes + plane) * tiles + tile;
-}
-// base_alignment_bits: bit k set = vector k (y, g, d, xk, sj, xkn; an absent xkn counts as y) starts 8 bytes off a 16-byte
-// boundary.  The result is a BatchPlan: ws_bytes holds four planes of partials per problem, [problem][plane][tile].
-inline BatchPlan ibatch_plan(int64_t n, int64_t batch, int64_t ld, int base_alignment_bits) {
-  (void)ld;
-  BatchPlan p{};
-  p.form = n <= kBatchRowMax ? BatchForm::kRow : BatchForm::kTiled;
-  p.pairs = base_alignment_bits == 0 || base_alignment_bits == kIbatchAllOff;
-  p.base_odd = (p.pairs && base_alignment_bits != 0) ? 1 : 0;
-  p.tiles_per_problem = batch_tiles(n);
-  if (p.form == BatchForm::kRow) {
-    p.grid = batch;
-  } else {
-    if (batch > kBatchGridMax / p.tiles_per_problem) return p;  // (no overflow: tiles_per_problem >= 5 here)
-    p.grid = batch * p.tiles_per_problem;
-    p.ws_bytes = (size_t)batch * kIbatchPlanes * (size_t)p.tiles_per_problem * sizeof(double);
+    p.ws_bytes = (size_t)batch * kind.planes * (size_t)p.tiles_per_problem * sizeof(double);
   }
   p.ok = p.grid <= kBatchGridMax;
   return p;

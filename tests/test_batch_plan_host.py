@@ -1,7 +1,7 @@
 """CPU: the device-free plan of the batched separable call (csrc/spx_plan.hpp: batch_plan and the row / tile mapping that
 k_sep_batch walks) -- every element of every row touched exactly once and no padding, the workspace slots, the form as a function
-of n alone, the refusal of a grid beyond 2^31 - 1 workgroups -- in a stand-alone program (tests/c/batch_plan_driver.hip, its own
-main) built with AddressSanitizer + UBSan on the host side and run as a child.  Nothing is put into LD_PRELOAD and the library is
+of n alone, the refusal of a grid beyond 2^31 - 1 workgroups -- in a stand-alone program (tests/c/batch_plan_driver.hip run as
+`prox`, its own main) built with AddressSanitizer + UBSan on the host side and run as a child.  Nothing is put into LD_PRELOAD and the library is
 not loaded."""
 import os
 import subprocess
@@ -24,7 +24,7 @@ def test_batch_plan_covers_every_row_exactly_once_sanitized(tmp_path):
     assert b.returncode == 0, b.stderr[-4000:]
     env = dict(os.environ)
     env.update(ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    r = subprocess.run([exe], env=env, capture_output=True, text=True, timeout=300)
+    r = subprocess.run([exe, "prox"], env=env, capture_output=True, text=True, timeout=300)
     lines = r.stdout.split()
     assert r.returncode == 0 and lines[-1:] == ["ok"], r.stdout[-2000:] + r.stderr[-4000:]
     # the grid of cases is there: 24584 sizes x 10 batches x 4 paddings x 3 alignments, several checks each

@@ -1,7 +1,7 @@
-"""CPU: the device-free plan of the batched iprox! call (csrc/spx_plan.hpp: ibatch_plan, ibatch_slot and the row / tile mapping
-that k_isep_batch walks) -- every element of every row of all six vectors touched exactly once and no padding, the four-plane
+"""CPU: the device-free plan of the batched iprox! call (csrc/spx_plan.hpp: batch_plan and batch_slot at kBatchIprox and the row /
+tile mapping that k_isep_batch walks) -- every element of every row of all six vectors touched exactly once and no padding, the four-plane
 workspace holding exactly the slots the reduce reads, the form as a function of n alone, the refusal of a grid beyond 2^31 - 1
-workgroups -- in a stand-alone program (tests/c/ibatch_plan_driver.hip, its own main) built with AddressSanitizer + UBSan on
+workgroups -- in a stand-alone program (tests/c/batch_plan_driver.hip run as `iprox`, its own main) built with AddressSanitizer + UBSan on
 the host side and run as a child.  Nothing is put into LD_PRELOAD and the library is not loaded."""
 import os
 import subprocess
@@ -19,12 +19,12 @@ def test_ibatch_plan_covers_every_row_exactly_once_sanitized(tmp_path):
     cmd = [HIPCC, "--offload-arch=gfx950", "--offload-host-only", "-O1", "-g", "-std=c++17", "-Xarch_host", "-fsanitize=address,undefined",
            "-Xarch_host", "-fno-sanitize-recover=undefined", "-I" + os.path.join(ROOT, "include"),
            "-I" + os.path.join(ROOT, "shiftedproximaloperators.jl_amd", "csrc"),
-           os.path.join(ROOT, "tests", "c", "ibatch_plan_driver.hip"), "-o", exe]
+           os.path.join(ROOT, "tests", "c", "batch_plan_driver.hip"), "-o", exe]
     b = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert b.returncode == 0, b.stderr[-4000:]
     env = dict(os.environ)
     env.update(ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    r = subprocess.run([exe], env=env, capture_output=True, text=True, timeout=300)
+    r = subprocess.run([exe, "iprox"], env=env, capture_output=True, text=True, timeout=300)
     lines = r.stdout.split()
     assert r.returncode == 0 and lines[-1:] == ["ok"], r.stdout[-2000:] + r.stderr[-4000:]
     # the grid of cases is there: 24584 sizes x 10 batches x 4 paddings x 4 alignments, several checks each

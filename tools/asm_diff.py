@@ -4,8 +4,9 @@
 DIR_A and DIR_B hold one .s per csrc/*.hip, compiled with the flags of csrc/build.sh plus `--cuda-device-only -S`.  Comments,
 .file / .ident / .loc lines and the position of a function in its file (the number in local labels such as .LBB12_3, which
 changes when the host code instantiates the kernels in another order) are dropped; then every function's instructions and
-every kernel descriptor (.amdhsa_* lines: registers, LDS, scratch) are compared by symbol.  One summary line per file, exit
-status 1 on any difference.  profiles/result_dest_asm_diff.txt is its output."""
+every kernel descriptor (.amdhsa_* lines: registers, LDS, scratch) are compared by symbol.  One summary line per file, then
+the symbols that differ; a kernel whose descriptor differs is listed with the keys that moved (`key a -> b`).  Exit status 1
+on any difference.  profiles/result_dest_asm_diff.txt and profiles/batch_shared_asm_diff.txt are its output."""
 import hashlib
 import os
 import re
@@ -58,8 +59,12 @@ def main(a, b):
               % (f, len(fa), len(ka), sum(len(v) for v in fa.values()), worst(ka, ".amdhsa_next_free_vgpr"),
                  worst(ka, ".amdhsa_group_segment_fixed_size"), worst(ka, ".amdhsa_private_segment_fixed_size"), digest,
                  "equal" if sets else "DIFFER", len(df), len(dk)))
-        for n in sorted(set(fa) ^ set(fb))[:8] + df[:8] + dk[:8]:
+        for n in sorted(set(fa) ^ set(fb))[:8] + df[:8]:
             print("    differs: " + n)
+        for n in dk:
+            da, db = (dict(l.split(None, 1) for l in k[n]) for k in (ka, kb))
+            print("    descriptor differs: %s  %s" % (n, ", ".join(
+                "%s %s -> %s" % (key, da.get(key, "-"), db.get(key, "-")) for key in sorted(set(da) | set(db)) if da.get(key) != db.get(key))))
         differing += (not sets) or bool(df) or bool(dk)
         nf += len(fa)
         nk += len(ka)
