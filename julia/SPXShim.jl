@@ -403,6 +403,46 @@ function iprox_step_batch!(Y::DMat, kind::Symbol, G::DMat, D::DMat, XK::DMat, SJ
 end
 
 # ---------------------------------------------------------------------------------------------
+# group_prox_step! of the plain operator (ShiftedGroupNormL2) for `batch` problems in ONE call, every per-problem parameter read
+# from DEVICE memory (spx_proxstep_group_l2_batch; no counterpart in the reference): a path of group-lasso problems in lock step.
+# Problem b is column b of the n × batch device matrices Y, Q, XK, SJ (and xkn), n = ngroups * group_size in uniform contiguous
+# groups of group_size (1 .. 512) elements.  λ: the group weights, a ROCVector{Float64} of length ngroups (ONE weight vector
+# shared by the problems: ldl = 0) or an ngroups × batch device matrix (one column per problem: ldl = its column stride).
+# λ_scale: a ROCVector{Float64} of length batch or nothing -- given, the weight of group g of problem b is λ_scale[b] * λ[g(, b)],
+# ONE rounded multiply.  σ, q_scale: ROCVector{Float64} of length batch.  out: a 3 × batch device matrix; out[:, b] = (h, qy, yy) of
+# problem b as group_prox_step! returns them.  Returns (Y, out); never synchronises.
+# (This binding has never been executed: there is no Julia toolchain where the library is built and tested.)
+# ---------------------------------------------------------------------------------------------
+const libspx_gbatch = get(ENV, "LIBSPX_GBATCH", "libspx_gbatch.so")   # include/spx_gbatch.h: a fourth library, linked against libspx
+function prox_step_group_batch!(Y::DMat, Q::DMat, XK::DMat, SJ::DMat, group_size::Integer, λ::Union{DVec, DMat}, σ::DVec,
+                                q_scale::DVec; λ_scale::Union{Nothing, DVec} = nothing, xkn::Union{Nothing, DMat} = nothing,
+                                out::DMat = ROCMatrix{Float64}(undef, 3, size(Y, 2)))
+  n, batch = size(Y)
+  (1 <= group_size <= 512 && n % group_size == 0) || throw(ArgumentError("uniform groups of 1 .. 512 elements"))
+  ngroups = n ÷ group_size
+  ld = batch > 1 ? stride(Y, 2) : max(n, 1)
+  for M in (Q, XK, SJ, xkn)
+    M === nothing && continue
+    (size(M) == (n, batch) && (batch <= 1 || stride(M, 2) == ld)) || throw(BoundsError())
+  end
+  ldl = 0
+  if λ isa DMat
+    size(λ) == (ngroups, batch) || throw(BoundsError())
+    ldl = batch > 1 ? stride(λ, 2) : max(ngroups, 1)
+  else
+    length(λ) == ngroups || throw(BoundsError())
+  end
+  (length(σ) == batch && length(q_scale) == batch && (λ_scale === nothing || length(λ_scale) == batch) &&
+   size(out) == (3, batch)) || throw(BoundsError())
+  check(ccall((:spx_proxstep_group_l2_batch, libspx_gbatch), Cint,
+              (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int64, Int64, Int64, Int64,
+               Ptr{Cdouble}, Int64, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+              ctx(), dptr(Y), dptr(Q), dptr(XK), dptr(SJ), group_size, ngroups, batch, ld, dptr(λ), ldl, dptr(λ_scale), dptr(σ),
+              dptr(q_scale), dptr(xkn), dptr(out)))
+  return Y, out
+end
+
+# ---------------------------------------------------------------------------------------------
 # l1 norm + l2-ball trust region     src/shiftedNormL1B2.jl:50-67   (χ = NormL2(χ.lambda))
 # ---------------------------------------------------------------------------------------------
 function prox!(y::DVec, ψ::ShiftedProximalOperators.ShiftedNormL1B2{Float64, <:DVec, <:DVec, <:DVec}, q::DVec, σ::Float64)

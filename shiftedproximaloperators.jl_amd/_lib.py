@@ -122,6 +122,12 @@ IBATCH_SIGNATURES = {
     "spx_iproxstep_l0_box_batch": [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _p],
 }
 
+# libspx_gbatch.so (include/spx_gbatch.h): the batched group call, a fourth library that links against libspx.so
+GBATCH_LIB_PATH = LIB_PATH[:-3] + "_gbatch.so"
+GBATCH_SIGNATURES = {
+    "spx_proxstep_group_l2_batch": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _i64, _p, _p, _p, _p, _p],
+}
+
 
 class SpxError(RuntimeError):
     """A libspx call returned a non-zero spx_status."""
@@ -189,6 +195,26 @@ def load_ibatch():
             fn.restype = _int
         _ibatch = L
     return _ibatch
+
+
+_gbatch = None
+
+
+def load_gbatch():
+    """Load libspx_gbatch.so (after libspx.so, whose contexts and error text it shares).  Raises if it is missing."""
+    global _gbatch
+    if _gbatch is None:
+        load()
+        if not os.path.exists(GBATCH_LIB_PATH):
+            raise ImportError("libspx_gbatch.so not found at %s -- build it with shiftedproximaloperators.jl_amd/csrc/build.sh; "
+                              "there is no CPU fallback" % GBATCH_LIB_PATH)
+        L = ctypes.CDLL(GBATCH_LIB_PATH)
+        for name, args in GBATCH_SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.argtypes = args
+            fn.restype = _int
+        _gbatch = L
+    return _gbatch
 
 
 def check(status):

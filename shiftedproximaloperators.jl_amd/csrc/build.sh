@@ -4,7 +4,8 @@
 # One object per source file, compiled in parallel (no cross-file device calls, so no -fgpu-rdc), then one link.
 # spx_batch.hip (the batched separable call, include/spx_batch.h) becomes a library of its own, lib/libspx_batch.so -- for
 # SPX_LIB_NAME=X.so: X_batch.so -- linked against the first one (found next to it: rpath $ORIGIN).  spx_ibatch.hip (the batched
-# iprox! call, include/spx_ibatch.h) becomes a third one in the same way: lib/libspx_ibatch.so, X_ibatch.so.
+# iprox! call, include/spx_ibatch.h) becomes a third one in the same way: lib/libspx_ibatch.so, X_ibatch.so; spx_gbatch.hip (the
+# batched group call, include/spx_gbatch.h) a fourth: lib/libspx_gbatch.so, X_gbatch.so.
 set -euo pipefail
 HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 ROOT="$(cd "$HERE/../.." && pwd)"
@@ -27,6 +28,8 @@ done
 pids+=($!)
 "$HIPCC" "${FLAGS[@]}" -c "$HERE/spx_ibatch.hip" -o "$OBJ/spx_ibatch.o" &
 pids+=($!)
+"$HIPCC" "${FLAGS[@]}" -c "$HERE/spx_gbatch.hip" -o "$OBJ/spx_gbatch.o" &
+pids+=($!)
 fail=0
 for p in "${pids[@]}"; do wait "$p" || fail=1; done
 [ "$fail" = 0 ] || { echo "compile failed" >&2; exit 1; }
@@ -40,4 +43,8 @@ IBATCH="${NAME%.so}_ibatch.so"
 "$HIPCC" --offload-arch=gfx950 -shared -fPIC -fvisibility=hidden "$OBJ/spx_ibatch.o" -L"$OUT" -l:"$NAME" '-Wl,-rpath,$ORIGIN' \
   -o "$OUT/$IBATCH.tmp"
 mv -f "$OUT/$IBATCH.tmp" "$OUT/$IBATCH"
+GBATCH="${NAME%.so}_gbatch.so"
+"$HIPCC" --offload-arch=gfx950 -shared -fPIC -fvisibility=hidden "$OBJ/spx_gbatch.o" -L"$OUT" -l:"$NAME" '-Wl,-rpath,$ORIGIN' \
+  -o "$OUT/$GBATCH.tmp"
+mv -f "$OUT/$GBATCH.tmp" "$OUT/$GBATCH"
 echo "built $OUT/$NAME"

@@ -9,6 +9,8 @@
 //   tiled form (larger n): workgroup (b, t) takes tile t of problem b and stores its partials to the workspace
 //              ([problem][plane][tile]); the reduce kernel, one workgroup per problem, adds them in a fixed order.
 // Which form, grid and workspace: batch_plan (spx_plan.hpp), a function of n alone as far as a problem's bits go.
+// (The batched group call, spx_gbatch.hip, has a kernel body and a host run of its own; it shares the workspace layout, the
+//  reduce -- batch_reduce_body -- and with_bool.)
 // Alignment: all vectors share ld, so when their bases share bit 3 of the address every row is peeled by the kernel -- a head of
 // 0 or 1 elements (batch_row_map: the parity of b * ld), 16-byte pairs, a tail of 0 or 1 elements; bases of mixed alignment take
 // the element-wise instantiation (PAIRS = false).  The mask is shared by the problems and read by bytes.
@@ -196,8 +198,9 @@ __device__ __forceinline__ void batch_body(const BatchArgs& k) {
 }
 // The reduce of the tiled form: workgroup b adds the NS planes of problem b's partials, `tiles` slots each, in a fixed order --
 // the order of the single call's sums on short lists (value_reduce_small), eight loads in flight per lane on long ones -- and
-// stores stats[NS b + p]: plane 0 times lambda[b], the other planes as they are.  Grid: batch.
-template <int NS>
+// stores stats[NS b + p]: plane 0 times lambda[b] (SCALE0; the group call's terms carry their own weights: plane 0 as it is,
+// lambda unused), the other planes as they are.  Grid: batch.
+template <int NS, bool SCALE0 = true>
 __device__ __forceinline__ void batch_reduce_body(const double* partials, int64_t tiles, const double* lambda, double* stats) {
   const int64_t b = blockIdx.x;
   const double* const part = partials + batch_slot(b, 0, 0, tiles, NS);
@@ -223,7 +226,8 @@ __device__ __forceinline__ void batch_reduce_body(const double* partials, int64_
     s = block_sum4(s);
   }
   if (threadIdx.x == 0) {
-    stats[NS * b] = lambda[b] * s.v[0];
+    if constexpr (SCALE0) stats[NS * b] = lambda[b] * s.v[0];
+    else stats[NS * b] = s.v[0];
 #pragma unroll
     for (int p = 1; p < NS; ++p) stats[NS * b + p] = s.v[p];
   }

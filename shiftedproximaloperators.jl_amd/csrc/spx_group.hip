@@ -922,38 +922,8 @@ struct GroupCall {
   double sigma, delta;
 };
 
-// Register tiles.  A row GroupTile<MAXG, LPG, EPL> sends the group sizes (uniform, or the caller's bound on ragged sizes) up to
-// MAXG that no earlier row takes to LPG lanes per group x EPL elements per lane: the smallest tile that holds a group, partly
-// filled tiles are padded with zeros.  A table states each bound with its tile, once; the launch site receives the row as a type.
-constexpr int kGroupRegMax = 512;  // the largest size on the register tiles
-template <int MAXG, int LPG, int EPL>
-struct GroupTile {
-  static_assert(LPG * EPL >= MAXG, "tile cannot hold the sizes routed to it");
-  static_assert(64 % LPG == 0 && EPL % 2 == 0, "LPG lanes of a wavefront, 16-byte pairs");
-  static constexpr int maxg = MAXG, lpg = LPG, epl = EPL;
-};
-constexpr bool group_bounds_ok(std::initializer_list<int> bounds) {  // ascending, up to kGroupRegMax
-  int prev = 0;
-  for (const int b : bounds) {
-    if (b <= prev) return false;
-    prev = b;
-  }
-  return prev == kGroupRegMax;
-}
-template <class... Rows>
-struct GroupTiles {
-  static_assert(group_bounds_ok({Rows::maxg...}), "row bounds must ascend to kGroupRegMax");
-  // f(row) for the row of this size (0 < gsize <= kGroupRegMax)
-  template <class F>
-  static bool select(int64_t gsize, F&& f) {
-    return ((gsize <= Rows::maxg ? (f(Rows{}), true) : false) || ...);
-  }
-  static int lpg(int64_t gsize) {
-    int lanes = 0;
-    select(gsize, [&](auto row) { lanes = decltype(row)::lpg; });
-    return lanes;
-  }
-};
+// Register tiles: GroupTile, GroupTiles and the plain operator's table GroupTilesPlain are spx_group_common.hpp's (the batched
+// call, spx_gbatch.hip, walks the same table).
 // Binf: as few lanes per group as the registers allow (4 x 4/8, 8 x 8/16, 16 x 16, 32 x 16 elements) -- the wave-uniform
 // scalar work of the root find, which every lane executes, is then shared by more groups per wave
 // Small groups (round 3): tiles that FIT -- a 4 x 4 tile spent four lanes' worth of root find (Binf) or reduction on a group
@@ -964,8 +934,6 @@ struct GroupTiles {
 using GroupTilesBinf = GroupTiles<GroupTile<2, 1, 2>, GroupTile<4, 1, 4>, GroupTile<8, 1, 8>, GroupTile<16, 2, 8>, GroupTile<32, 4, 8>,
                                   GroupTile<64, 8, 8>,  // (4 x 16 is slower here: 64-byte runs per group and load)
                                   GroupTile<128, 8, 16>, GroupTile<256, 16, 16>, GroupTile<512, 32, 16>>;
-using GroupTilesPlain = GroupTiles<GroupTile<2, 1, 2>, GroupTile<4, 2, 4>, GroupTile<12, 4, 4>, GroupTile<32, 16, 2>, GroupTile<64, 16, 4>,
-                                   GroupTile<128, 16, 8>, GroupTile<256, 32, 8>, GroupTile<384, 64, 6>, GroupTile<512, 64, 8>>;
 // The LIT launch of the Binf form (its own tiles, by the group size: the list is short, the literal evaluation wants lanes)
 using GroupTilesLit = GroupTiles<GroupTile<16, 4, 4>, GroupTile<32, 4, 8>, GroupTile<64, 8, 8>, GroupTile<128, 8, 16>,
                                  GroupTile<256, 16, 16>, GroupTile<512, 32, 16>>;

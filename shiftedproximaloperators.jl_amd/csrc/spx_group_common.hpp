@@ -1,8 +1,10 @@
 // spx_group_common.hpp -- device code shared by the group kernels (spx_group.hip: register tiles, wavefront / workgroup per
 // group; spx_group_team.hip: a TEAM OF WORKGROUPS per group): team reductions, element providers, the Binf root find
 // (src/shiftedGroupNormL2Binf.jl:85-108) and the per-group body (src/shiftedGroupNormL2.jl:67-76, shiftedGroupNormL2Binf.jl:84-117).
-// k_csr_uncovered, at the end, serves both precisions (spx_group.hip, spx_group_f32.hip); behind it, the host's choice of the
-// lanes per group for the kernels that take that width as a template argument.
+// k_csr_uncovered serves both precisions (spx_group.hip, spx_group_f32.hip); behind it, the register tiles (GroupTile, GroupTiles
+// and the plain operator's table GroupTilesPlain) and the plain operator's step site on such a tile (group_l2_step_site: the
+// batched call, spx_gbatch.hip), then the host's choice of the lanes per group for the kernels that take that width as a
+// template argument.
 #pragma once
 #include <cmath>
 #include <type_traits>
@@ -1012,6 +1014,176 @@ __global__ __launch_bounds__(256) void k_csr_uncovered(T* y, const T* xk, const 
     const int64_t i = (t < head) ? t : tail0 + (t - head);
     y[i] = y[i] - (xk[i] + sj[i]);
   }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Register tiles (k_group_reg of spx_group.hip; k_group_batch of spx_gbatch.hip)
+// ---------------------------------------------------------------------------------------------
+// Register tiles.  A row GroupTile<MAXG, LPG, EPL> sends the group sizes (uniform, or the caller's bound on ragged sizes) up to
+// MAXG that no earlier row takes to LPG lanes per group x EPL elements per lane: the smallest tile that holds a group, partly
+// filled tiles are padded with zeros.  A table states each bound with its tile, once; the launch site receives the row as a type.
+constexpr int kGroupRegMax = 512;  // the largest size on the register tiles
+template <int MAXG, int LPG, int EPL>
+struct GroupTile {
+  static_assert(LPG * EPL >= MAXG, "tile cannot hold the sizes routed to it");
+  static_assert(64 % LPG == 0 && EPL % 2 == 0, "LPG lanes of a wavefront, 16-byte pairs");
+  static constexpr int maxg = MAXG, lpg = LPG, epl = EPL;
+};
+constexpr bool group_bounds_ok(std::initializer_list<int> bounds) {  // ascending, up to kGroupRegMax
+  int prev = 0;
+  for (const int b : bounds) {
+    if (b <= prev) return false;
+    prev = b;
+  }
+  return prev == kGroupRegMax;
+}
+template <class... Rows>
+struct GroupTiles {
+  static_assert(group_bounds_ok({Rows::maxg...}), "row bounds must ascend to kGroupRegMax");
+  // f(row) for the row of this size (0 < gsize <= kGroupRegMax)
+  template <class F>
+  static bool select(int64_t gsize, F&& f) {
+    return ((gsize <= Rows::maxg ? (f(Rows{}), true) : false) || ...);
+  }
+  static int lpg(int64_t gsize) {
+    int lanes = 0;
+    select(gsize, [&](auto row) { lanes = decltype(row)::lpg; });
+    return lanes;
+  }
+};
+using GroupTilesPlain = GroupTiles<GroupTile<2, 1, 2>, GroupTile<4, 2, 4>, GroupTile<12, 4, 4>, GroupTile<32, 16, 2>, GroupTile<64, 16, 4>,
+                                   GroupTile<128, 16, 8>, GroupTile<256, 32, 8>, GroupTile<384, 64, 6>, GroupTile<512, 64, 8>>;
+
+// ---------------------------------------------------------------------------------------------
+// The group site of the plain operator's step form (ShiftedGroupNormL2: prox!, xkn and the three step statistics of ONE
+// group of `gs` elements on an LPG x EPL register tile), as k_group_reg<.., BINF = false, .., VALUE, STEP> of spx_group.hip
+// states it inside its loop: load -> S = (qs q + xk) + sj, XS = xk + sj; snorm; alpha; out = alpha S - XS; v = XS + out; the
+// term lam ||v||; q y; y^2 -- the same lane-to-element mapping (PAIRS: lane j owns the 16-byte pairs j, j + LPG, ...; else
+// the elements j, j + LPG, ...), the same statements in the same order, hence the same bits in y and xkn.  k_group_reg keeps
+// its own text (it stages its loads through LDS and drops q across the Binf root find, which this site does not need to:
+// q stays in registers); tests/test_gpu_proxstep_group_batch.py holds the two statements together bit for bit.
+// y, q, xk, sj, xkn point at the group's first element (xkn may be NULL).  valid = false: an idle slot of the wave tile,
+// which shadows a live group's loads, stores nothing and adds nothing.  cached (wave-uniform): plain accesses (a lane's pairs
+// share cache lines), else non-temporal ones.  Returns acc with the site's terms added: [0] by the group's lane 0,
+// [1] and [2] by every lane over the elements it stored.
+// ---------------------------------------------------------------------------------------------
+struct GroupStepSums { double h, qy, yy; };
+template <int LPG, int EPL, bool PAIRS>
+__device__ __forceinline__ GroupStepSums group_l2_step_site(GroupStepSums acc, double* y, const double* q, const double* xk,
+                                                            const double* sj, double* xkn, int gs, int j, bool valid, double lam,
+                                                            double sigma, double qs, bool cached) {
+  static_assert((EPL % 2) == 0, "EPL must be even (16-byte pairs)");
+  const int npairs = gs >> 1;
+  double A[EPL], S[EPL], XS[EPL];  // q as passed, (qs q + xk) + sj, xk + sj
+  if constexpr (PAIRS) {
+    const f64x2* q2 = reinterpret_cast<const f64x2*>(q);
+    const f64x2* x2 = reinterpret_cast<const f64x2*>(xk);
+    const f64x2* s2 = reinterpret_cast<const f64x2*>(sj);
+    f64x2 vq[EPL / 2], vx[EPL / 2], vs[EPL / 2];
+#pragma unroll
+    for (int k = 0; k < EPL / 2; ++k) {
+      const int p = (k * LPG + j < npairs) ? (k * LPG + j) : 0;  // masked pairs re-read pair 0, zeroed below
+      if (cached) {
+        vq[k] = q2[p]; vx[k] = x2[p]; vs[k] = s2[p];
+      } else {
+        vq[k] = __builtin_nontemporal_load(q2 + p);
+        vx[k] = __builtin_nontemporal_load(x2 + p);
+        vs[k] = __builtin_nontemporal_load(s2 + p);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < EPL / 2; ++k) {
+      const bool in = (k * LPG + j) < npairs;
+      const f64x2 zero2 = f64x2{0.0, 0.0};
+      f64x2 a = in ? vq[k] : zero2;
+      const f64x2 b = in ? vx[k] : zero2, c = in ? vs[k] : zero2;
+      A[2 * k] = a.x;
+      A[2 * k + 1] = a.y;
+      a.x = qs * a.x; a.y = qs * a.y;  // (rounded here: never contracted into the sum below)
+      S[2 * k] = (a.x + b.x) + c.x;  // shiftedGroupNormL2.jl:65
+      S[2 * k + 1] = (a.y + b.y) + c.y;
+      XS[2 * k] = b.x + c.x;
+      XS[2 * k + 1] = b.y + c.y;
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < EPL; ++k) {
+      const int e = k * LPG + j;
+      const bool in = e < gs;
+      const int i = in ? e : 0;
+      double a = in ? q[i] : 0.0;
+      const double b = in ? xk[i] : 0.0, c = in ? sj[i] : 0.0;
+      A[k] = a;
+      a = qs * a;
+      S[k] = (a + b) + c;
+      XS[k] = b + c;
+    }
+  }
+  double out[EPL];
+  double ss = 0.0;
+#pragma unroll
+  for (int k = 0; k < EPL; ++k) ss += S[k] * S[k];
+  const double snorm = sqrt(lanes_sum<LPG>(ss));                                       // shiftedGroupNormL2.jl:69
+  const double alpha = (snorm == 0.0) ? 0.0 : jl_max(1 - sigma * lam / snorm, 0.0);  // :70-73
+#pragma unroll
+  for (int k = 0; k < EPL; ++k) out[k] = ((snorm == 0.0) ? 0.0 : alpha * S[k]) - XS[k];  // :74,:77
+  // v = (xk + sj) + y of the elements this lane is about to store; slots past the end of the group add nothing
+  double vv = 0.0;
+#pragma unroll
+  for (int k = 0; k < EPL; ++k) {
+    const bool in = PAIRS ? ((k >> 1) * LPG + j) < npairs : (k * LPG + j) < gs;
+    const double v = XS[k] + out[k];
+    vv += in ? v * v : 0.0;
+  }
+  vv = lanes_sum<LPG>(vv);
+  if (valid && j == 0) acc.h += lam * sqrt(vv);
+  double qy = 0.0, yy = 0.0;
+  if constexpr (PAIRS) {
+#pragma unroll
+    for (int k = 0; k < EPL / 2; ++k) {
+      const bool in = (k * LPG + j) < npairs;
+      qy += in ? A[2 * k] * out[2 * k] : 0.0;
+      qy += in ? A[2 * k + 1] * out[2 * k + 1] : 0.0;
+      yy += in ? out[2 * k] * out[2 * k] : 0.0;
+      yy += in ? out[2 * k + 1] * out[2 * k + 1] : 0.0;
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < EPL; ++k) {
+      const bool in = (k * LPG + j) < gs;
+      qy += in ? A[k] * out[k] : 0.0;
+      yy += in ? out[k] * out[k] : 0.0;
+    }
+  }
+  if (valid) {
+    acc.qy += qy;
+    acc.yy += yy;
+    if constexpr (PAIRS) {
+      f64x2* y2 = reinterpret_cast<f64x2*>(y);
+      f64x2* v2 = reinterpret_cast<f64x2*>(xkn);
+#pragma unroll
+      for (int k = 0; k < EPL / 2; ++k)
+        if (k * LPG + j < npairs) {
+          const f64x2 o = f64x2{out[2 * k], out[2 * k + 1]};
+          const f64x2 v = f64x2{XS[2 * k] + out[2 * k], XS[2 * k + 1] + out[2 * k + 1]};  // v as the h term formed it
+          if (cached) {
+            y2[k * LPG + j] = o;
+            if (xkn != nullptr) v2[k * LPG + j] = v;
+          } else {
+            __builtin_nontemporal_store(o, y2 + k * LPG + j);
+            if (xkn != nullptr) __builtin_nontemporal_store(v, v2 + k * LPG + j);
+          }
+        }
+    } else {
+#pragma unroll
+      for (int k = 0; k < EPL; ++k)
+        if (k * LPG + j < gs) {
+          y[k * LPG + j] = out[k];
+          if (xkn != nullptr) xkn[k * LPG + j] = XS[k] + out[k];
+        }
+    }
+  }
+  return acc;
 }
 
 // ---------------------------------------------------------------------------------------------

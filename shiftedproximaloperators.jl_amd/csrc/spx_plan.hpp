@@ -1,6 +1,6 @@
 // spx_plan.hpp -- WHICH kernel runs, on WHICH grid, with WHICH workspace: the decisions of the calls whose kernels synchronise
 // inside one launch (top-r: spx_select.hip; ShiftedNormL1B2: spx_b2.hip; large groups on teams: spx_group_team.hip) and of the
-// batched separable call (spx_batch.hip), as plain functions of plain values.  No HIP include, no runtime call, no kernel, no spx_ctx: what a call would do at a given n,
+// batched separable calls (spx_batch.hip, spx_ibatch.hip) and the batched group call (spx_gbatch.hip), as plain functions of plain values.  No HIP include, no runtime call, no kernel, no spx_ctx: what a call would do at a given n,
 // alignment, residency and tuning is computable -- and testable, tests/c/plan_driver.hip -- on a CPU.
 //
 // Residency comes in through `cap`: cap(kernel) returns what spx_resident_cap returns for that kernel (0 = it cannot run; the
@@ -394,6 +394,64 @@ inline BatchPlan batch_plan(int64_t n, int64_t batch, int64_t ld, int base_align
     if (batch > kBatchGridMax / p.tiles_per_problem) return p;  // (no overflow: tiles_per_problem >= 5 here)
     p.grid = batch * p.tiles_per_problem;
     p.ws_bytes = (size_t)batch * kind.planes * (size_t)p.tiles_per_problem * sizeof(double);
+  }
+  p.ok = p.grid <= kBatchGridMax;
+  return p;
+}
+
+// ---------------------------------------------------------------------------------------------
+// batched group call (spx_proxstep_group_l2_batch, spx_gbatch.hip): `batch` problems of ngroups uniform contiguous groups of
+// group_size elements, problem b at elements [b * ld, b * ld + ngroups * group_size) of every vector.  A wavefront serves
+// 64 / lpg groups at a time (a wave tile; lpg = the lanes per group of the size's row of GroupTilesPlain, spx_group_common.hpp,
+// handed in by the caller: the table is stated there, once).
+//   row form   (n = ngroups * group_size <= kBatchRowMax): one workgroup owns a problem; wave w takes its wave tiles w, w + 4, ...
+//   tiled form (larger n): workgroup (b, t) takes the groups [t * run, (t + 1) * run) of problem b -- whole groups, `run` a
+//              multiple of the 4 wave tiles a workgroup serves side by side, about kBatchTile elements -- and stores three
+//              partials to batch_slot(b, plane, t); the reduce kernel, one workgroup per problem, adds them.
+// Form, run and tiles are functions of (group_size, ngroups) alone: a problem's bits do not depend on batch or on its row.
+// Pairs (16-byte accesses): group_size even, ld even and every base on a 16-byte boundary -- every group of every row then
+// starts on one; otherwise the element-wise form for the whole launch.
+// ---------------------------------------------------------------------------------------------
+constexpr int kGBatchPlanes = 3;  // h terms, <q, y>, <y, y>
+struct GBatchPlan {
+  bool ok;          // false: the call needs more than kBatchGridMax workgroups (refused)
+  BatchForm form;
+  bool pairs;
+  int64_t run;      // groups per workgroup of the tiled form (row form: all of them)
+  int64_t tiles_per_problem;
+  int64_t grid;     // workgroups of the launch that stores y
+  size_t ws_bytes;  // tiled form: kGBatchPlanes planes of partials per problem, [problem][plane][tile]
+};
+// groups per tile of the tiled form: the largest multiple of 4 * (64 / lpg) groups within kBatchTile elements, at least one
+SPX_PLAN_HD inline int64_t gbatch_run(int64_t group_size, int lpg) {
+  const int64_t quad = 4 * (64 / lpg);
+  const int64_t k = kBatchTile / (group_size * quad);
+  return (k < 1 ? 1 : k) * quad;
+}
+// the groups [*lo, *hi) of a problem that tile `tile` owns
+SPX_PLAN_HD inline void gbatch_tile_groups(int64_t ngroups, int64_t tile, int64_t run, int64_t* lo, int64_t* hi) {
+  const int64_t a = tile * run;
+  const int64_t e = a + run;
+  *lo = a < ngroups ? a : ngroups;
+  *hi = e < ngroups ? e : ngroups;
+}
+// base_alignment_bits: bit k set = vector k of y, q, xk, sj, xkn starts off a 16-byte boundary (an absent xkn: clear).
+// ngroups * group_size must not overflow (the caller refuses that first).
+inline GBatchPlan gbatch_plan(int64_t group_size, int lpg, int64_t ngroups, int64_t batch, int64_t ld, int base_alignment_bits) {
+  GBatchPlan p{};
+  const int64_t n = ngroups * group_size;
+  p.form = n <= kBatchRowMax ? BatchForm::kRow : BatchForm::kTiled;
+  p.pairs = (group_size & 1) == 0 && (ld & 1) == 0 && base_alignment_bits == 0;
+  if (p.form == BatchForm::kRow) {
+    p.run = ngroups;
+    p.tiles_per_problem = 1;
+    p.grid = batch;
+  } else {
+    p.run = gbatch_run(group_size, lpg);
+    p.tiles_per_problem = (ngroups + p.run - 1) / p.run;
+    if (batch > kBatchGridMax / p.tiles_per_problem) return p;  // (no overflow: tiles_per_problem >= 5 here)
+    p.grid = batch * p.tiles_per_problem;
+    p.ws_bytes = (size_t)batch * kGBatchPlanes * (size_t)p.tiles_per_problem * sizeof(double);
   }
   p.ok = p.grid <= kBatchGridMax;
   return p;

@@ -976,6 +976,75 @@ def prox_step_batch(kind, Q, XK, SJ, lam, sigma, q_scale, l=None, u=None, select
                                 q_scale, l, u, selected, xkn, out)
 
 
+def prox_step_group_batch_bang(Y, Q, XK, SJ, group_size, lam, sigma, q_scale, lam_scale=None, xkn=None, out=None):
+    """group_prox_step_bang of the plain operator (ShiftedGroupNormL2) for `batch` problems in ONE library call
+    (spx_proxstep_group_l2_batch, libspx_gbatch.so), every per-problem scalar read from DEVICE memory.  Row b of the batch × n
+    tensors Y, Q, XK, SJ (and xkn) is one problem of n / group_size uniform contiguous groups of group_size (1 .. 512) elements:
+    Y[b] = prox!(ψ_b, q_scale[b] .* Q[b], sigma[b]) with ψ_b = shifted(shifted(GroupNormL2(λ_b), XK[b]), SJ[b]), and
+
+        out[b, 0] = h  = Σ over the groups of λ_{b,g} · ‖((XK[b] + SJ[b]) + Y[b])[g]‖
+        out[b, 1] = qy = Σ over ALL i of Q[b, i] · Y[b, i]   -- with the UNSCALED Q as passed, not q_scale[b] · Q
+        out[b, 2] = yy = Σ over ALL i of Y[b, i]²
+        xkn[b, i] = (XK[b, i] + SJ[b, i]) + Y[b, i] (None: not stored)
+
+    lam: the group weights, a float64 device tensor -- 1-D of length ngroups (ONE weight vector shared by the problems) or 2-D
+    batch × ngroups with unit inner stride (its row stride is the library's ldl).  lam_scale: None, or a 1-D float64 device
+    tensor with one entry per problem: λ_{b,g} = lam_scale[b] · lam[.., g], ONE rounded multiply -- a λ path over shared
+    weights is `batch` scalars.  sigma, q_scale: 1-D float64 device tensors with one entry per problem.  The kernel reads all of
+    them, so a loop (or a captured graph) that updates them on the device needs no host round trip.
+    The 2-D tensors are float64 device tensors with unit inner stride and a common row stride (the library's ld >= n; the
+    elements between the rows are never touched).  out: a contiguous batch × 3 float64 device tensor (None: allocated).
+    Returns (Y, out); nothing is read back and the stream is not synchronised.  Y must not be Q; xkn must be none of the other
+    tensors.  Y[b] and xkn[b] have the bits of group_prox_step_bang on row b alone with the same scalars, on vectors of the
+    launch's alignment class (16-byte pairs when group_size and the row stride are even and every tensor is 16-byte aligned;
+    the element-wise form otherwise -- include/spx_gbatch.h)."""
+    _batch_matrix(Y, "Y")
+    for t, name in ((Q, "Q"), (XK, "XK"), (SJ, "SJ")):
+        _batch_matrix(t, name, like=Y)
+    if xkn is not None:
+        _batch_matrix(xkn, "xkn", like=Y)
+    if Y is Q:
+        raise TypeError("prox_step_group_batch: Y must not be Q (qy is taken with the Q that was passed)")
+    batch, n = Y.shape
+    if not (isinstance(group_size, numbers.Integral) and 1 <= group_size <= 512):
+        raise TypeError("group_size must be an integer in 1 .. 512 (larger groups: group_prox_step, one problem per call)")
+    group_size = int(group_size)
+    if n % group_size:
+        raise TypeError("n = %d is not a multiple of group_size = %d (uniform groups)" % (n, group_size))
+    ngroups = n // group_size
+    ld = Y.stride(0) if batch > 1 else max(n, 1)
+    if ld < n:
+        raise TypeError("the rows of Y overlap (row stride %d < n = %d)" % (ld, n))
+    if not (type(lam) is _Tensor and lam.is_cuda and lam.dtype == torch.float64 and lam.device == Y.device and lam.dim() in (1, 2)
+            and lam.shape[-1] == ngroups and (ngroups <= 1 or lam.stride(-1) == 1)):
+        raise TypeError("lam must be a float64 device tensor on Y's device with unit inner stride: ngroups (shared) or batch x ngroups")
+    if lam.dim() == 1:
+        ldl = 0
+    else:
+        if lam.shape[0] != batch:
+            raise TypeError("a 2-D lam has one row per problem (%d, got %d)" % (batch, lam.shape[0]))
+        ldl = lam.stride(0) if batch > 1 else max(ngroups, 1)
+        if ldl < ngroups:
+            raise TypeError("the rows of lam overlap (row stride %d < ngroups = %d)" % (ldl, ngroups))
+    for t, name in ((sigma, "sigma"), (q_scale, "q_scale")) + (((lam_scale, "lam_scale"),) if lam_scale is not None else ()):
+        _batch_params(t, name, batch, Y)
+    if out is None:
+        out = torch.empty((batch, 3), dtype=torch.float64, device=Y.device)
+    elif not (type(out) is _Tensor and out.is_cuda and out.dtype == torch.float64 and tuple(out.shape) == (batch, 3)
+              and out.is_contiguous() and out.device == Y.device):
+        raise TypeError("out must be a contiguous batch x 3 float64 device tensor on Y's device")
+    L = _lib.load_gbatch()
+    _lib.check(L.spx_proxstep_group_l2_batch(_ctx(Y.device), _ptr(Y), _ptr(Q), _ptr(XK), _ptr(SJ), group_size, ngroups, batch, ld,
+                                             _ptr(lam), ldl, _ptr(lam_scale), _ptr(sigma), _ptr(q_scale), _ptr(xkn), _ptr(out)))
+    return Y, out
+
+
+def prox_step_group_batch(Q, XK, SJ, group_size, lam, sigma, q_scale, lam_scale=None, xkn=None, out=None):
+    """prox_step_group_batch_bang into a new Y shaped and strided like Q: (Y, out); see prox_step_group_batch_bang"""
+    return prox_step_group_batch_bang(torch.empty_strided(Q.shape, Q.stride(), dtype=Q.dtype, device=Q.device), Q, XK, SJ, group_size,
+                                      lam, sigma, q_scale, lam_scale, xkn, out)
+
+
 def group_prox_step_bang(y, ψ, q, σ, q_scale=1.0, xkn=None, out=None):
     """prox_step_bang for the group operators, ShiftedGroupNormL2 and ShiftedGroupNormL2Binf (spx_proxstep_group_l2[_binf]):
     prox!(y, ψ, q_scale .* q, σ) and the step statistics of a trust-region iteration in one library call,
