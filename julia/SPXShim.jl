@@ -443,7 +443,44 @@ function prox_step_group_batch!(Y::DMat, Q::DMat, XK::DMat, SJ::DMat, group_size
 end
 
 # ---------------------------------------------------------------------------------------------
-# l1 norm + l2-ball trust region     src/shiftedNormL1B2.jl:50-67   (χ = NormL2(χ.lambda))
+# The same for the trust-region operator (ShiftedGroupNormL2Binf, spx_proxstep_group_l2_binf_batch; no counterpart in the
+# reference): `batch` TR problems in ONE call, every problem with its own radius.  Δ: a ROCVector{Float64} of length batch, read
+# by the kernel like σ and q_scale -- a loop that shrinks and grows the radii on the device needs no host round trip.  Everything
+# else as prox_step_group_batch!.  Column b of Y and xkn has the bits of group_prox_step! on that column alone (under tuning key
+# 9 of the context), on vectors of the launch's alignment class (include/spx_gbinf_batch.h).
+# (This binding has never been executed: there is no Julia toolchain where the library is built and tested.)
+# ---------------------------------------------------------------------------------------------
+const libspx_gbinf_batch = get(ENV, "LIBSPX_GBINF_BATCH", "libspx_gbinf_batch.so")   # include/spx_gbinf_batch.h: a fifth library, linked against libspx
+function prox_step_group_binf_batch!(Y::DMat, Q::DMat, XK::DMat, SJ::DMat, group_size::Integer, λ::Union{DVec, DMat}, σ::DVec,
+                                     Δ::DVec, q_scale::DVec; λ_scale::Union{Nothing, DVec} = nothing,
+                                     xkn::Union{Nothing, DMat} = nothing, out::DMat = ROCMatrix{Float64}(undef, 3, size(Y, 2)))
+  n, batch = size(Y)
+  (1 <= group_size <= 512 && n % group_size == 0) || throw(ArgumentError("uniform groups of 1 .. 512 elements"))
+  ngroups = n ÷ group_size
+  ld = batch > 1 ? stride(Y, 2) : max(n, 1)
+  for M in (Q, XK, SJ, xkn)
+    M === nothing && continue
+    (size(M) == (n, batch) && (batch <= 1 || stride(M, 2) == ld)) || throw(BoundsError())
+  end
+  ldl = 0
+  if λ isa DMat
+    size(λ) == (ngroups, batch) || throw(BoundsError())
+    ldl = batch > 1 ? stride(λ, 2) : max(ngroups, 1)
+  else
+    length(λ) == ngroups || throw(BoundsError())
+  end
+  (length(σ) == batch && length(Δ) == batch && length(q_scale) == batch && (λ_scale === nothing || length(λ_scale) == batch) &&
+   size(out) == (3, batch)) || throw(BoundsError())
+  check(ccall((:spx_proxstep_group_l2_binf_batch, libspx_gbinf_batch), Cint,
+              (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int64, Int64, Int64, Int64,
+               Ptr{Cdouble}, Int64, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+              ctx(), dptr(Y), dptr(Q), dptr(XK), dptr(SJ), group_size, ngroups, batch, ld, dptr(λ), ldl, dptr(λ_scale), dptr(σ),
+              dptr(Δ), dptr(q_scale), dptr(xkn), dptr(out)))
+  return Y, out
+end
+
+# ---------------------------------------------------------------------------------------------
+# l1 norm + l2-ball trust region    src/shiftedNormL1B2.jl:50-67   (χ = NormL2(χ.lambda))
 # ---------------------------------------------------------------------------------------------
 function prox!(y::DVec, ψ::ShiftedProximalOperators.ShiftedNormL1B2{Float64, <:DVec, <:DVec, <:DVec}, q::DVec, σ::Float64)
   n = length(ψ.xk)

@@ -128,6 +128,12 @@ GBATCH_SIGNATURES = {
     "spx_proxstep_group_l2_batch": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _i64, _p, _p, _p, _p, _p],
 }
 
+# libspx_gbinf_batch.so (include/spx_gbinf_batch.h): the batched Binf group call, a fifth library that links against libspx.so
+GBINF_BATCH_LIB_PATH = LIB_PATH[:-3] + "_gbinf_batch.so"
+GBINF_BATCH_SIGNATURES = {
+    "spx_proxstep_group_l2_binf_batch": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _i64, _p, _p, _p, _p, _p, _p],
+}
+
 
 class SpxError(RuntimeError):
     """A libspx call returned a non-zero spx_status."""
@@ -215,6 +221,26 @@ def load_gbatch():
             fn.restype = _int
         _gbatch = L
     return _gbatch
+
+
+_gbinf_batch = None
+
+
+def load_gbinf_batch():
+    """Load libspx_gbinf_batch.so (after libspx.so, whose contexts and error text it shares).  Raises if it is missing."""
+    global _gbinf_batch
+    if _gbinf_batch is None:
+        load()
+        if not os.path.exists(GBINF_BATCH_LIB_PATH):
+            raise ImportError("libspx_gbinf_batch.so not found at %s -- build it with shiftedproximaloperators.jl_amd/csrc/build.sh; "
+                              "there is no CPU fallback" % GBINF_BATCH_LIB_PATH)
+        L = ctypes.CDLL(GBINF_BATCH_LIB_PATH)
+        for name, args in GBINF_BATCH_SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.argtypes = args
+            fn.restype = _int
+        _gbinf_batch = L
+    return _gbinf_batch
 
 
 def check(status):

@@ -5,7 +5,8 @@
 # spx_batch.hip (the batched separable call, include/spx_batch.h) becomes a library of its own, lib/libspx_batch.so -- for
 # SPX_LIB_NAME=X.so: X_batch.so -- linked against the first one (found next to it: rpath $ORIGIN).  spx_ibatch.hip (the batched
 # iprox! call, include/spx_ibatch.h) becomes a third one in the same way: lib/libspx_ibatch.so, X_ibatch.so; spx_gbatch.hip (the
-# batched group call, include/spx_gbatch.h) a fourth: lib/libspx_gbatch.so, X_gbatch.so.
+# batched group call, include/spx_gbatch.h) a fourth: lib/libspx_gbatch.so, X_gbatch.so; spx_gbinf_batch.hip (the batched Binf
+# group call, include/spx_gbinf_batch.h) a fifth: lib/libspx_gbinf_batch.so, X_gbinf_batch.so.
 set -euo pipefail
 HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 ROOT="$(cd "$HERE/../.." && pwd)"
@@ -30,6 +31,8 @@ pids+=($!)
 pids+=($!)
 "$HIPCC" "${FLAGS[@]}" -c "$HERE/spx_gbatch.hip" -o "$OBJ/spx_gbatch.o" &
 pids+=($!)
+"$HIPCC" "${FLAGS[@]}" -c "$HERE/spx_gbinf_batch.hip" -o "$OBJ/spx_gbinf_batch.o" &
+pids+=($!)
 fail=0
 for p in "${pids[@]}"; do wait "$p" || fail=1; done
 [ "$fail" = 0 ] || { echo "compile failed" >&2; exit 1; }
@@ -47,4 +50,8 @@ GBATCH="${NAME%.so}_gbatch.so"
 "$HIPCC" --offload-arch=gfx950 -shared -fPIC -fvisibility=hidden "$OBJ/spx_gbatch.o" -L"$OUT" -l:"$NAME" '-Wl,-rpath,$ORIGIN' \
   -o "$OUT/$GBATCH.tmp"
 mv -f "$OUT/$GBATCH.tmp" "$OUT/$GBATCH"
+GBINF="${NAME%.so}_gbinf_batch.so"
+"$HIPCC" --offload-arch=gfx950 -shared -fPIC -fvisibility=hidden "$OBJ/spx_gbinf_batch.o" -L"$OUT" -l:"$NAME" '-Wl,-rpath,$ORIGIN' \
+  -o "$OUT/$GBINF.tmp"
+mv -f "$OUT/$GBINF.tmp" "$OUT/$GBINF"
 echo "built $OUT/$NAME"

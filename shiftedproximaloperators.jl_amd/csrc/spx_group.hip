@@ -922,21 +922,8 @@ struct GroupCall {
   double sigma, delta;
 };
 
-// Register tiles: GroupTile, GroupTiles and the plain operator's table GroupTilesPlain are spx_group_common.hpp's (the batched
-// call, spx_gbatch.hip, walks the same table).
-// Binf: as few lanes per group as the registers allow (4 x 4/8, 8 x 8/16, 16 x 16, 32 x 16 elements) -- the wave-uniform
-// scalar work of the root find, which every lane executes, is then shared by more groups per wave
-// Small groups (round 3): tiles that FIT -- a 4 x 4 tile spent four lanes' worth of root find (Binf) or reduction on a group
-// of two, and three quarters of its loads on padding.  us per call at n = 1.6e7, old -> new tile (tools/r3/binf_small_groups.py):
-// Binf groups of 2: 1305 -> 368, of 4: 680 -> 208, of 8: 317 -> 174, of 16: 155 -> 142; plain groups of 2: 508 -> 89, of 4:
-// 283 -> 92, of 8: 162 -> 90, of 10: 132 -> 107.  (One lane per group beyond 8 elements loses more to the 64-byte strides
-// between its lanes' loads than it saves: Binf 1 x 16 on groups of 16 270 us.)
-using GroupTilesBinf = GroupTiles<GroupTile<2, 1, 2>, GroupTile<4, 1, 4>, GroupTile<8, 1, 8>, GroupTile<16, 2, 8>, GroupTile<32, 4, 8>,
-                                  GroupTile<64, 8, 8>,  // (4 x 16 is slower here: 64-byte runs per group and load)
-                                  GroupTile<128, 8, 16>, GroupTile<256, 16, 16>, GroupTile<512, 32, 16>>;
-// The LIT launch of the Binf form (its own tiles, by the group size: the list is short, the literal evaluation wants lanes)
-using GroupTilesLit = GroupTiles<GroupTile<16, 4, 4>, GroupTile<32, 4, 8>, GroupTile<64, 8, 8>, GroupTile<128, 8, 16>,
-                                 GroupTile<256, 16, 16>, GroupTile<512, 32, 16>>;
+// Register tiles: GroupTile, GroupTiles and the tables GroupTilesPlain, GroupTilesBinf and GroupTilesLit are
+// spx_group_common.hpp's (the batched calls, spx_gbatch.hip and spx_gbinf_batch.hip, walk the same tables).
 
 // What the k_group_reg launches of a call share.
 struct GroupRegArgs {

@@ -2,9 +2,10 @@
 // group; spx_group_team.hip: a TEAM OF WORKGROUPS per group): team reductions, element providers, the Binf root find
 // (src/shiftedGroupNormL2Binf.jl:85-108) and the per-group body (src/shiftedGroupNormL2.jl:67-76, shiftedGroupNormL2Binf.jl:84-117).
 // k_csr_uncovered serves both precisions (spx_group.hip, spx_group_f32.hip); behind it, the register tiles (GroupTile, GroupTiles
-// and the plain operator's table GroupTilesPlain) and the plain operator's step site on such a tile (group_l2_step_site: the
-// batched call, spx_gbatch.hip), then the host's choice of the lanes per group for the kernels that take that width as a
-// template argument.
+// and the tables GroupTilesPlain, GroupTilesBinf, GroupTilesLit), the plain operator's step site on such a tile
+// (group_l2_step_site: the batched call, spx_gbatch.hip) and the Binf operator's, in two halves (group_l2_binf_step_site,
+// group_l2_binf_literal_site: the batched call, spx_gbinf_batch.hip), then the host's choice of the lanes per group for the
+// kernels that take that width as a template argument.
 #pragma once
 #include <cmath>
 #include <type_traits>
@@ -1017,7 +1018,7 @@ __global__ __launch_bounds__(256) void k_csr_uncovered(T* y, const T* xk, const 
 }
 
 // ---------------------------------------------------------------------------------------------
-// Register tiles (k_group_reg of spx_group.hip; k_group_batch of spx_gbatch.hip)
+// Register tiles (k_group_reg of spx_group.hip; k_group_batch of spx_gbatch.hip; k_binf_batch of spx_gbinf_batch.hip)
 // ---------------------------------------------------------------------------------------------
 // Register tiles.  A row GroupTile<MAXG, LPG, EPL> sends the group sizes (uniform, or the caller's bound on ragged sizes) up to
 // MAXG that no earlier row takes to LPG lanes per group x EPL elements per lane: the smallest tile that holds a group, partly
@@ -1053,6 +1054,30 @@ struct GroupTiles {
 };
 using GroupTilesPlain = GroupTiles<GroupTile<2, 1, 2>, GroupTile<4, 2, 4>, GroupTile<12, 4, 4>, GroupTile<32, 16, 2>, GroupTile<64, 16, 4>,
                                    GroupTile<128, 16, 8>, GroupTile<256, 32, 8>, GroupTile<384, 64, 6>, GroupTile<512, 64, 8>>;
+// Binf: as few lanes per group as the registers allow (4 x 4/8, 8 x 8/16, 16 x 16, 32 x 16 elements) -- the wave-uniform
+// scalar work of the root find, which every lane executes, is then shared by more groups per wave
+// Small groups (round 3): tiles that FIT -- a 4 x 4 tile spent four lanes' worth of root find (Binf) or reduction on a group
+// of two, and three quarters of its loads on padding.  us per call at n = 1.6e7, old -> new tile (tools/r3/binf_small_groups.py):
+// Binf groups of 2: 1305 -> 368, of 4: 680 -> 208, of 8: 317 -> 174, of 16: 155 -> 142; plain groups of 2: 508 -> 89, of 4:
+// 283 -> 92, of 8: 162 -> 90, of 10: 132 -> 107.  (One lane per group beyond 8 elements loses more to the 64-byte strides
+// between its lanes' loads than it saves: Binf 1 x 16 on groups of 16 270 us.)
+using GroupTilesBinf = GroupTiles<GroupTile<2, 1, 2>, GroupTile<4, 1, 4>, GroupTile<8, 1, 8>, GroupTile<16, 2, 8>, GroupTile<32, 4, 8>,
+                                  GroupTile<64, 8, 8>,  // (4 x 16 is slower here: 64-byte runs per group and load)
+                                  GroupTile<128, 8, 16>, GroupTile<256, 16, 16>, GroupTile<512, 32, 16>>;
+// The LIT launch of the Binf form (its own tiles, by the group size: the list is short, the literal evaluation wants lanes)
+using GroupTilesLit = GroupTiles<GroupTile<16, 4, 4>, GroupTile<32, 4, 8>, GroupTile<64, 8, 8>, GroupTile<128, 8, 16>,
+                                 GroupTile<256, 16, 16>, GroupTile<512, 32, 16>>;
+// the row of a table that takes size G, as a type (a kernel that names its second tile at compile time: spx_gbinf_batch.hip)
+template <int G, class... Rows>
+struct GroupTileFor { using type = void; };
+template <int G, class R, class... Rest>
+struct GroupTileFor<G, R, Rest...> {
+  using type = typename std::conditional<(G <= R::maxg), R, typename GroupTileFor<G, Rest...>::type>::type;
+};
+template <int G, class Tiles>
+struct GroupTileOf;
+template <int G, class... Rows>
+struct GroupTileOf<G, GroupTiles<Rows...>> { using type = typename GroupTileFor<G, Rows...>::type; };
 
 // ---------------------------------------------------------------------------------------------
 // The group site of the plain operator's step form (ShiftedGroupNormL2: prox!, xkn and the three step statistics of ONE
@@ -1184,6 +1209,194 @@ __device__ __forceinline__ GroupStepSums group_l2_step_site(GroupStepSums acc, d
     }
   }
   return acc;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The group site of the Binf operator's step form (ShiftedGroupNormL2Binf), as k_group_reg<.., BINF = true, .., VALUE, STEP>
+// states it inside its loop, in two halves (the batched call, spx_gbinf_batch.hip, runs them as two phases of one workgroup):
+//   group_l2_binf_step_site    : the main launch's site on the size's row of GroupTilesBinf -- load, S, X, XS, binf_root; on
+//                                BINF_ZERO / BINF_ROOT y, xkn and the three terms; on BINF_LITERAL nothing is stored or added and
+//                                the site returns true.  RegGroup's `live` slots as the main launch sets them on a partly
+//                                filled tile (on a full tile live == EPL: the statements of the FULL instantiation).
+//   group_l2_binf_literal_site : the LIT launch's site on the size's row of GroupTilesLit -- load with THAT tile's mapping,
+//                                binf_literal_reg, y, xkn and the three terms.
+// Arguments as group_l2_step_site, except that y, q, xk, sj and xkn (which may be NULL) are the vectors at the workgroup's first
+// element -- uniform, scalar registers -- and `base` is the group's first element behind them, a 32-bit offset in a lane's vector
+// register (64-bit lane offsets cost the 16-element tiles 16 to 40 spilled VGPRs).  The loads are direct (k_group_reg brings the one- and two-lane tiles in through LDS: other
+// instructions, the same values); q, which the kernel does not keep across the root find, is read again once y is stored, as
+// there.  tests/test_gpu_proxstep_group_binf_batch.py holds these statements and k_group_reg's together bit for bit.
+// ---------------------------------------------------------------------------------------------
+// the loads of either site: S = (qs q + xk) + sj, X = xk, XS = xk + sj; slots past the end of the group hold zeros
+template <int LPG, int EPL, bool PAIRS, class G>
+__device__ __forceinline__ void group_binf_load(G& grp, const double* q_, const double* xk_, const double* sj_, unsigned int base, int gs,
+                                                int j, double qs, bool cached) {
+  const double *q = q_ + base, *xk = xk_ + base, *sj = sj_ + base;
+  const int npairs = gs >> 1;
+  if constexpr (PAIRS) {
+    const f64x2* q2 = reinterpret_cast<const f64x2*>(q);
+    const f64x2* x2 = reinterpret_cast<const f64x2*>(xk);
+    const f64x2* s2 = reinterpret_cast<const f64x2*>(sj);
+    f64x2 vq[EPL / 2], vx[EPL / 2], vs[EPL / 2];
+#pragma unroll
+    for (int k = 0; k < EPL / 2; ++k) {
+      const int p = (k * LPG + j < npairs) ? (k * LPG + j) : 0;  // masked pairs re-read pair 0, zeroed below
+      if (cached) {
+        vq[k] = q2[p]; vx[k] = x2[p]; vs[k] = s2[p];
+      } else {
+        vq[k] = __builtin_nontemporal_load(q2 + p);
+        vx[k] = __builtin_nontemporal_load(x2 + p);
+        vs[k] = __builtin_nontemporal_load(s2 + p);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < EPL / 2; ++k) {
+      const bool in = (k * LPG + j) < npairs;
+      const f64x2 zero2 = f64x2{0.0, 0.0};
+      f64x2 a = in ? vq[k] : zero2;
+      const f64x2 b = in ? vx[k] : zero2, c = in ? vs[k] : zero2;
+      a.x = qs * a.x; a.y = qs * a.y;  // (rounded here: never contracted into the sum below)
+      grp.S[2 * k] = (a.x + b.x) + c.x;  // shiftedGroupNormL2Binf.jl:80
+      grp.S[2 * k + 1] = (a.y + b.y) + c.y;
+      grp.X[2 * k] = b.x;
+      grp.X[2 * k + 1] = b.y;
+      grp.XS[2 * k] = b.x + c.x;
+      grp.XS[2 * k + 1] = b.y + c.y;
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < EPL; ++k) {
+      const int e = k * LPG + j;
+      const bool in = e < gs;
+      const int i = in ? e : 0;
+      double a = in ? q[i] : 0.0;
+      const double b = in ? xk[i] : 0.0, c = in ? sj[i] : 0.0;
+      a = qs * a;
+      grp.S[k] = (a + b) + c;
+      grp.X[k] = b;
+      grp.XS[k] = b + c;
+    }
+  }
+}
+// what follows `out` (y of this lane's slots) at either site: the term lam ||v||, the stores of y and xkn, q read again, q y, y^2
+template <int LPG, int EPL, bool PAIRS>
+__device__ __forceinline__ GroupStepSums group_binf_finish(GroupStepSums acc, const double (&XS)[EPL], const double (&out)[EPL], double* y_,
+                                                           const double* q_, double* xkn_, unsigned int base, int gs, int j, bool valid,
+                                                           double lam, bool cached) {
+  const int npairs = gs >> 1;
+  double* const y = y_ + base;
+  const double* const q = q_ + base;
+  double* const xkn = xkn_ + base;  // (used behind xkn_ != nullptr only)
+  // v = (xk + sj) + y of the elements this lane is about to store; slots past the end of the group add nothing
+  double vv = 0.0;
+#pragma unroll
+  for (int k = 0; k < EPL; ++k) {
+    const bool in = PAIRS ? ((k >> 1) * LPG + j) < npairs : (k * LPG + j) < gs;
+    const double v = XS[k] + out[k];
+    vv += in ? v * v : 0.0;
+  }
+  vv = lanes_sum<LPG>(vv);
+  if (valid && j == 0) acc.h += lam * sqrt(vv);
+  if (valid) {
+    if constexpr (PAIRS) {
+      f64x2* y2 = reinterpret_cast<f64x2*>(y);
+      f64x2* v2 = reinterpret_cast<f64x2*>(xkn);
+#pragma unroll
+      for (int k = 0; k < EPL / 2; ++k)
+        if (k * LPG + j < npairs) {
+          const f64x2 o = f64x2{out[2 * k], out[2 * k + 1]};
+          if (cached) y2[k * LPG + j] = o;
+          else __builtin_nontemporal_store(o, y2 + k * LPG + j);
+        }
+      if (xkn_ != nullptr) {  // v as the h term formed it, stored the way y is
+#pragma unroll
+        for (int k = 0; k < EPL / 2; ++k)
+          if (k * LPG + j < npairs) {
+            const f64x2 v = f64x2{XS[2 * k] + out[2 * k], XS[2 * k + 1] + out[2 * k + 1]};
+            if (cached) v2[k * LPG + j] = v;
+            else __builtin_nontemporal_store(v, v2 + k * LPG + j);
+          }
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < EPL; ++k)
+        if (k * LPG + j < gs) y[k * LPG + j] = out[k];
+      if (xkn_ != nullptr) {
+#pragma unroll
+        for (int k = 0; k < EPL; ++k)
+          if (k * LPG + j < gs) xkn[k * LPG + j] = XS[k] + out[k];
+      }
+    }
+  }
+  asm volatile("" ::: "memory");  // (q is read AGAIN below: the values loaded above are not kept alive across the root find)
+  double qy = 0.0, yy = 0.0;
+  if constexpr (PAIRS) {
+    const f64x2* q2 = reinterpret_cast<const f64x2*>(q);
+#pragma unroll
+    for (int k = 0; k < EPL / 2; ++k) {
+      const bool in = (k * LPG + j) < npairs;
+      const int p = in ? (k * LPG + j) : 0;
+      f64x2 a;
+      if (cached) a = q2[p];
+      else a = __builtin_nontemporal_load(q2 + p);
+      qy += in ? a.x * out[2 * k] : 0.0;
+      qy += in ? a.y * out[2 * k + 1] : 0.0;
+      yy += in ? out[2 * k] * out[2 * k] : 0.0;
+      yy += in ? out[2 * k + 1] * out[2 * k + 1] : 0.0;
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < EPL; ++k) {
+      const bool in = (k * LPG + j) < gs;
+      const double a = q[in ? k * LPG + j : 0];
+      qy += in ? a * out[k] : 0.0;
+      yy += in ? out[k] * out[k] : 0.0;
+    }
+  }
+  if (valid) {
+    acc.qy += qy;
+    acc.yy += yy;
+  }
+  return acc;
+}
+template <int LPG, int EPL, bool PAIRS>
+__device__ __forceinline__ bool group_l2_binf_step_site(GroupStepSums& acc, double* y, const double* q, const double* xk, const double* sj,
+                                                        double* xkn, unsigned int base, int gs, int j, bool valid, double lam, double sigma,
+                                                        double delta, double qs, bool pole_lit, bool cached) {
+  static_assert((EPL % 2) == 0, "EPL must be even (16-byte pairs)");
+  RegGroup<EPL, true> grp;
+  {  // live slots of the tile (wave-uniform: the launch's group size)
+    const int slices = PAIRS ? ((gs >> 1) + LPG - 1) / LPG : ((gs + LPG - 1) / LPG + 1) / 2;
+    grp.live = (2 * slices < EPL) ? 2 * slices : EPL;
+  }
+  group_binf_load<LPG, EPL, PAIRS>(grp, q, xk, sj, base, gs, j, qs, cached);
+  double out[EPL];
+  double ru;
+  const int status = binf_root<LPG>(grp, lam, sigma, delta, nullptr, ru, pole_lit);
+  const double sl = lam * sigma;
+  const bool literal = status == BINF_LITERAL;  // (the lanes of a group agree: every decision is taken on the group's sums)
+  if (status != BINF_ROOT || ru == 0.0) {  // shiftedGroupNormL2Binf.jl:102-103, :107-108
+#pragma unroll
+    for (int k = 0; k < EPL; ++k) out[k] = 0.0 - grp.XS[k];
+  } else {
+    const double tau = ru * fast_rcp(sl + ru);  // = alpha at the root (:83 with ||w|| = n)
+#pragma unroll
+    for (int k = 0; k < EPL; ++k) out[k] = binf_y(grp.S[k], grp.X[k], tau, delta) - grp.XS[k];  // :110-116
+  }
+  acc = group_binf_finish<LPG, EPL, PAIRS>(acc, grp.XS, out, y, q, xkn, base, gs, j, valid && !literal, lam, cached);
+  return valid && literal;
+}
+template <int LPG, int EPL, bool PAIRS>
+__device__ __forceinline__ GroupStepSums group_l2_binf_literal_site(GroupStepSums acc, double* y, const double* q, const double* xk,
+                                                                    const double* sj, double* xkn, unsigned int base, int gs, int j, bool valid,
+                                                                    double lam, double sigma, double delta, double qs) {
+  static_assert((EPL % 2) == 0, "EPL must be even (16-byte pairs)");
+  RegGroup<EPL, false> grp;
+  group_binf_load<LPG, EPL, PAIRS>(grp, q, xk, sj, base, gs, j, qs, LPG <= 2);
+  double out[EPL];
+  binf_literal_reg<LPG, EPL, false>(grp, lam, sigma, delta, out);
+#pragma unroll
+  for (int k = 0; k < EPL; ++k) out[k] = out[k] - grp.XS[k];  // :116
+  return group_binf_finish<LPG, EPL, PAIRS>(acc, grp.XS, out, y, q, xkn, base, gs, j, valid, lam, LPG <= 2);
 }
 
 // ---------------------------------------------------------------------------------------------

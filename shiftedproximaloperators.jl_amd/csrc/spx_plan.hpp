@@ -1,6 +1,6 @@
 // spx_plan.hpp -- WHICH kernel runs, on WHICH grid, with WHICH workspace: the decisions of the calls whose kernels synchronise
 // inside one launch (top-r: spx_select.hip; ShiftedNormL1B2: spx_b2.hip; large groups on teams: spx_group_team.hip) and of the
-// batched separable calls (spx_batch.hip, spx_ibatch.hip) and the batched group call (spx_gbatch.hip), as plain functions of plain values.  No HIP include, no runtime call, no kernel, no spx_ctx: what a call would do at a given n,
+// batched separable calls (spx_batch.hip, spx_ibatch.hip) and the batched group calls (spx_gbatch.hip, spx_gbinf_batch.hip), as plain functions of plain values.  No HIP include, no runtime call, no kernel, no spx_ctx: what a call would do at a given n,
 // alignment, residency and tuning is computable -- and testable, tests/c/plan_driver.hip -- on a CPU.
 //
 // Residency comes in through `cap`: cap(kernel) returns what spx_resident_cap returns for that kernel (0 = it cannot run; the
@@ -455,4 +455,28 @@ inline GBatchPlan gbatch_plan(int64_t group_size, int lpg, int64_t ngroups, int6
   }
   p.ok = p.grid <= kBatchGridMax;
   return p;
+}
+
+// ---------------------------------------------------------------------------------------------
+// batched Binf group call (spx_proxstep_group_l2_binf_batch, spx_gbinf_batch.hip): gbatch_plan with the lanes per group of the
+// size's row of GroupTilesBinf.  A workgroup keeps one bit per group it owns -- group g of the workgroup's [g_lo, g_hi) is bit
+// (g - g_lo) & 63 of word (g - g_lo) >> 6 -- and sets it where the group wants the literal evaluation; a workgroup owns at most
+// kBatchRowMax groups (row form, groups of one element; a tile of the tiled form holds at most kBatchTile).  Behind one barrier
+// the workgroup walks the bitmap in a fixed order, which is all of this section: wave w takes the words w, w + kBinfWalkWaves,
+// ...; a word's set bits are served `slots` at a time (slots = 64 / lanes per group of the GroupTilesLit row), in ascending order:
+// pass p gives slot s the (p * slots + s)-th set bit.  Every set bit is visited once, and a wave meets its groups in ascending
+// order -- so the order in which a lane adds its terms depends on the row's own bits alone.
+// ---------------------------------------------------------------------------------------------
+constexpr int kBinfBitmapWords = (int)(kBatchRowMax / 64);  // 192 words, 1.5 KiB
+constexpr int kBinfWalkWaves = 4;                           // wavefronts of a workgroup
+SPX_PLAN_HD inline int binf_bitmap_words(int64_t groups) { return (int)((groups + 63) / 64); }
+// passes a word needs at `slots` groups a pass
+SPX_PLAN_HD inline int binf_walk_passes(unsigned long long word, int slots) {
+  return (__builtin_popcountll(word) + slots - 1) / slots;
+}
+// the bit (0 .. 63) that slot `slot` of pass `pass` serves, or -1 when the word has no such set bit
+SPX_PLAN_HD inline int binf_walk_bit(unsigned long long word, int slots, int pass, int slot) {
+  const int k = pass * slots + slot;
+  for (int i = 0; i < k && word != 0ull; ++i) word &= word - 1ull;  // drop the k lowest set bits
+  return word != 0ull ? __builtin_ctzll(word) : -1;
 }

@@ -976,6 +976,47 @@ def prox_step_batch(kind, Q, XK, SJ, lam, sigma, q_scale, l=None, u=None, select
                                 q_scale, l, u, selected, xkn, out)
 
 
+def _group_batch_call(who, Y, Q, XK, SJ, group_size, lam, params, lam_scale, xkn, out):
+    """The checks the batched group calls share (`who` names the caller in a message; params: the per-problem device tensors with
+    their names).  Returns (group_size, ngroups, batch, ld, ldl, out)."""
+    _batch_matrix(Y, "Y")
+    for t, name in ((Q, "Q"), (XK, "XK"), (SJ, "SJ")):
+        _batch_matrix(t, name, like=Y)
+    if xkn is not None:
+        _batch_matrix(xkn, "xkn", like=Y)
+    if Y is Q:
+        raise TypeError("%s: Y must not be Q (qy is taken with the Q that was passed)" % who)
+    batch, n = Y.shape
+    if not (isinstance(group_size, numbers.Integral) and 1 <= group_size <= 512):
+        raise TypeError("group_size must be an integer in 1 .. 512 (larger groups: group_prox_step, one problem per call)")
+    group_size = int(group_size)
+    if n % group_size:
+        raise TypeError("n = %d is not a multiple of group_size = %d (uniform groups)" % (n, group_size))
+    ngroups = n // group_size
+    ld = Y.stride(0) if batch > 1 else max(n, 1)
+    if ld < n:
+        raise TypeError("the rows of Y overlap (row stride %d < n = %d)" % (ld, n))
+    if not (type(lam) is _Tensor and lam.is_cuda and lam.dtype == torch.float64 and lam.device == Y.device and lam.dim() in (1, 2)
+            and lam.shape[-1] == ngroups and (ngroups <= 1 or lam.stride(-1) == 1)):
+        raise TypeError("lam must be a float64 device tensor on Y's device with unit inner stride: ngroups (shared) or batch x ngroups")
+    if lam.dim() == 1:
+        ldl = 0
+    else:
+        if lam.shape[0] != batch:
+            raise TypeError("a 2-D lam has one row per problem (%d, got %d)" % (batch, lam.shape[0]))
+        ldl = lam.stride(0) if batch > 1 else max(ngroups, 1)
+        if ldl < ngroups:
+            raise TypeError("the rows of lam overlap (row stride %d < ngroups = %d)" % (ldl, ngroups))
+    for t, name in params + (((lam_scale, "lam_scale"),) if lam_scale is not None else ()):
+        _batch_params(t, name, batch, Y)
+    if out is None:
+        out = torch.empty((batch, 3), dtype=torch.float64, device=Y.device)
+    elif not (type(out) is _Tensor and out.is_cuda and out.dtype == torch.float64 and tuple(out.shape) == (batch, 3)
+              and out.is_contiguous() and out.device == Y.device):
+        raise TypeError("out must be a contiguous batch x 3 float64 device tensor on Y's device")
+    return group_size, ngroups, batch, ld, ldl, out
+
+
 def prox_step_group_batch_bang(Y, Q, XK, SJ, group_size, lam, sigma, q_scale, lam_scale=None, xkn=None, out=None):
     """group_prox_step_bang of the plain operator (ShiftedGroupNormL2) for `batch` problems in ONE library call
     (spx_proxstep_group_l2_batch, libspx_gbatch.so), every per-problem scalar read from DEVICE memory.  Row b of the batch × n
@@ -998,41 +1039,8 @@ def prox_step_group_batch_bang(Y, Q, XK, SJ, group_size, lam, sigma, q_scale, la
     tensors.  Y[b] and xkn[b] have the bits of group_prox_step_bang on row b alone with the same scalars, on vectors of the
     launch's alignment class (16-byte pairs when group_size and the row stride are even and every tensor is 16-byte aligned;
     the element-wise form otherwise -- include/spx_gbatch.h)."""
-    _batch_matrix(Y, "Y")
-    for t, name in ((Q, "Q"), (XK, "XK"), (SJ, "SJ")):
-        _batch_matrix(t, name, like=Y)
-    if xkn is not None:
-        _batch_matrix(xkn, "xkn", like=Y)
-    if Y is Q:
-        raise TypeError("prox_step_group_batch: Y must not be Q (qy is taken with the Q that was passed)")
-    batch, n = Y.shape
-    if not (isinstance(group_size, numbers.Integral) and 1 <= group_size <= 512):
-        raise TypeError("group_size must be an integer in 1 .. 512 (larger groups: group_prox_step, one problem per call)")
-    group_size = int(group_size)
-    if n % group_size:
-        raise TypeError("n = %d is not a multiple of group_size = %d (uniform groups)" % (n, group_size))
-    ngroups = n // group_size
-    ld = Y.stride(0) if batch > 1 else max(n, 1)
-    if ld < n:
-        raise TypeError("the rows of Y overlap (row stride %d < n = %d)" % (ld, n))
-    if not (type(lam) is _Tensor and lam.is_cuda and lam.dtype == torch.float64 and lam.device == Y.device and lam.dim() in (1, 2)
-            and lam.shape[-1] == ngroups and (ngroups <= 1 or lam.stride(-1) == 1)):
-        raise TypeError("lam must be a float64 device tensor on Y's device with unit inner stride: ngroups (shared) or batch x ngroups")
-    if lam.dim() == 1:
-        ldl = 0
-    else:
-        if lam.shape[0] != batch:
-            raise TypeError("a 2-D lam has one row per problem (%d, got %d)" % (batch, lam.shape[0]))
-        ldl = lam.stride(0) if batch > 1 else max(ngroups, 1)
-        if ldl < ngroups:
-            raise TypeError("the rows of lam overlap (row stride %d < ngroups = %d)" % (ldl, ngroups))
-    for t, name in ((sigma, "sigma"), (q_scale, "q_scale")) + (((lam_scale, "lam_scale"),) if lam_scale is not None else ()):
-        _batch_params(t, name, batch, Y)
-    if out is None:
-        out = torch.empty((batch, 3), dtype=torch.float64, device=Y.device)
-    elif not (type(out) is _Tensor and out.is_cuda and out.dtype == torch.float64 and tuple(out.shape) == (batch, 3)
-              and out.is_contiguous() and out.device == Y.device):
-        raise TypeError("out must be a contiguous batch x 3 float64 device tensor on Y's device")
+    group_size, ngroups, batch, ld, ldl, out = _group_batch_call("prox_step_group_batch", Y, Q, XK, SJ, group_size, lam,
+                                                                 ((sigma, "sigma"), (q_scale, "q_scale")), lam_scale, xkn, out)
     L = _lib.load_gbatch()
     _lib.check(L.spx_proxstep_group_l2_batch(_ctx(Y.device), _ptr(Y), _ptr(Q), _ptr(XK), _ptr(SJ), group_size, ngroups, batch, ld,
                                              _ptr(lam), ldl, _ptr(lam_scale), _ptr(sigma), _ptr(q_scale), _ptr(xkn), _ptr(out)))
@@ -1043,6 +1051,31 @@ def prox_step_group_batch(Q, XK, SJ, group_size, lam, sigma, q_scale, lam_scale=
     """prox_step_group_batch_bang into a new Y shaped and strided like Q: (Y, out); see prox_step_group_batch_bang"""
     return prox_step_group_batch_bang(torch.empty_strided(Q.shape, Q.stride(), dtype=Q.dtype, device=Q.device), Q, XK, SJ, group_size,
                                       lam, sigma, q_scale, lam_scale, xkn, out)
+
+
+def prox_step_group_binf_batch_bang(Y, Q, XK, SJ, group_size, lam, sigma, delta, q_scale, lam_scale=None, xkn=None, out=None):
+    """prox_step_group_batch_bang for the trust-region operator (ShiftedGroupNormL2Binf) in ONE library call
+    (spx_proxstep_group_l2_binf_batch, libspx_gbinf_batch.so): Y[b] = prox!(ψ_b, q_scale[b] .* Q[b], sigma[b]) with
+    ψ_b = shifted(shifted(GroupNormL2(λ_b), XK[b], delta[b], NormLinf(1)), SJ[b]) -- the step of `batch` TR problems, each with its
+    own radius.  delta: a 1-D float64 device tensor with one entry per problem, read by the kernel like sigma and q_scale, so a
+    loop (or a captured graph) that shrinks and grows the radii on the device needs no host round trip.  Everything else --
+    layout, lam / lam_scale, out, xkn, the refusals -- as prox_step_group_batch_bang.  Y[b] and xkn[b] have the bits of
+    group_prox_step_bang on row b alone with the same scalars, under the context's tuning key 9, on vectors of the launch's
+    alignment class (include/spx_gbinf_batch.h)."""
+    group_size, ngroups, batch, ld, ldl, out = _group_batch_call("prox_step_group_binf_batch", Y, Q, XK, SJ, group_size, lam,
+                                                                 ((sigma, "sigma"), (delta, "delta"), (q_scale, "q_scale")), lam_scale,
+                                                                 xkn, out)
+    L = _lib.load_gbinf_batch()
+    _lib.check(L.spx_proxstep_group_l2_binf_batch(_ctx(Y.device), _ptr(Y), _ptr(Q), _ptr(XK), _ptr(SJ), group_size, ngroups, batch, ld,
+                                                  _ptr(lam), ldl, _ptr(lam_scale), _ptr(sigma), _ptr(delta), _ptr(q_scale), _ptr(xkn),
+                                                  _ptr(out)))
+    return Y, out
+
+
+def prox_step_group_binf_batch(Q, XK, SJ, group_size, lam, sigma, delta, q_scale, lam_scale=None, xkn=None, out=None):
+    """prox_step_group_binf_batch_bang into a new Y shaped and strided like Q: (Y, out); see prox_step_group_binf_batch_bang"""
+    return prox_step_group_binf_batch_bang(torch.empty_strided(Q.shape, Q.stride(), dtype=Q.dtype, device=Q.device), Q, XK, SJ,
+                                           group_size, lam, sigma, delta, q_scale, lam_scale, xkn, out)
 
 
 def group_prox_step_bang(y, ψ, q, σ, q_scale=1.0, xkn=None, out=None):
