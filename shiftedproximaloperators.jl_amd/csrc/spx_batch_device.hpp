@@ -9,8 +9,8 @@
 //   tiled form (larger n): workgroup (b, t) takes tile t of problem b and stores its partials to the workspace
 //              ([problem][plane][tile]); the reduce kernel, one workgroup per problem, adds them in a fixed order.
 // Which form, grid and workspace: batch_plan (spx_plan.hpp), a function of n alone as far as a problem's bits go.
-// (The batched group call, spx_gbatch.hip, has a kernel body and a host run of its own; it shares the workspace layout, the
-//  reduce -- batch_reduce_body -- and with_bool.)
+// (The batched group calls, spx_gbatch.hip and spx_gbinf_batch.hip, have kernel bodies of their own and a host run of their
+//  own, run_gbatch of spx_gbatch_device.hpp; they share the workspace layout, the reduce -- batch_reduce_body -- and with_bool.)
 // Alignment: all vectors share ld, so when their bases share bit 3 of the address every row is peeled by the kernel -- a head of
 // 0 or 1 elements (batch_row_map: the parity of b * ld), 16-byte pairs, a tail of 0 or 1 elements; bases of mixed alignment take
 // the element-wise instantiation (PAIRS = false).  The mask is shared by the problems and read by bytes.

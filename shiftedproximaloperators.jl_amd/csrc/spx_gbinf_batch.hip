@@ -3,7 +3,7 @@
 // links against libspx.so (the context, its workspace, the error text).  `batch` trust-region problems of ngroups uniform groups
 // in ONE launch, problem b at elements [b * ld, b * ld + n) of every vector; sigma[b], delta[b], q_scale[b] and the group weights
 // are read from device memory by the workgroup that stores y.  Which form, run, grid and workspace: gbatch_plan (spx_plan.hpp)
-// with the lanes per group of the size's row of GroupTilesBinf.
+// with the lanes per group of the size's row of GroupTilesBinf; the host run: run_gbatch (spx_gbatch_device.hpp).
 //   row form   : workgroup b owns problem b; one launch, no workspace.
 //   tiled form : workgroup (b, t) takes the groups gbatch_tile_groups(t) and stores three partials to batch_slot(b, plane, t);
 //                k_binf_batch_reduce, one workgroup per problem, adds them in a fixed order (batch_reduce_body).
@@ -18,8 +18,7 @@
 // Both phases add into the same per-lane sums; block_sum4 adds those and lane 0 stores the triple.  No workgroup waits for
 // another: no global atomics, no tickets, no count words, no list in memory, no second launch for the literal groups.
 #include "spx_gbinf_batch.h"
-#include "spx_group_common.hpp"
-#include "spx_batch_device.hpp"
+#include "spx_gbatch_device.hpp"
 
 namespace {
 // min waves/SIMD of the tiles of 8 elements per lane and fewer; 16 elements per lane: 2 (as k_group_reg, spx_group.hip)
@@ -128,6 +127,22 @@ __global__ __launch_bounds__(256, EPL >= 16 ? 2 : kBinfBatchWaves) void k_binf_b
 __global__ __launch_bounds__(256) void k_binf_batch_reduce(const double* partials, int64_t tiles, double* stats) {
   batch_reduce_body<kGBatchPlanes, false>(partials, tiles, nullptr, stats);
 }
+// what the host run (run_gbatch, spx_gbatch_device.hpp) takes from this call
+struct GroupBinfKind {
+  static constexpr const char* kLibName = "libspx_gbinf_batch.so";
+  using Tiles = GroupTilesBinf;
+  static constexpr bool kHasDelta = true;
+  static constexpr const char* kBadGroupSize = "group_size outside 1 .. 512 (larger groups: spx_proxstep_group_l2_binf, one problem per call)";
+  static constexpr const char* kNullParams = "a parameter array (lambda_vec, sigma, delta, q_scale) is NULL";
+  template <class Row, bool TILED, bool PAIRS>
+  static void launch(const GBatchCall& c, const GBatchPlan& p, double* out) {
+    static_assert(Row::lpg * Row::epl == Row::maxg, "k_binf_batch names its GroupTilesLit row by the main tile's capacity");
+    const GBinfArgs a{c.y, c.q, c.xk, c.sj, c.xkn, c.lambda_vec, c.lambda_scale, c.sigma, c.delta, c.q_scale, c.ngroups, c.ld, c.ldl, p.run,
+                      p.tiles_per_problem, (int)c.group_size, c.ctx->tune_binf_literal, out};
+    hipLaunchKernelGGL((k_binf_batch<Row::lpg, Row::epl, TILED, PAIRS>), dim3((unsigned)p.grid), dim3(256), 0, c.ctx->stream, a);
+  }
+  static constexpr auto kReduce = k_binf_batch_reduce;
+};
 }  // namespace
 
 SPX_EXPORT int spx_proxstep_group_l2_binf_batch(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj,
@@ -135,65 +150,6 @@ SPX_EXPORT int spx_proxstep_group_l2_binf_batch(spx_ctx* ctx, double* y, const d
                                                 const double* lambda_vec, int64_t ldl, const double* lambda_scale,
                                                 const double* sigma, const double* delta, const double* q_scale, double* xkn,
                                                 double* stats_dev) {
-  // the libraries share spx_ctx and four functions: refuse to touch a context of a libspx.so built from other sources
-  if (spx_shared_abi() != kSpxSharedAbi) {
-    spx_set_error("libspx_gbinf_batch.so and libspx.so do not match (shared layout %d, expected %d): rebuild both", spx_shared_abi(), kSpxSharedAbi);
-    return SPX_ERR_INTERNAL;
-  }
-  SPX_REQUIRE(ctx != nullptr, "ctx is NULL");
-  SPX_REQUIRE(group_size >= 1 && group_size <= kGroupRegMax,
-              "group_size outside 1 .. 512 (larger groups: spx_proxstep_group_l2_binf, one problem per call)");
-  SPX_REQUIRE(ngroups >= 0, "ngroups < 0");
-  SPX_REQUIRE(batch >= 0, "batch < 0");
-  SPX_REQUIRE(ngroups <= INT64_MAX / group_size, "ngroups * group_size overflows");
-  const int64_t n = ngroups * group_size;
-  if (batch == 0) return SPX_OK;
-  SPX_REQUIRE(stats_dev != nullptr, "stats_dev is NULL");
-  SPX_REQUIRE(ld >= n, "ld < n");
-  SPX_REQUIRE(ldl == 0 || ldl >= ngroups, "ldl is neither 0 (shared weights) nor >= ngroups");
-  const void* const in[4] = {y, q, xk, sj};
-  if (n > 0) {
-    SPX_REQUIRE(lambda_vec != nullptr && sigma != nullptr && delta != nullptr && q_scale != nullptr,
-                "a parameter array (lambda_vec, sigma, delta, q_scale) is NULL");
-    for (const void* v : in) SPX_REQUIRE(v != nullptr, "NULL vector with n > 0");
-    SPX_REQUIRE(y != q, kSpxYAliasesQ);
-    if (xkn != nullptr) {
-      for (const void* o : in) SPX_REQUIRE(xkn != o, "xkn is one of the other vectors");
-    }
-  }
-  int bits = spx_aligned16(xkn) ? 0 : 1 << 4;
-  for (int v = 0; v < 4; ++v) bits |= spx_aligned16(in[v]) ? 0 : 1 << v;
-  const int lpg = GroupTilesBinf::lpg(group_size);
-  const GBatchPlan p = gbatch_plan(group_size, lpg, ngroups, batch, ld, bits);
-  SPX_REQUIRE(p.ok, "the call needs more than 2^31 - 1 workgroups");
-  if (n == 0) {  // zeros for every problem, by a kernel
-    SPX_ON_DEVICE(ctx);
-    return spx_zero_async(ctx, stats_dev, (size_t)batch * kGBatchPlanes * sizeof(double));
-  }
-  const bool tiled = p.form == BatchForm::kTiled;
-  if (tiled) {
-    const int rcw = spx_ws_reserve(ctx, p.ws_bytes);
-    if (rcw) return rcw;
-  }
-  SPX_ON_DEVICE(ctx);
-  double* const out = tiled ? reinterpret_cast<double*>(ctx->ws) : stats_dev;
-  const GBinfArgs a{y, q, xk, sj, xkn, lambda_vec, lambda_scale, sigma, delta, q_scale, ngroups, ld, ldl, p.run, p.tiles_per_problem,
-                    (int)group_size, ctx->tune_binf_literal, out};
-  GroupTilesBinf::select(group_size, [&](auto row) {
-    constexpr int LPG = decltype(row)::lpg, EPL = decltype(row)::epl;
-    static_assert(LPG * EPL == decltype(row)::maxg, "k_binf_batch names its GroupTilesLit row by the main tile's capacity");
-    with_bool(tiled, [&](auto T) {
-      with_bool(p.pairs, [&](auto P) {
-        hipLaunchKernelGGL((k_binf_batch<LPG, EPL, decltype(T)::value, decltype(P)::value>), dim3((unsigned)p.grid), dim3(256), 0,
-                           ctx->stream, a);
-      });
-    });
-  });
-  SPX_LAUNCH_CHECK();
-  if (tiled) {
-    hipLaunchKernelGGL(k_binf_batch_reduce, dim3((unsigned)batch), dim3(256), 0, ctx->stream, (const double*)out, p.tiles_per_problem,
-                       stats_dev);
-    SPX_LAUNCH_CHECK();
-  }
-  return SPX_OK;
+  return run_gbatch<GroupBinfKind>({ctx, y, q, xk, sj, group_size, ngroups, batch, ld, lambda_vec, ldl, lambda_scale, sigma, delta, q_scale,
+                                    xkn, stats_dev});
 }
