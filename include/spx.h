@@ -271,6 +271,9 @@ int spx_obj_group_l2_binf_f32(spx_ctx* ctx, const float* y, const float* xk, con
  * feasibility scan: a prox result lies inside the box by construction).  The prox is taken at q_scale * q[i], formed on
  * the fly (R2's `mnu_grad .= -nu .* grad` without the extra pass; pass 1.0 for q itself; bit-identical to scaling q
  * beforehand).  Synchronous: *value is written on the host.
+ * MAGNITUDE RANGE (every entry point): data whose squares, products and sums stay finite and normal numbers are held to the
+ * reference at every scale -- whole problems at 2^+-500, Float32 at 2^+-60, tests/test_gpu_scales.py -- and beyond that the library
+ * computes sqrt(sum v^2) where the reference's LinearAlgebra.norm rescales (a norm whose squares overflow is Inf here).
  * NON-FINITE DATA (NaN, +-Inf, subnormals in q, xk or sj) -- the contract of every spx_proxval_* and spx_proxstep_* entry
  * point, the group forms and the ShiftedNormL1B2 forms below included (tests/test_gpu_nonfinite.py):
  *   y     : as spx_prox_X on the same data -- the same bits, NaN where that is NaN; xkn = (xk + sj) + y of that y.

@@ -29,7 +29,10 @@
  *   - Roots.jl `fzero(f, a, b)` (compat "^1.0.0", unpinned; Project.toml:17): bracketing
  *     bisection on Float64 run to floating-point exhaustion.  Restated as orc_bisect().
  *   - LinearAlgebra.norm: 2-norm; summation order unspecified (BLAS dnrm2 for long
- *     contiguous views).  Restated as a plain left-to-right sum of squares + sqrt.
+ *     contiguous views).  Restated as a plain left-to-right sum of squares + sqrt.  The
+ *     restatement is NOT overflow-safe (LinearAlgebra.norm rescales, this sum does not): it is
+ *     the reference's value only while every square and the sum are finite normal doubles, and
+ *     the scale tests (tests/scales.py) therefore stop at 2^+-500.
  *   - Base.sortperm!(p, y, rev=true, by=abs): stable.  Restated as a stable merge sort.
  *   - Base min/max on Float64: IEEE-754-2019 minimum/maximum (-0.0 < +0.0, NaN propagates).
  *   - Base complex acos/cos, real ^, cos, acos, sqrt: libm (glibc) here; ulp-level differences

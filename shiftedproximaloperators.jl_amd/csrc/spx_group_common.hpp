@@ -348,10 +348,16 @@ __device__ __forceinline__ void binf_ab(const G& grp, double tau, double delta, 
     sb = __builtin_fma(bm, bm, sb);
   });
   team_sum2<TEAM>(sa, sb, lds);
-  // keep_if leaves sub-2^-1042 residues of the masked-out terms in the sums: an empty set must sum to exactly 0 (the
-  // piece confirmation compares sums bit for bit, and sb == 0 identifies the all-inactive piece)
-  sa = (sa < 1e-300) ? 0.0 : sa;
-  sb = (sb < 1e-300) ? 0.0 : sb;
+  // An empty set must sum to exactly 0 (the piece confirmation compares sums bit for bit, and sb == 0 identifies the
+  // all-inactive piece).  The masked-out operands keep_if leaves are below 2^-1042; their squares, at most 2^-2084, are lost
+  // in the rounding of each fma, so the sums are exact zeros already and the cut below is a belt only: it is kept for a
+  // subnormal sum, whose terms have lost bits, and costs two compares per pass.  It sits at the smallest NORMAL double, so a
+  // set with one term that is a normal number sums to at least the cut at any scale of the data (an absolute 1e-300 took
+  // the groups of a problem at scale 2^-500, sums ~1e-300, for empty: DESIGN section 4).  An active term is b = X +- Delta:
+  // where |X| and Delta cancel, b^2 may underflow at such a scale although X^2 and Delta^2 do not -- out of the supported
+  // range like any square that is not a normal number (tests/scales.py states it for | |X| - Delta |).
+  sa = (sa < 0x1p-1022) ? 0.0 : sa;
+  sb = (sb < 0x1p-1022) ? 0.0 : sb;
 }
 
 // Register-resident groups: true in the lanes of a team whose active set {i : |tau S_i - X_i| > Delta} is the same at
