@@ -98,6 +98,13 @@ struct spx_ctx {
   const void* occ_fn[32] = {};
   int occ_blocks[32] = {};
   int nocc = 0;
+#ifdef SPX_TEST_HOOKS  // (last, and in test builds only: the product's layout and its kSpxSharedAbi are what they were)
+  int tune_ws_fill = 0;            // key 103: fill pattern of library-owned scratch (`ws` and `stage`): 0 off, 1 zero bytes, 2 the word
+                                   //          0x00000001, 3 0xFF bytes.  Setting it fills both blocks as they are; from then on every block
+                                   //          spx_ws_reserve or the staging allocator newly allocates is filled before the call's first launch
+  int tune_ws_trace = 0;           // key 104: every spx_ws_reserve call site and the staging allocator print one line to stdout per call:
+                                   //          "SPX_WS_SITE <file> <function> <line> <bytes>" (tests/test_gpu_ws_poison.py, tests/ws_sites.json)
+#endif
 };
 
 // codes of spx_ctx::status_host (bits)
@@ -114,6 +121,15 @@ constexpr int kSpxSharedAbi = kSpxSharedVersion * 65536 + (int)sizeof(spx_ctx);
 SPX_SHARED int spx_shared_abi();
 SPX_SHARED void spx_set_error(const char* fmt, ...);
 SPX_SHARED int spx_ws_reserve(spx_ctx* ctx, size_t bytes);
+#ifdef SPX_TEST_HOOKS
+// Test builds: every call site of spx_ws_reserve names itself (key 104) before it reserves; the staging allocator (spx_host.hip)
+// reports through spx_hook_trace and fills what it allocates through spx_hook_fill (key 103).  Nothing of this exists in the
+// product build.
+SPX_SHARED int spx_ws_reserve_at(spx_ctx* ctx, size_t bytes, const char* file, const char* func, int line);
+void spx_hook_trace(const spx_ctx* ctx, const char* file, const char* func, int line, size_t bytes);
+int spx_hook_fill(spx_ctx* ctx, void* ptr, size_t bytes);  // the pattern of key 103 over [ptr, ptr + bytes), by a kernel on the stream
+#define spx_ws_reserve(ctx, bytes) spx_ws_reserve_at((ctx), (bytes), __FILE__, __func__, __LINE__)
+#endif
 // spx_ctx::sync is there unless the context was created while its stream was being captured: then the first call that needs
 // it allocates it outside a capture and refuses inside one (SPX_ERR_INVALID_ARG, before anything is enqueued)
 int spx_sync_alloc(spx_ctx* ctx);

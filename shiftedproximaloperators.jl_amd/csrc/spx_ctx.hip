@@ -193,6 +193,15 @@ SPX_EXPORT int spx_ctx_set_tuning(spx_ctx* ctx, int key, int value) {
     case 100: if (value < 0 || value > 65535) break; ctx->tune_force_grid = value; return SPX_OK;
     case 101: if (value < 0 || value > 65535) break; ctx->tune_force_tail = value; return SPX_OK;
     case 102: if (value < 0 || value > 65535) break; ctx->tune_force_team = value; return SPX_OK;
+    case 103: {  // the fill pattern of library-owned scratch; a non-zero value fills what the context holds now
+      if (value < 0 || value > 3) break;
+      ctx->tune_ws_fill = value;
+      if (value == 0 || spx_capture_check(ctx)) return SPX_OK;  // (nothing is filled while the stream is being captured)
+      int rc = ctx->ws ? spx_hook_fill(ctx, ctx->ws, ctx->ws_bytes) : SPX_OK;
+      if (rc == SPX_OK && ctx->stage) rc = spx_hook_fill(ctx, ctx->stage, ctx->stage_bytes);
+      return rc;
+    }
+    case 104: ctx->tune_ws_trace = value ? 1 : 0; return SPX_OK;
 #endif
     default: break;
   }
@@ -318,9 +327,46 @@ int spx_require_not_capturing(spx_ctx* ctx, const char* what) {
   return SPX_ERR_INVALID_ARG;
 }
 
+#ifdef SPX_TEST_HOOKS
+// Key 103: 4-byte words of the pattern, the last (bytes % 4) bytes from the same word.  A kernel, like spx_zero_async.
+__global__ __launch_bounds__(256) void k_hook_fill(unsigned char* p, size_t bytes, unsigned int word) {
+  const size_t words = bytes / 4;
+  unsigned int* const w = reinterpret_cast<unsigned int*>(p);
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += (size_t)gridDim.x * blockDim.x) w[i] = word;
+  if (blockIdx.x == 0 && threadIdx.x < (bytes & 3u)) p[words * 4 + threadIdx.x] = (unsigned char)(word >> (8u * threadIdx.x));
+}
+int spx_hook_fill(spx_ctx* ctx, void* ptr, size_t bytes) {
+  if (ptr == nullptr || bytes == 0 || ctx->tune_ws_fill == 0) return SPX_OK;
+  SPX_REQUIRE((reinterpret_cast<uintptr_t>(ptr) & 3u) == 0, "spx_hook_fill: unaligned block");
+  SPX_ON_DEVICE_RAW(ctx);
+  const unsigned int word = ctx->tune_ws_fill == 1 ? 0u : ctx->tune_ws_fill == 2 ? 1u : 0xFFFFFFFFu;
+  size_t blocks = (bytes / 4 + 255) / 256;
+  if (blocks < 1) blocks = 1;
+  if (blocks > (size_t)ctx->num_cu * 8) blocks = (size_t)ctx->num_cu * 8;
+  hipLaunchKernelGGL(k_hook_fill, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, static_cast<unsigned char*>(ptr), bytes, word);
+  SPX_LAUNCH_CHECK();
+  return SPX_OK;
+}
+void spx_hook_trace(const spx_ctx* ctx, const char* file, const char* func, int line, size_t bytes) {
+  if (!ctx || !ctx->tune_ws_trace) return;
+  const char* base = file;
+  for (const char* c = file; *c; ++c)
+    if (*c == '/') base = c + 1;
+  std::printf("SPX_WS_SITE %s %s %d %zu\n", base, func, line, bytes);
+  std::fflush(stdout);
+}
+int spx_ws_reserve_at(spx_ctx* ctx, size_t bytes, const char* file, const char* func, int line) {
+  spx_hook_trace(ctx, file, func, line, bytes);
+  const bool grows = bytes > ctx->ws_bytes;
+  const int rc = (spx_ws_reserve)(ctx, bytes);  // (in parentheses: the function, not the macro over it)
+  if (rc != SPX_OK || !grows) return rc;
+  return spx_hook_fill(ctx, ctx->ws, ctx->ws_bytes);  // (growing refused a capture; the fill is ahead of the call's first launch)
+}
+#endif
+
 // Grows the context scratch.  Called from entry points BEFORE any launch of that call; growing
 // synchronises the stream (the old block may still be in use by earlier calls).
-int spx_ws_reserve(spx_ctx* ctx, size_t bytes) {
+int (spx_ws_reserve)(spx_ctx* ctx, size_t bytes) {  // (in parentheses: test builds put a macro of this name over the call sites)
   if (bytes <= ctx->ws_bytes) return SPX_OK;
   { const int rc = spx_require_not_capturing(ctx, "growing the workspace"); if (rc) return rc; }
   SPX_ON_DEVICE_RAW(ctx);

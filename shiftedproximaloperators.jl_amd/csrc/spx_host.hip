@@ -27,7 +27,11 @@ int stage_reserve(spx_ctx* ctx, size_t bytes) {
     return SPX_ERR_ALLOC;
   }
   ctx->stage_bytes = bytes;
+#ifdef SPX_TEST_HOOKS
+  return spx_hook_fill(ctx, ctx->stage, bytes);  // key 103: a new staging block is filled before the call's first copy
+#else
   return SPX_OK;
+#endif
 }
 
 // Copies `nin` host arrays (NULL / empty ones stay NULL) to the staging area and reserves `out_bytes` more for the
@@ -40,6 +44,9 @@ int stage_in(spx_ctx* ctx, const In (&in)[NIN], const void* (&dev)[NIN], size_t 
     if (in[i].host && in[i].bytes) total += aligned(in[i].bytes);
   int rc = spx_require_not_capturing(ctx, "a host-pointer call (it copies and synchronises)");
   if (rc) return rc;
+#ifdef SPX_TEST_HOOKS
+  spx_hook_trace(ctx, __FILE__, __func__, __LINE__, total ? total : kAlign);  // key 104: the staging allocator's one site
+#endif
   rc = stage_reserve(ctx, total ? total : kAlign);
   if (rc) return rc;
   SPX_ON_DEVICE(ctx);
