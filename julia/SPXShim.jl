@@ -480,6 +480,35 @@ function prox_step_group_binf_batch!(Y::DMat, Q::DMat, XK::DMat, SJ::DMat, group
 end
 
 # ---------------------------------------------------------------------------------------------
+# prox! + step statistics of ShiftedNormL1B2 for MANY problems in ONE call (spx_proxstep_l1_b2_batch; no counterpart in the
+# reference): column b of the n × batch matrices is one lasso problem inside its own l2 ball.  λ, σ, Δ, q_scale:
+# ROCVector{Float64}s of length batch, read by the one workgroup that owns the column -- a loop that shrinks and grows the radii
+# on the device needs no host round trip; χλ: one host number (χ.lambda, 1.0 in the reference).  n <= 2^20 (larger problems:
+# prox_step! on ShiftedNormL1B2, one problem per call).  Column b of Y meets the accuracy of that call (1e-12 on the scale
+# max(‖y‖, ‖xk‖)) and has its bits where the trust region is inactive; out[:, b] = (λ_b ‖xk + sj + y‖₁, Σ q .* y, Σ y .^ 2);
+# the bits of a column depend on n, the launch's alignment class and the column's own data only (include/spx_b2_batch.h).
+# (This binding has never been executed: there is no Julia toolchain where the library is built and tested.)
+# ---------------------------------------------------------------------------------------------
+const libspx_b2_batch = get(ENV, "LIBSPX_B2_BATCH", "libspx_b2_batch.so")   # include/spx_b2_batch.h: a sixth library, linked against libspx
+function prox_step_b2_batch!(Y::DMat, Q::DMat, XK::DMat, SJ::DMat, λ::DVec, σ::DVec, Δ::DVec, q_scale::DVec; χλ::Float64 = 1.0,
+                             xkn::Union{Nothing, DMat} = nothing, out::DMat = ROCMatrix{Float64}(undef, 3, size(Y, 2)))
+  n, batch = size(Y)
+  ld = batch > 1 ? stride(Y, 2) : max(n, 1)
+  for M in (Q, XK, SJ, xkn)
+    M === nothing && continue
+    (size(M) == (n, batch) && (batch <= 1 || stride(M, 2) == ld)) || throw(BoundsError())
+  end
+  (length(λ) == batch && length(σ) == batch && length(Δ) == batch && length(q_scale) == batch && size(out) == (3, batch)) ||
+    throw(BoundsError())
+  check(ccall((:spx_proxstep_l1_b2_batch, libspx_b2_batch), Cint,
+              (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int64, Int64, Int64,
+               Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}),
+              ctx(), dptr(Y), dptr(Q), dptr(XK), dptr(SJ), n, batch, ld, dptr(λ), dptr(σ), dptr(Δ), dptr(q_scale), χλ, dptr(xkn),
+              dptr(out)))
+  return Y, out
+end
+
+# ---------------------------------------------------------------------------------------------
 # l1 norm + l2-ball trust region    src/shiftedNormL1B2.jl:50-67   (χ = NormL2(χ.lambda))
 # ---------------------------------------------------------------------------------------------
 function prox!(y::DVec, ψ::ShiftedProximalOperators.ShiftedNormL1B2{Float64, <:DVec, <:DVec, <:DVec}, q::DVec, σ::Float64)

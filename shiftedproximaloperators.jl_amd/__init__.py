@@ -12,7 +12,7 @@ from .shifted import (ShiftedGroupNormL2, ShiftedGroupNormL2Binf, ShiftedIndBall
                       context, device_values,
                       group_prox_step, group_prox_step_bang, iprox, iprox_bang, iprox_step, iprox_step_bang,
                       iprox_step_batch, iprox_step_batch_bang, prox,
-                      prox_bang, prox_step, prox_step_bang, prox_step_batch, prox_step_batch_bang,
+                      prox_bang, prox_step, prox_step_b2_batch, prox_step_b2_batch_bang, prox_step_bang, prox_step_batch, prox_step_batch_bang,
                       prox_step_group_batch, prox_step_group_batch_bang, prox_step_group_binf_batch,
                       prox_step_group_binf_batch_bang, prox_value, prox_value_bang, set_bounds_bang, set_radius_bang, shift_bang, shifted, synchronize, value)
 

@@ -134,6 +134,12 @@ GBINF_BATCH_SIGNATURES = {
     "spx_proxstep_group_l2_binf_batch": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _i64, _p, _p, _p, _p, _p, _p],
 }
 
+# libspx_b2_batch.so (include/spx_b2_batch.h): the batched ShiftedNormL1B2 call, a sixth library that links against libspx.so
+B2_BATCH_LIB_PATH = LIB_PATH[:-3] + "_b2_batch.so"
+B2_BATCH_SIGNATURES = {
+    "spx_proxstep_l1_b2_batch": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _d, _p, _p],
+}
+
 
 class SpxError(RuntimeError):
     """A libspx call returned a non-zero spx_status."""
@@ -241,6 +247,26 @@ def load_gbinf_batch():
             fn.restype = _int
         _gbinf_batch = L
     return _gbinf_batch
+
+
+_b2_batch = None
+
+
+def load_b2_batch():
+    """Load libspx_b2_batch.so (after libspx.so, whose contexts and error text it shares).  Raises if it is missing."""
+    global _b2_batch
+    if _b2_batch is None:
+        load()
+        if not os.path.exists(B2_BATCH_LIB_PATH):
+            raise ImportError("libspx_b2_batch.so not found at %s -- build it with shiftedproximaloperators.jl_amd/csrc/build.sh; "
+                              "there is no CPU fallback" % B2_BATCH_LIB_PATH)
+        L = ctypes.CDLL(B2_BATCH_LIB_PATH)
+        for name, args in B2_BATCH_SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.argtypes = args
+            fn.restype = _int
+        _b2_batch = L
+    return _b2_batch
 
 
 def check(status):

@@ -6,7 +6,8 @@
 # SPX_LIB_NAME=X.so: X_batch.so -- linked against the first one (found next to it: rpath $ORIGIN).  spx_ibatch.hip (the batched
 # iprox! call, include/spx_ibatch.h) becomes a third one in the same way: lib/libspx_ibatch.so, X_ibatch.so; spx_gbatch.hip (the
 # batched group call, include/spx_gbatch.h) a fourth: lib/libspx_gbatch.so, X_gbatch.so; spx_gbinf_batch.hip (the batched Binf
-# group call, include/spx_gbinf_batch.h) a fifth: lib/libspx_gbinf_batch.so, X_gbinf_batch.so.
+# group call, include/spx_gbinf_batch.h) a fifth: lib/libspx_gbinf_batch.so, X_gbinf_batch.so; spx_b2_batch.hip (the batched
+# ShiftedNormL1B2 call, include/spx_b2_batch.h) a sixth: lib/libspx_b2_batch.so, X_b2_batch.so.
 set -euo pipefail
 HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 ROOT="$(cd "$HERE/../.." && pwd)"
@@ -33,6 +34,8 @@ pids+=($!)
 pids+=($!)
 "$HIPCC" "${FLAGS[@]}" -c "$HERE/spx_gbinf_batch.hip" -o "$OBJ/spx_gbinf_batch.o" &
 pids+=($!)
+"$HIPCC" "${FLAGS[@]}" -c "$HERE/spx_b2_batch.hip" -o "$OBJ/spx_b2_batch.o" &
+pids+=($!)
 fail=0
 for p in "${pids[@]}"; do wait "$p" || fail=1; done
 [ "$fail" = 0 ] || { echo "compile failed" >&2; exit 1; }
@@ -54,4 +57,8 @@ GBINF="${NAME%.so}_gbinf_batch.so"
 "$HIPCC" --offload-arch=gfx950 -shared -fPIC -fvisibility=hidden "$OBJ/spx_gbinf_batch.o" -L"$OUT" -l:"$NAME" '-Wl,-rpath,$ORIGIN' \
   -o "$OUT/$GBINF.tmp"
 mv -f "$OUT/$GBINF.tmp" "$OUT/$GBINF"
+B2BATCH="${NAME%.so}_b2_batch.so"
+"$HIPCC" --offload-arch=gfx950 -shared -fPIC -fvisibility=hidden "$OBJ/spx_b2_batch.o" -L"$OUT" -l:"$NAME" '-Wl,-rpath,$ORIGIN' \
+  -o "$OUT/$B2BATCH.tmp"
+mv -f "$OUT/$B2BATCH.tmp" "$OUT/$B2BATCH"
 echo "built $OUT/$NAME"

@@ -1,6 +1,7 @@
 // spx_plan.hpp -- WHICH kernel runs, on WHICH grid, with WHICH workspace: the decisions of the calls whose kernels synchronise
 // inside one launch (top-r: spx_select.hip; ShiftedNormL1B2: spx_b2.hip; large groups on teams: spx_group_team.hip) and of the
-// batched separable calls (spx_batch.hip, spx_ibatch.hip) and the batched group calls (spx_gbatch.hip, spx_gbinf_batch.hip), as plain functions of plain values.  No HIP include, no runtime call, no kernel, no spx_ctx: what a call would do at a given n,
+// batched separable calls (spx_batch.hip, spx_ibatch.hip), the batched group calls (spx_gbatch.hip, spx_gbinf_batch.hip) and the
+// batched ShiftedNormL1B2 call (spx_b2_batch.hip), as plain functions of plain values.  No HIP include, no runtime call, no kernel, no spx_ctx: what a call would do at a given n,
 // alignment, residency and tuning is computable -- and testable, tests/c/plan_driver.hip -- on a CPU.
 //
 // Residency comes in through `cap`: cap(kernel) returns what spx_resident_cap returns for that kernel (0 = it cannot run; the
@@ -479,4 +480,68 @@ SPX_PLAN_HD inline int binf_walk_bit(unsigned long long word, int slots, int pas
   const int k = pass * slots + slot;
   for (int i = 0; i < k && word != 0ull; ++i) word &= word - 1ull;  // drop the k lowest set bits
   return word != 0ull ? __builtin_ctzll(word) : -1;
+}
+
+// ---------------------------------------------------------------------------------------------
+// batched ShiftedNormL1B2 call (spx_proxstep_l1_b2_batch, spx_b2_batch.hip): `batch` problems of n elements, problem b at
+// elements [b * ld, b * ld + n) of every vector.  ONE workgroup owns a problem through its whole root iteration (spx_b2_row.hpp):
+// no workgroup waits for another, so there is no residency question and no workspace.
+//   row-resident (n <= kB2BatchRowMax): xk and the box ends of the row stay in registers across the reductions; lanes x elements
+//              per lane by n (kB2BatchTiles) -- a row of 1e3 takes 256 lanes, not a CU-wide workgroup.
+//   row walk   (kB2BatchRowMax < n <= kB2BatchNMax): kB2BatchWalkLanes lanes re-read the row once per reduction (from L2 or the
+//              Infinity Cache at these sizes).  Beyond kB2BatchNMax the call is refused: spx_proxstep_l1_b2 holds such a problem on
+//              chip across many CUs.
+// A lane owns the units u = k * lanes + t (k = 0, 1, ...); a unit is a 16-byte pair of elements (pairs) or one element
+// (element-wise).  Pairs: y, q, xk, sj all on a 16-byte boundary, ld even and n >= 2 -- every row then starts on one; a row of odd
+// n ends in a unit of one element.  Otherwise the element-wise form for the whole launch.  xkn takes no part in the choice:
+// where it sits 8 bytes off, only its stores drop to 8 bytes (xkn_pairs).
+// Form, tile and pairs are functions of n and the alignment class alone: a problem's bits do not depend on batch or on its row.
+// ---------------------------------------------------------------------------------------------
+constexpr int64_t kB2BatchRowMax = kB2RegBlock;          // 8192: 512 lanes x 16 elements, the tile of k_b2_coop<REG>
+constexpr int64_t kB2BatchNMax = (int64_t)1 << 20;
+constexpr int kB2BatchWalkLanes = 1024;
+constexpr int kB2BatchWalkUnroll = 4;                    // units a lane of the row walk has in flight
+struct B2BatchTile { int lanes, epl; };
+constexpr int kB2BatchTileCount = 4;
+constexpr B2BatchTile kB2BatchTiles[kB2BatchTileCount] = {{64, 4}, {256, 4}, {256, 16}, {kB2RegThreads, kB2Epl}};  // 256, 1024, 4096, 8192 elements
+enum class B2BatchForm { kResident, kWalk };
+enum class B2BatchRefusal { kNone, kNTooLarge, kBatchTooLarge };
+struct B2BatchPlan {
+  bool ok;
+  B2BatchRefusal why;  // !ok
+  B2BatchForm form;
+  int tile;            // kResident: the row of kB2BatchTiles
+  int lanes;           // of the workgroup
+  int epl;             // kResident: elements per lane held in registers
+  bool pairs;
+  bool xkn_pairs;      // xkn is stored by 16-byte pairs too
+  int64_t grid;        // = batch
+};
+SPX_PLAN_HD inline int b2_batch_unit_elems(bool pairs) { return pairs ? 2 : 1; }
+// units of a row: full ones and, in the pairs form with odd n, one of a single element behind them
+SPX_PLAN_HD inline int64_t b2_batch_units(int64_t n, bool pairs) { return pairs ? (n + 1) >> 1 : n; }
+// the unit that slot k of lane t owns
+SPX_PLAN_HD inline int64_t b2_batch_unit(int64_t k, int lanes, int t) { return k * lanes + t; }
+// base_alignment_bits: bit k set = vector k of y, q, xk, sj, xkn starts off a 16-byte boundary (an absent xkn: clear)
+inline B2BatchPlan b2_batch_plan(int64_t n, int64_t batch, int64_t ld, int base_alignment_bits) {
+  B2BatchPlan p{};
+  if (n > kB2BatchNMax) { p.why = B2BatchRefusal::kNTooLarge; return p; }
+  if (batch > kBatchGridMax) { p.why = B2BatchRefusal::kBatchTooLarge; return p; }
+  p.pairs = (base_alignment_bits & 15) == 0 && (ld & 1) == 0 && n >= 2;
+  p.xkn_pairs = p.pairs && (base_alignment_bits & 16) == 0;
+  if (n <= kB2BatchRowMax) {
+    p.form = B2BatchForm::kResident;
+    p.tile = 0;
+    while ((int64_t)kB2BatchTiles[p.tile].lanes * kB2BatchTiles[p.tile].epl < n) ++p.tile;
+    p.lanes = kB2BatchTiles[p.tile].lanes;
+    p.epl = kB2BatchTiles[p.tile].epl;
+  } else {
+    p.form = B2BatchForm::kWalk;
+    p.tile = -1;
+    p.lanes = kB2BatchWalkLanes;
+    p.epl = 0;
+  }
+  p.grid = batch;
+  p.ok = true;
+  return p;
 }

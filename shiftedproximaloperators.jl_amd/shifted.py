@@ -1078,6 +1078,58 @@ def prox_step_group_binf_batch(Q, XK, SJ, group_size, lam, sigma, delta, q_scale
                                            group_size, lam, sigma, delta, q_scale, lam_scale, xkn, out)
 
 
+def prox_step_b2_batch_bang(Y, Q, XK, SJ, lam, sigma, delta, q_scale, chi_lambda=1.0, xkn=None, out=None):
+    """b2_prox_step_bang (ShiftedNormL1B2: l1 inside an l2-ball trust region) for `batch` problems in ONE library call
+    (spx_proxstep_l1_b2_batch, libspx_b2_batch.so), every per-problem scalar read from DEVICE memory.  Row b of the batch × n
+    tensors Y, Q, XK, SJ (and xkn) is one problem: Y[b] = prox!(ψ_b, q_scale[b] .* Q[b], sigma[b]) with
+    ψ_b = shifted(shifted(NormL1(lam[b]), XK[b], delta[b], NormL2(chi_lambda)), SJ[b]), and
+
+        out[b, 0] = h  = lam[b] · Σ |(XK[b] + SJ[b]) + Y[b]|
+        out[b, 1] = qy = Σ over ALL i of Q[b, i] · Y[b, i]   -- with the UNSCALED Q as passed, not q_scale[b] · Q
+        out[b, 2] = yy = Σ over ALL i of Y[b, i]²
+        xkn[b, i] = (XK[b, i] + SJ[b, i]) + Y[b, i] (None: not stored)
+
+    lam, sigma, delta, q_scale: 1-D float64 device tensors with one entry per problem -- the kernel reads them, so a loop (or a
+    captured graph) that shrinks and grows the radii on the device needs no host round trip.  chi_lambda: one host number for
+    all problems (1.0 in the reference).  The 2-D tensors are float64 device tensors with unit inner stride and a common row
+    stride (the library's ld >= n; the elements between the rows are never touched); n <= 2^20 (larger problems:
+    b2_prox_step_bang, one problem per call).  out: a contiguous batch × 3 float64 device tensor (None: allocated).  Returns
+    (Y, out); nothing is read back and the stream is not synchronised.  Y must not be Q; xkn must be none of the other tensors.
+    One workgroup owns one problem: Y[b] meets the accuracy of b2_prox_step_bang (1e-12 on the scale max(‖y‖, ‖xk‖)) but not
+    its bits, except on rows whose trust region is inactive; the bits of a row depend on n, the launch's alignment class and
+    the row's own data alone, not on batch or on the row's place (include/spx_b2_batch.h)."""
+    _batch_matrix(Y, "Y")
+    for t, name in ((Q, "Q"), (XK, "XK"), (SJ, "SJ")):
+        _batch_matrix(t, name, like=Y)
+    if xkn is not None:
+        _batch_matrix(xkn, "xkn", like=Y)
+    if Y is Q:
+        raise TypeError("prox_step_b2_batch: Y must not be Q (qy is taken with the Q that was passed)")
+    batch, n = Y.shape
+    ld = Y.stride(0) if batch > 1 else max(n, 1)
+    if ld < n:
+        raise TypeError("the rows of Y overlap (row stride %d < n = %d)" % (ld, n))
+    for t, name in ((lam, "lam"), (sigma, "sigma"), (delta, "delta"), (q_scale, "q_scale")):
+        _batch_params(t, name, batch, Y)
+    if not _is_real(chi_lambda):
+        raise TypeError("chi_lambda is one real number for all problems")
+    if out is None:
+        out = torch.empty((batch, 3), dtype=torch.float64, device=Y.device)
+    elif not (type(out) is _Tensor and out.is_cuda and out.dtype == torch.float64 and tuple(out.shape) == (batch, 3)
+              and out.is_contiguous() and out.device == Y.device):
+        raise TypeError("out must be a contiguous batch x 3 float64 device tensor on Y's device")
+    L = _lib.load_b2_batch()
+    _lib.check(L.spx_proxstep_l1_b2_batch(_ctx(Y.device), _ptr(Y), _ptr(Q), _ptr(XK), _ptr(SJ), n, batch, ld, _ptr(lam), _ptr(sigma),
+                                          _ptr(delta), _ptr(q_scale), float(chi_lambda), _ptr(xkn), _ptr(out)))
+    return Y, out
+
+
+def prox_step_b2_batch(Q, XK, SJ, lam, sigma, delta, q_scale, chi_lambda=1.0, xkn=None, out=None):
+    """prox_step_b2_batch_bang into a new Y shaped and strided like Q: (Y, out); see prox_step_b2_batch_bang"""
+    return prox_step_b2_batch_bang(torch.empty_strided(Q.shape, Q.stride(), dtype=Q.dtype, device=Q.device), Q, XK, SJ, lam, sigma,
+                                   delta, q_scale, chi_lambda, xkn, out)
+
+
 def group_prox_step_bang(y, ψ, q, σ, q_scale=1.0, xkn=None, out=None):
     """prox_step_bang for the group operators, ShiftedGroupNormL2 and ShiftedGroupNormL2Binf (spx_proxstep_group_l2[_binf]):
     prox!(y, ψ, q_scale .* q, σ) and the step statistics of a trust-region iteration in one library call,

@@ -1,0 +1,119 @@
+"""CPU: the device-free parts of the batched ShiftedNormL1B2 call (spx_proxstep_l1_b2_batch) in a stand-alone program
+(tests/c/b2_batch_plan_driver.hip, its own main) built with AddressSanitizer + UBSan on the host side and run as a child.
+Nothing is put into LD_PRELOAD and the library is not loaded.
+
+(a) b2_batch_plan (csrc/spx_plan.hpp) over a grid of n, batch, ld and alignment bits: every element of every row is visited by
+    exactly one lane slot, the form is a function of n and the alignment class alone, refusals come at the grid and n bounds.
+(b) the step rule of csrc/spx_b2_row.hpp -- the one k_b2_batch runs -- on the host with plain sequential sums, on Gaussian,
+    integer-lattice and sparse rows with the trust region active, barely active (Delta = 0.9 ||xk||) and inactive: y against
+    oracle.prox_l1_b2 at the B2 bar, max |y - ref| <= 1e-12 max(||ref||, ||xk||), and the reductions a row needs stay under
+    the kernel's cap (printed: the maximum)."""
+import os
+import re
+import struct
+import subprocess
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+NS = (1, 2, 3, 7, 64, 1000, 4097, 8192, 12289)
+ENV = dict(ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
+
+
+@pytest.fixture(scope="module")
+def driver(tmp_path_factory):
+    if not os.path.exists(HIPCC):
+        pytest.skip("no hipcc")
+    exe = str(tmp_path_factory.mktemp("b2_batch_plan") / "b2_batch_plan_driver")
+    cmd = [HIPCC, "--offload-arch=gfx950", "--offload-host-only", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-Xarch_host",
+           "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined", "-I" + os.path.join(ROOT, "include"),
+           "-I" + os.path.join(ROOT, "shiftedproximaloperators.jl_amd", "csrc"),
+           os.path.join(ROOT, "tests", "c", "b2_batch_plan_driver.hip"), "-o", exe]
+    b = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert b.returncode == 0, b.stderr[-4000:]
+    return exe
+
+
+def _clean(r):
+    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-4000:]
+
+
+def test_b2_batch_plan_sanitized(driver):
+    r = subprocess.run([driver], env=dict(os.environ, **ENV), capture_output=True, text=True, timeout=600)
+    lines = r.stdout.split()
+    assert r.returncode == 0 and lines[-1:] == ["ok"], r.stdout[-2000:] + r.stderr[-4000:]
+    # the grid of cases is there: ~50 sizes x 7 batches x 4 paddings x 32 alignments, ten checks each
+    assert lines[1] == "checks" and int(lines[0]) > 300_000, r.stdout[-2000:]
+    _clean(r)
+
+
+def _rows():
+    """(name, q, xk, sj, lam, sigma, delta, q_scale): three kinds of data x NS x five (lambda, sigma, Delta) settings"""
+    rng = np.random.default_rng(20251021)
+    out = []
+    for n in NS:
+        for kind in ("gauss", "lattice", "sparse"):
+            if kind == "gauss":
+                q, xk, sj = rng.standard_normal(n), rng.standard_normal(n), 0.3 * rng.standard_normal(n)
+            elif kind == "lattice":
+                q, xk, sj = (rng.integers(-4, 5, n).astype(np.float64) for _ in range(3))
+                if not xk.any():
+                    xk[0] = 3.0
+            else:
+                keep = rng.random(n) < 0.1
+                keep[0] = True
+                q, sj = rng.standard_normal(n) * keep, 0.3 * rng.standard_normal(n) * (rng.random(n) < 0.1)
+                xk = rng.standard_normal(n) * keep
+                if xk[0] == 0.0:
+                    xk[0] = 1.0
+            nx = float(np.linalg.norm(xk))
+            for lam, sigma, qs, what in ((0.1, 1.0, 1.0, "active"), (1.0, 0.5, 0.7, "active"), (5.0, 1.0, 1.0, "barely"),
+                                         (0.1, 1.0, -1.3, "barely"), (1.0, 1.0, 1.0, "inactive")):
+                ls = lam * sigma
+                sq = sj + qs * q
+                chi0 = float(np.linalg.norm(np.minimum(np.maximum(-xk, sq - ls), sq + ls)))
+                delta = {"active": 0.3 * chi0 if chi0 > 0 else 1.0, "barely": 0.9 * nx, "inactive": 2.0 * chi0 + 1.0}[what]
+                out.append(("%s-%d-%s-%g" % (kind, n, what, lam), q, xk, sj, lam, sigma, delta, qs))
+    return out
+
+
+def test_b2_row_rule_on_the_host_against_the_oracle(driver, tmp_path):
+    from oracle import oracle
+    oracle.build()
+    rows = _rows()
+    fin, fout = str(tmp_path / "rows.bin"), str(tmp_path / "y.bin")
+    with open(fin, "wb") as f:
+        f.write(struct.pack("<q", len(rows)))
+        for _, q, xk, sj, lam, sigma, delta, qs in rows:
+            f.write(struct.pack("<q5d", len(q), lam, sigma, delta, qs, 1.0))
+            for v in (q, xk, sj):
+                f.write(np.ascontiguousarray(v, dtype="<f8").tobytes())
+    r = subprocess.run([driver, "rows", fin, fout], env=dict(os.environ, **ENV), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and r.stdout.split()[-1:] == ["ok"], r.stdout[-2000:] + r.stderr[-4000:]
+    _clean(r)
+    cap = int(re.search(r"^cap (\d+)$", r.stdout, flags=re.M).group(1))
+    printed = [int(m) for m in re.findall(r"^row \d+ n \d+ reductions (\d+)$", r.stdout, flags=re.M)]
+    assert len(printed) == len(rows)
+    blob = open(fout, "rb").read()
+    pos, worst, scaled_rows = 0, 0.0, 0
+    for k, (name, q, xk, sj, lam, sigma, delta, qs) in enumerate(rows):
+        n = len(q)
+        reds, = struct.unpack_from("<q", blob, pos)
+        y = np.frombuffer(blob, dtype="<f8", count=n, offset=pos + 8)
+        pos += 8 + 8 * n
+        assert reds == printed[k]
+        ref = oracle.prox_l1_b2(qs * q, xk, sj, lam, sigma, delta)
+        scale = max(float(np.linalg.norm(ref)), float(np.linalg.norm(xk)))
+        err = float(np.max(np.abs(y - ref))) / scale if scale > 0 else float(np.max(np.abs(y - ref)))
+        worst = max(worst, err)
+        assert err <= 1e-12, (name, err, reds)
+        if "inactive" in name:
+            assert reds == 1 and np.array_equal(y, ref), (name, reds)   # no sum decides an inactive row's bits
+        else:
+            scaled_rows += reds > 1
+    assert pos == len(blob)
+    assert scaled_rows > len(rows) // 3                                   # the active settings did run the iteration
+    print("reductions per row: max %d (cap %d); worst error on the B2 scale %.2e" % (max(printed), cap, worst))
+    assert max(printed) < cap                 # (the cap is for degenerate parameters: ordinary rows end far below it)

@@ -14,6 +14,6 @@ for line in sys.stdin:
 flt=sys.argv[1] if len(sys.argv)>1 else ''
 for r in rows:
     name=subprocess.run(['c++filt',r['name']],capture_output=True,text=True).stdout.strip()
-    name=re.sub(r'\(.*','',name)
+    name=re.sub(r'\(.*','',name.replace('(anonymous namespace)::',''))
     if flt in name: print('%-60s vgpr=%s sgpr=%s occ=%s spill=%s scratch=%s lds=%s'%(name[:60],r.get('vgpr'),r.get('sgpr'),r.get('occ'),r.get('spill'),r.get('scratch'),r.get('lds')))
 " "${2:-}"
