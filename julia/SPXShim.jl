@@ -509,6 +509,43 @@ function prox_step_b2_batch!(Y::DMat, Q::DMat, XK::DMat, SJ::DMat, λ::DVec, σ:
 end
 
 # ---------------------------------------------------------------------------------------------
+# prox! + step statistics of ShiftedIndBallL0 / ShiftedIndBallL0BInf for MANY problems in ONE call
+# (spx_proxstep_indball_l0_batch, spx_proxstep_indball_l0_binf_batch; no counterpart in the reference): column b of the n × batch
+# matrices is one top-r problem.  r: a ROCVector{Int64}, q_scale and Δ: ROCVector{Float64}s of length batch, read by the one
+# workgroup that owns the column -- a sparsity path, folds or multi-start need no host round trip.  Δ === nothing: the plain form.
+# n <= 2^20 (larger problems: prox! on ShiftedIndBallL0[BInf], one problem per call).  Column b of Y has the BITS of that prox! at
+# q_scale[b] .* Q[:, b]; out[:, b] = (count(!iszero, xk + sj + y), Σ q .* y, Σ y .^ 2): h of the new point is 0 iff out[1, b] <= r[b]
+# (include/spx_topr_batch.h).  Y must be none of Q, XK, SJ.
+# (This binding has never been executed: there is no Julia toolchain where the library is built and tested.)
+# ---------------------------------------------------------------------------------------------
+const libspx_topr_batch = get(ENV, "LIBSPX_TOPR_BATCH", "libspx_topr_batch.so")   # include/spx_topr_batch.h: a seventh library, linked against libspx
+function prox_step_topr_batch!(Y::DMat, Q::DMat, XK::DMat, SJ::DMat, r::ROCVector{Int64}, q_scale::DVec;
+                               Δ::Union{Nothing, DVec} = nothing, xkn::Union{Nothing, DMat} = nothing,
+                               out::DMat = ROCMatrix{Float64}(undef, 3, size(Y, 2)))
+  n, batch = size(Y)
+  ld = batch > 1 ? stride(Y, 2) : max(n, 1)
+  for M in (Q, XK, SJ, xkn)
+    M === nothing && continue
+    (size(M) == (n, batch) && (batch <= 1 || stride(M, 2) == ld)) || throw(BoundsError())
+  end
+  (length(r) == batch && length(q_scale) == batch && (Δ === nothing || length(Δ) == batch) && size(out) == (3, batch)) ||
+    throw(BoundsError())
+  rptr = Ptr{Int64}(UInt(pointer(r)))
+  if Δ === nothing
+    check(ccall((:spx_proxstep_indball_l0_batch, libspx_topr_batch), Cint,
+                (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int64, Int64, Int64,
+                 Ptr{Int64}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                ctx(), dptr(Y), dptr(Q), dptr(XK), dptr(SJ), n, batch, ld, rptr, dptr(q_scale), dptr(xkn), dptr(out)))
+  else
+    check(ccall((:spx_proxstep_indball_l0_binf_batch, libspx_topr_batch), Cint,
+                (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int64, Int64, Int64,
+                 Ptr{Int64}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                ctx(), dptr(Y), dptr(Q), dptr(XK), dptr(SJ), n, batch, ld, rptr, dptr(Δ), dptr(q_scale), dptr(xkn), dptr(out)))
+  end
+  return Y, out
+end
+
+# ---------------------------------------------------------------------------------------------
 # l1 norm + l2-ball trust region    src/shiftedNormL1B2.jl:50-67   (χ = NormL2(χ.lambda))
 # ---------------------------------------------------------------------------------------------
 function prox!(y::DVec, ψ::ShiftedProximalOperators.ShiftedNormL1B2{Float64, <:DVec, <:DVec, <:DVec}, q::DVec, σ::Float64)

@@ -14,6 +14,6 @@ from .shifted import (ShiftedGroupNormL2, ShiftedGroupNormL2Binf, ShiftedIndBall
                       iprox_step_batch, iprox_step_batch_bang, prox,
                       prox_bang, prox_step, prox_step_b2_batch, prox_step_b2_batch_bang, prox_step_bang, prox_step_batch, prox_step_batch_bang,
                       prox_step_group_batch, prox_step_group_batch_bang, prox_step_group_binf_batch,
-                      prox_step_group_binf_batch_bang, prox_value, prox_value_bang, set_bounds_bang, set_radius_bang, shift_bang, shifted, synchronize, value)
+                      prox_step_group_binf_batch_bang, prox_step_topr_batch, prox_step_topr_batch_bang, prox_value, prox_value_bang, set_bounds_bang, set_radius_bang, shift_bang, shifted, synchronize, value)
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -140,6 +140,13 @@ B2_BATCH_SIGNATURES = {
     "spx_proxstep_l1_b2_batch": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _d, _p, _p],
 }
 
+# libspx_topr_batch.so (include/spx_topr_batch.h): the batched top-r calls, a seventh library that links against libspx.so
+TOPR_BATCH_LIB_PATH = LIB_PATH[:-3] + "_topr_batch.so"
+TOPR_BATCH_SIGNATURES = {
+    "spx_proxstep_indball_l0_batch": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p],
+    "spx_proxstep_indball_l0_binf_batch": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p],
+}
+
 
 class SpxError(RuntimeError):
     """A libspx call returned a non-zero spx_status."""
@@ -267,6 +274,26 @@ def load_b2_batch():
             fn.restype = _int
         _b2_batch = L
     return _b2_batch
+
+
+_topr_batch = None
+
+
+def load_topr_batch():
+    """Load libspx_topr_batch.so (after libspx.so, whose contexts and error text it shares).  Raises if it is missing."""
+    global _topr_batch
+    if _topr_batch is None:
+        load()
+        if not os.path.exists(TOPR_BATCH_LIB_PATH):
+            raise ImportError("libspx_topr_batch.so not found at %s -- build it with shiftedproximaloperators.jl_amd/csrc/build.sh; "
+                              "there is no CPU fallback" % TOPR_BATCH_LIB_PATH)
+        L = ctypes.CDLL(TOPR_BATCH_LIB_PATH)
+        for name, args in TOPR_BATCH_SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.argtypes = args
+            fn.restype = _int
+        _topr_batch = L
+    return _topr_batch
 
 
 def check(status):

@@ -7,7 +7,8 @@
 # iprox! call, include/spx_ibatch.h) becomes a third one in the same way: lib/libspx_ibatch.so, X_ibatch.so; spx_gbatch.hip (the
 # batched group call, include/spx_gbatch.h) a fourth: lib/libspx_gbatch.so, X_gbatch.so; spx_gbinf_batch.hip (the batched Binf
 # group call, include/spx_gbinf_batch.h) a fifth: lib/libspx_gbinf_batch.so, X_gbinf_batch.so; spx_b2_batch.hip (the batched
-# ShiftedNormL1B2 call, include/spx_b2_batch.h) a sixth: lib/libspx_b2_batch.so, X_b2_batch.so.
+# ShiftedNormL1B2 call, include/spx_b2_batch.h) a sixth: lib/libspx_b2_batch.so, X_b2_batch.so; spx_topr_batch.hip (the batched
+# top-r calls, include/spx_topr_batch.h) a seventh: lib/libspx_topr_batch.so, X_topr_batch.so.
 set -euo pipefail
 HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 ROOT="$(cd "$HERE/../.." && pwd)"
@@ -36,6 +37,8 @@ pids+=($!)
 pids+=($!)
 "$HIPCC" "${FLAGS[@]}" -c "$HERE/spx_b2_batch.hip" -o "$OBJ/spx_b2_batch.o" &
 pids+=($!)
+"$HIPCC" "${FLAGS[@]}" -c "$HERE/spx_topr_batch.hip" -o "$OBJ/spx_topr_batch.o" &
+pids+=($!)
 fail=0
 for p in "${pids[@]}"; do wait "$p" || fail=1; done
 [ "$fail" = 0 ] || { echo "compile failed" >&2; exit 1; }
@@ -61,4 +64,8 @@ B2BATCH="${NAME%.so}_b2_batch.so"
 "$HIPCC" --offload-arch=gfx950 -shared -fPIC -fvisibility=hidden "$OBJ/spx_b2_batch.o" -L"$OUT" -l:"$NAME" '-Wl,-rpath,$ORIGIN' \
   -o "$OUT/$B2BATCH.tmp"
 mv -f "$OUT/$B2BATCH.tmp" "$OUT/$B2BATCH"
+TOPRBATCH="${NAME%.so}_topr_batch.so"
+"$HIPCC" --offload-arch=gfx950 -shared -fPIC -fvisibility=hidden "$OBJ/spx_topr_batch.o" -L"$OUT" -l:"$NAME" '-Wl,-rpath,$ORIGIN' \
+  -o "$OUT/$TOPRBATCH.tmp"
+mv -f "$OUT/$TOPRBATCH.tmp" "$OUT/$TOPRBATCH"
 echo "built $OUT/$NAME"

@@ -1,7 +1,7 @@
 // spx_plan.hpp -- WHICH kernel runs, on WHICH grid, with WHICH workspace: the decisions of the calls whose kernels synchronise
 // inside one launch (top-r: spx_select.hip; ShiftedNormL1B2: spx_b2.hip; large groups on teams: spx_group_team.hip) and of the
 // batched separable calls (spx_batch.hip, spx_ibatch.hip), the batched group calls (spx_gbatch.hip, spx_gbinf_batch.hip) and the
-// batched ShiftedNormL1B2 call (spx_b2_batch.hip), as plain functions of plain values.  No HIP include, no runtime call, no kernel, no spx_ctx: what a call would do at a given n,
+// batched ShiftedNormL1B2 call (spx_b2_batch.hip) and the batched top-r calls (spx_topr_batch.hip), as plain functions of plain values.  No HIP include, no runtime call, no kernel, no spx_ctx: what a call would do at a given n,
 // alignment, residency and tuning is computable -- and testable, tests/c/plan_driver.hip -- on a CPU.
 //
 // Residency comes in through `cap`: cap(kernel) returns what spx_resident_cap returns for that kernel (0 = it cannot run; the
@@ -539,6 +539,69 @@ inline B2BatchPlan b2_batch_plan(int64_t n, int64_t batch, int64_t ld, int base_
     p.form = B2BatchForm::kWalk;
     p.tile = -1;
     p.lanes = kB2BatchWalkLanes;
+    p.epl = 0;
+  }
+  p.grid = batch;
+  p.ok = true;
+  return p;
+}
+
+// ---------------------------------------------------------------------------------------------
+// batched top-r calls (spx_proxstep_indball_l0[_binf]_batch, spx_topr_batch.hip): `batch` problems of n elements, problem b at
+// elements [b * ld, b * ld + n) of every vector.  ONE workgroup owns a problem through its whole selection (spx_topr_row.hpp):
+// no workgroup waits for another, so there is no residency question and no workspace.
+//   row-resident (n <= kToprBatchRowMax): v, xk + sj and q of the row stay in registers across the digit passes; lanes x elements
+//              per lane by n (kToprBatchTiles) -- a row of 1e3 takes 256 lanes, not a CU-wide workgroup.
+//   row walk   (kToprBatchRowMax < n <= kToprBatchNMax): kToprBatchWalkLanes lanes park v in the row of y and re-read it once per
+//              digit (from L2 or the Infinity Cache at these sizes).  Beyond kToprBatchNMax the call is refused:
+//              spx_prox_indball_l0[_binf] spreads such a problem over many CUs.
+// A lane owns the units u = k * lanes + t (k = 0, 1, ...) in EVERY pass; a unit is a 16-byte pair of elements (pairs) or one
+// element (element-wise).  Pairs: y, q, xk, sj all on a 16-byte boundary, ld even and n >= 2 -- every row then starts on one; a
+// row of odd n ends in a unit of one element.  Otherwise the element-wise form for the whole launch.  xkn takes no part in the
+// choice: where it sits 8 bytes off, only its stores drop to 8 bytes (xkn_pairs).
+// Form, tile and pairs are functions of n and the alignment class alone: a problem's bits do not depend on batch or on its row.
+// ---------------------------------------------------------------------------------------------
+constexpr int64_t kToprBatchRowMax = 8192;               // 512 lanes x 16 elements
+constexpr int64_t kToprBatchNMax = (int64_t)1 << 20;
+constexpr int kToprBatchWalkLanes = 1024;
+constexpr int kToprBatchWalkUnroll = 4;                  // units a lane of the row walk has in flight
+struct ToprBatchTile { int lanes, epl; };
+constexpr int kToprBatchTileCount = 4;
+constexpr ToprBatchTile kToprBatchTiles[kToprBatchTileCount] = {{64, 4}, {256, 4}, {256, 16}, {512, 16}};  // 256, 1024, 4096, 8192 elements
+enum class ToprBatchForm { kResident, kWalk };
+enum class ToprBatchRefusal { kNone, kNTooLarge, kBatchTooLarge };
+struct ToprBatchPlan {
+  bool ok;
+  ToprBatchRefusal why;  // !ok
+  ToprBatchForm form;
+  int tile;              // kResident: the row of kToprBatchTiles; -1 on the walk
+  int lanes;             // of the workgroup
+  int epl;               // kResident: elements per lane held in registers; 0 on the walk
+  bool pairs;
+  bool xkn_pairs;        // xkn is stored by 16-byte pairs too
+  int64_t grid;          // = batch
+};
+// units of a row: full ones and, in the pairs form with odd n, one of a single element behind them
+SPX_PLAN_HD inline int64_t topr_batch_units(int64_t n, bool pairs) { return pairs ? (n + 1) >> 1 : n; }
+// the unit that slot k of lane t owns
+SPX_PLAN_HD inline int64_t topr_batch_unit(int64_t k, int lanes, int t) { return k * lanes + t; }
+// base_alignment_bits: bit k set = vector k of y, q, xk, sj, xkn starts off a 16-byte boundary (an absent xkn: clear)
+inline ToprBatchPlan topr_batch_plan(int64_t n, int64_t batch, int64_t ld, int base_alignment_bits) {
+  ToprBatchPlan p{};
+  if (n > kToprBatchNMax) { p.why = ToprBatchRefusal::kNTooLarge; return p; }
+  if (batch > kBatchGridMax) { p.why = ToprBatchRefusal::kBatchTooLarge; return p; }
+  p.pairs = (base_alignment_bits & 15) == 0 && (ld & 1) == 0 && n >= 2;
+  p.xkn_pairs = p.pairs && (base_alignment_bits & 16) == 0;
+  if (n <= kToprBatchRowMax) {
+    p.form = ToprBatchForm::kResident;
+    p.tile = 0;
+    while ((int64_t)kToprBatchTiles[p.tile].lanes * kToprBatchTiles[p.tile].epl < n) ++p.tile;
+    p.lanes = kToprBatchTiles[p.tile].lanes;
+    p.epl = kToprBatchTiles[p.tile].epl;
+  } else {
+    p.form = ToprBatchForm::kWalk;
+    p.tile = -1;
+    p.lanes = kToprBatchWalkLanes;
     p.epl = 0;
   }
   p.grid = batch;

@@ -1130,6 +1130,68 @@ def prox_step_b2_batch(Q, XK, SJ, lam, sigma, delta, q_scale, chi_lambda=1.0, xk
                                    delta, q_scale, chi_lambda, xkn, out)
 
 
+def prox_step_topr_batch_bang(Y, Q, XK, SJ, r, q_scale, delta=None, xkn=None, out=None):
+    """prox! + step statistics of the top-r operators, ShiftedIndBallL0 (delta=None) and ShiftedIndBallL0BInf (delta given), for
+    `batch` problems in ONE library call (spx_proxstep_indball_l0_batch / spx_proxstep_indball_l0_binf_batch,
+    libspx_topr_batch.so), every per-problem parameter read from DEVICE memory.  Row b of the batch × n tensors Y, Q, XK, SJ (and
+    xkn) is one problem: Y[b] = prox!(ψ_b, q_scale[b] .* Q[b], σ) with ψ_b = shifted(shifted(IndBallL0(r[b]), XK[b][, delta[b],
+    NormLinf(1)]), SJ[b]) -- the r[b] entries of (XK[b] + SJ[b]) + q_scale[b] Q[b] largest in magnitude kept (ties to the lowest
+    index, NaN above Inf), the others zeroed, XK[b] + SJ[b] subtracted, then clamped to ±delta[b] -- and
+
+        out[b, 0] = the NUMBER of i with (XK[b, i] + SJ[b, i]) + Y[b, i] != 0, exact; h of the new point is 0 iff it is <= r[b]
+                    and +Inf otherwise (with delta the new point can miss the ball: a dropped entry is clamp(-(xk + sj), ±delta))
+        out[b, 1] = qy = Σ over ALL i of Q[b, i] · Y[b, i]   -- with the UNSCALED Q as passed, not q_scale[b] · Q
+        out[b, 2] = yy = Σ over ALL i of Y[b, i]²
+        xkn[b, i] = (XK[b, i] + SJ[b, i]) + Y[b, i] (None: not stored)
+
+    r: a 1-D int64 DEVICE tensor, q_scale and delta: 1-D float64 device tensors, one entry per problem -- the kernel reads them,
+    so a loop (or a captured graph) that walks r or the radii on the device needs no host round trip.  r[b] <= 0 keeps nothing,
+    r[b] >= n everything.  The 2-D tensors are float64 device tensors with unit inner stride and a common row stride (the
+    library's ld >= n; the elements between the rows are never touched); n <= 2^20 (larger problems: prox_bang, one problem per
+    call).  out: a contiguous batch × 3 float64 device tensor (None: allocated).  Returns (Y, out); nothing is read back and the
+    stream is not synchronised.  Y must be none of Q, XK, SJ (the rows of Y hold intermediate values above n = 8192); xkn must
+    be none of the other tensors.  One workgroup owns one problem and the selection is exact: Y[b] has the BITS of prox_bang on
+    that row, in every form and at every alignment; the sums depend on n and the launch's alignment class alone, not on batch
+    or on the row's place (include/spx_topr_batch.h)."""
+    _batch_matrix(Y, "Y")
+    for t, name in ((Q, "Q"), (XK, "XK"), (SJ, "SJ")):
+        _batch_matrix(t, name, like=Y)
+        if Y is t:
+            raise TypeError("prox_step_topr_batch: Y must not be %s (qy is taken with the Q that was passed, and the rows of Y hold "
+                            "intermediate values)" % name)
+    if xkn is not None:
+        _batch_matrix(xkn, "xkn", like=Y)
+    batch, n = Y.shape
+    ld = Y.stride(0) if batch > 1 else max(n, 1)
+    if ld < n:
+        raise TypeError("the rows of Y overlap (row stride %d < n = %d)" % (ld, n))
+    if not (type(r) is _Tensor and r.is_cuda and r.dtype == torch.int64 and r.dim() == 1 and r.numel() == batch
+            and (batch <= 1 or r.stride(0) == 1) and r.device == Y.device):
+        raise TypeError("r must be a contiguous 1-D int64 device tensor with one entry per problem (%d) on Y's device" % batch)
+    _batch_params(q_scale, "q_scale", batch, Y)
+    if delta is not None:
+        _batch_params(delta, "delta", batch, Y)
+    if out is None:
+        out = torch.empty((batch, 3), dtype=torch.float64, device=Y.device)
+    elif not (type(out) is _Tensor and out.is_cuda and out.dtype == torch.float64 and tuple(out.shape) == (batch, 3)
+              and out.is_contiguous() and out.device == Y.device):
+        raise TypeError("out must be a contiguous batch x 3 float64 device tensor on Y's device")
+    L = _lib.load_topr_batch()
+    if delta is None:
+        _lib.check(L.spx_proxstep_indball_l0_batch(_ctx(Y.device), _ptr(Y), _ptr(Q), _ptr(XK), _ptr(SJ), n, batch, ld, _ptr(r),
+                                                   _ptr(q_scale), _ptr(xkn), _ptr(out)))
+    else:
+        _lib.check(L.spx_proxstep_indball_l0_binf_batch(_ctx(Y.device), _ptr(Y), _ptr(Q), _ptr(XK), _ptr(SJ), n, batch, ld, _ptr(r),
+                                                        _ptr(delta), _ptr(q_scale), _ptr(xkn), _ptr(out)))
+    return Y, out
+
+
+def prox_step_topr_batch(Q, XK, SJ, r, q_scale, delta=None, xkn=None, out=None):
+    """prox_step_topr_batch_bang into a new Y shaped and strided like Q: (Y, out); see prox_step_topr_batch_bang"""
+    return prox_step_topr_batch_bang(torch.empty_strided(Q.shape, Q.stride(), dtype=Q.dtype, device=Q.device), Q, XK, SJ, r, q_scale,
+                                     delta, xkn, out)
+
+
 def group_prox_step_bang(y, ψ, q, σ, q_scale=1.0, xkn=None, out=None):
     """prox_step_bang for the group operators, ShiftedGroupNormL2 and ShiftedGroupNormL2Binf (spx_proxstep_group_l2[_binf]):
     prox!(y, ψ, q_scale .* q, σ) and the step statistics of a trust-region iteration in one library call,

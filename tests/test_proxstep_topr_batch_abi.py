@@ -1,0 +1,150 @@
+"""CPU: the batched top-r prox! + step statistics entry points (spx_proxstep_indball_l0_batch, spx_proxstep_indball_l0_binf_batch)
+exist at every layer that can be looked at without a GPU -- include/spx_topr_batch.h (a header of its own: the calls live in
+libspx_topr_batch.so, the seventh library next to libspx.so) compiles as C99 and as C++11 on its own, declares the calls and
+states their contract, libspx_topr_batch.so exports them (and no other library does), links against libspx.so and does not ask
+for spx_ws_reserve, the ctypes table (TOPR_BATCH_SIGNATURES) binds exactly the declared set with the three integers by value and
+pointers elsewhere, the ABI version is unchanged, and the mirror takes r as an int64 device tensor and delta and q_scale as
+float64 device tensors: anything else is refused."""
+import ctypes
+import inspect
+import os
+import re
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PLAIN, BINF = "spx_proxstep_indball_l0_batch", "spx_proxstep_indball_l0_binf_batch"
+HEAD = ["spx_ctx* ctx", "double* y", "const double* q", "const double* xk", "const double* sj", "int64_t n", "int64_t batch",
+        "int64_t ld", "const int64_t* r"]
+ARGS = {PLAIN: HEAD + ["const double* q_scale", "double* xkn", "double* stats_dev"],
+        BINF: HEAD + ["const double* delta", "const double* q_scale", "double* xkn", "double* stats_dev"]}
+I64_BY_VALUE = [5, 6, 7]
+HEADER = os.path.join(ROOT, "include", "spx_topr_batch.h")
+
+
+@pytest.fixture(scope="module")
+def built():
+    import __graft_entry__ as ge
+    ge.build()
+    import spx_amd
+    return spx_amd
+
+
+def _header_text():
+    return open(HEADER).read()
+
+
+def _header_declarations(path=HEADER):
+    txt = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
+    return {m.group(1): m.group(2) for m in re.finditer(r"\bint\s+(spx_[a-z0-9_]+)\s*\(([^;]*?)\)\s*;", txt, flags=re.S)}
+
+
+def test_header_is_plain_c_and_cxx():
+    if shutil.which("gcc"):
+        subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-fsyntax-only", "-x", "c", HEADER])
+    if shutil.which("g++"):
+        subprocess.check_call(["g++", "-std=c++11", "-Wall", "-Werror", "-fsyntax-only", "-x", "c++", HEADER])
+
+
+def test_header_is_additive_and_includes_spx_h():
+    assert '#include "spx.h"' in _header_text()
+    assert sorted(_header_declarations()) == sorted(ARGS)
+
+
+@pytest.mark.parametrize("name", [PLAIN, BINF])
+def test_header_declares_the_calls(name):
+    args = [" ".join(a.split()) for a in _header_declarations()[name].split(",")]
+    assert args == ARGS[name], args
+    # the single call's vectors under their names, r and delta as device arrays, plus batch, ld, q_scale, xkn and stats_dev
+    single = _header_declarations(os.path.join(ROOT, "include", "spx.h"))[name.replace("proxstep", "prox").replace("_batch", "")]
+    names = lambda decl: [a.split()[-1].lstrip("*") for a in decl.split(",")]
+    assert sorted(names(_header_declarations()[name])) == sorted(names(single) + ["batch", "ld", "q_scale", "xkn", "stats_dev"])
+    assert names(_header_declarations()[name])[:6] == names(single)[:6]
+
+
+def test_header_states_the_contract():
+    txt = " ".join(re.sub(r"\n \*", "\n", _header_text()).split())   # (the comment's line breaks and their stars dropped)
+    for word in ("ALIGNMENT CLASS", "16-byte pairs form when ld is even", "element-wise form for EVERY row", "ONE rounded multiply",
+                 "r, delta, q_scale : DEVICE int64_t[batch], double[batch], double[batch]", "r[b] <= 0 keeps nothing",
+                 "r[b] >= n keeps everything", "has the BITS of spx_prox_indball_l0[_binf]", "ties to the lowest index first",
+                 "all NaNs one key above Inf", "exact (a NaN counts as nonzero)", "0 iff stats_dev[3 b] <= r[b]",
+                 "the count is what the caller cannot recover from h", "q AS PASSED", "fixed order", "batch-of-1",
+                 "workspace: NONE", "capturable cold", "n > 2^20", "spx_prox_indball_l0[_binf] spreads such a problem",
+                 "2^31 - 1", "no memset node", "fixed cap of passes", "y equal to q, xk or sj",
+                 "a NULL r, delta, q_scale or stats_dev", "only its stores drop to 8 bytes", "touches that row's y and sums only"):
+        assert word in txt, word
+    # the sentence of spx.h about the missing single step form stays as it is
+    spx_h = " ".join(re.sub(r"\n \*", "\n", open(os.path.join(ROOT, "include", "spx.h")).read()).split())
+    assert "no top-r form (its h is 0 at any prox result)" in spx_h
+
+
+def test_library_exports_the_calls(built):
+    lib = built._lib.load_topr_batch()
+    assert os.path.basename(built._lib.TOPR_BATCH_LIB_PATH) == "libspx_topr_batch.so"
+    # built and found as the other batch libraries are: next to libspx.so, named after it
+    assert built._lib.TOPR_BATCH_LIB_PATH == built._lib.LIB_PATH[:-3] + "_topr_batch.so"
+    for name in ARGS:
+        assert hasattr(lib, name)
+        for other in (ctypes.CDLL(built._lib.LIB_PATH), built._lib.load_batch(), built._lib.load_ibatch(), built._lib.load_gbatch(),
+                      built._lib.load_gbinf_batch(), built._lib.load_b2_batch()):
+            assert not hasattr(other, name)                  # the new entry points live in the seventh library only
+        assert not hasattr(lib, "spx_host_" + name[4:])      # no host-pointer twin
+    core = ctypes.CDLL(built._lib.LIB_PATH)
+    core.spx_abi_version.restype = ctypes.c_int
+    assert core.spx_abi_version() == 1                       # the change is additive
+
+
+def test_library_links_against_libspx_and_reserves_no_workspace(built):
+    if not shutil.which("readelf") or not shutil.which("nm"):
+        pytest.skip("no binutils")
+    dyn = subprocess.run(["readelf", "-d", built._lib.TOPR_BATCH_LIB_PATH], check=True, capture_output=True, text=True).stdout
+    assert re.search(r"NEEDED.*\[%s\]" % re.escape(os.path.basename(built._lib.LIB_PATH)), dyn), dyn
+    assert re.search(r"R(UN)?PATH.*\$ORIGIN", dyn), dyn
+    undefined = subprocess.run(["nm", "-D", "--undefined-only", built._lib.TOPR_BATCH_LIB_PATH], check=True, capture_output=True,
+                               text=True).stdout
+    assert "spx_set_error" in undefined and "spx_zero_async" in undefined   # what it takes from libspx.so ...
+    assert "spx_ws_reserve" not in undefined                                # ... and what it does not: workspace NONE
+    src = open(os.path.join(ROOT, "shiftedproximaloperators.jl_amd", "csrc", "spx_topr_batch.hip")).read()
+    assert "spx_ws_reserve(" not in src and "hipMemsetAsync" not in src and "ctx->sync" not in src
+
+
+def test_ctypes_table_binds_the_calls(built):
+    sig = built._lib.TOPR_BATCH_SIGNATURES
+    assert sorted(sig) == sorted(_header_declarations())      # the table binds exactly the declared set
+    for name, args in ARGS.items():
+        assert len(sig[name]) == len(args), sig[name]
+        for k, t in enumerate(sig[name]):
+            assert t is (ctypes.c_int64 if k in I64_BY_VALUE else ctypes.c_void_p), (name, k, t)
+        assert [k for k, a in enumerate(args) if a.startswith("int64_t")] == I64_BY_VALUE
+        fn = getattr(built._lib.load_topr_batch(), name)
+        assert list(fn.argtypes) == sig[name] and fn.restype is ctypes.c_int
+
+
+def test_build_knows_the_seventh_library():
+    src = open(os.path.join(ROOT, "__graft_entry__.py")).read()
+    assert "spx_topr_batch.h" in src and "_topr_batch.so" in src and "load_topr_batch()" in src
+    sh = open(os.path.join(ROOT, "shiftedproximaloperators.jl_amd", "csrc", "build.sh")).read()
+    assert sh.count("spx_topr_batch") >= 3 and "_topr_batch.so" in sh
+
+
+def test_mirror_takes_the_parameters_per_problem_on_the_device(built):
+    import torch
+    for f in (built.prox_step_topr_batch_bang, built.prox_step_topr_batch):
+        names = list(inspect.signature(f).parameters)
+        assert names[-5:] == ["r", "q_scale", "delta", "xkn", "out"], names
+        assert inspect.signature(f).parameters["delta"].default is None
+    assert list(inspect.signature(built.prox_step_topr_batch_bang).parameters)[:4] == ["Y", "Q", "XK", "SJ"]
+    src = inspect.getsource(built.prox_step_topr_batch_bang)
+    assert "_batch_matrix(" in src and "_batch_params(" in src and "torch.int64" in src
+    like = torch.zeros(3, 8, dtype=torch.float64)
+    # the call itself refuses what it can see before it looks for a device: host tensors, Y among the inputs
+    with pytest.raises(TypeError):
+        built.prox_step_topr_batch_bang(like.clone(), like, like, like, torch.ones(3, dtype=torch.int64),
+                                        torch.ones(3, dtype=torch.float64))
+    doc = built.prox_step_topr_batch_bang.__doc__
+    for word in ("delta", "ShiftedIndBallL0BInf", "spx_proxstep_indball_l0_binf_batch", "alignment class", "DEVICE", "int64", "BITS",
+                 "2^20"):
+        assert word in doc, word
+    assert "prox_step_topr_batch" in built.__all__ and "prox_step_topr_batch_bang" in built.__all__
