@@ -546,6 +546,53 @@ function prox_step_topr_batch!(Y::DMat, Q::DMat, XK::DMat, SJ::DMat, r::ROCVecto
 end
 
 # ---------------------------------------------------------------------------------------------
+# prox! + step statistics of ShiftedRootNormLhalf / ShiftedRootNormLhalfBox for MANY problems in ONE call
+# (spx_proxstep_lhalf_batch, spx_proxstep_lhalf_box_batch; no counterpart in the reference): the arguments and the layout of
+# prox_step_batch! above -- column b of the n × batch matrices is one problem, λ, σ, q_scale (and l, u) are ROCVector{Float64}s of
+# length batch read by the kernel, `selected` is ONE byte mask shared by the problems, out[:, b] = (λ_b Σ √|xk + sj + y|, Σ q .* y,
+# Σ y .^ 2).  Box form (l and u given): column b of Y has the BITS of prox_step! on that column.  Unboxed form: the same except
+# for an element whose |q_scale q + (xk + sj)| lies between the host's threshold 54^(1/3) (2σλ)^(2/3) / 4 and the device's (4 ulps
+# apart at most), which has the other branch of the prox's jump (include/spx_lhalf_batch.h); lhalf_threshold_batch! returns the
+# device's thresholds.
+# (These bindings have never been executed: there is no Julia toolchain where the library is built and tested.)
+# ---------------------------------------------------------------------------------------------
+const libspx_lhalf_batch = get(ENV, "LIBSPX_LHALF_BATCH", "libspx_lhalf_batch.so")   # include/spx_lhalf_batch.h: an eighth library, linked against libspx
+function prox_step_lhalf_batch!(Y::DMat, Q::DMat, XK::DMat, SJ::DMat, λ::DVec, σ::DVec, q_scale::DVec;
+                                l::Union{Nothing, DVec} = nothing, u::Union{Nothing, DVec} = nothing,
+                                selected::Union{Nothing, ROCVector{UInt8}} = nothing, xkn::Union{Nothing, DMat} = nothing,
+                                out::DMat = ROCMatrix{Float64}(undef, 3, size(Y, 2)))
+  n, batch = size(Y)
+  ld = batch > 1 ? stride(Y, 2) : max(n, 1)
+  for M in (Q, XK, SJ, xkn)
+    M === nothing && continue
+    (size(M) == (n, batch) && (batch <= 1 || stride(M, 2) == ld)) || throw(BoundsError())
+  end
+  (length(λ) == batch && length(σ) == batch && length(q_scale) == batch && size(out) == (3, batch)) || throw(BoundsError())
+  (l === nothing) == (u === nothing) || throw(ArgumentError("l and u are given together"))
+  if l === nothing
+    selected === nothing || throw(ArgumentError("selected needs the box form"))
+    check(ccall((:spx_proxstep_lhalf_batch, libspx_lhalf_batch), Cint,
+                (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int64, Int64, Int64,
+                 Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                ctx(), dptr(Y), dptr(Q), dptr(XK), dptr(SJ), n, batch, ld, dptr(λ), dptr(σ), dptr(q_scale), dptr(xkn), dptr(out)))
+  else
+    (length(l) == batch && length(u) == batch && (selected === nothing || length(selected) == n)) || throw(BoundsError())
+    check(ccall((:spx_proxstep_lhalf_box_batch, libspx_lhalf_batch), Cint,
+                (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int64, Int64, Int64,
+                 Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{UInt8}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                ctx(), dptr(Y), dptr(Q), dptr(XK), dptr(SJ), n, batch, ld, dptr(λ), dptr(σ), dptr(l), dptr(u), mptr(selected),
+                dptr(q_scale), dptr(xkn), dptr(out)))
+  end
+  return Y, out
+end
+function lhalf_threshold_batch!(p::DVec, λ::DVec, σ::DVec)
+  (length(λ) == length(p) && length(σ) == length(p)) || throw(BoundsError())
+  check(ccall((:spx_lhalf_threshold_batch, libspx_lhalf_batch), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Int64, Ptr{Cdouble}),
+              ctx(), dptr(λ), dptr(σ), length(p), dptr(p)))
+  return p
+end
+
+# ---------------------------------------------------------------------------------------------
 # l1 norm + l2-ball trust region    src/shiftedNormL1B2.jl:50-67   (χ = NormL2(χ.lambda))
 # ---------------------------------------------------------------------------------------------
 function prox!(y::DVec, ψ::ShiftedProximalOperators.ShiftedNormL1B2{Float64, <:DVec, <:DVec, <:DVec}, q::DVec, σ::Float64)

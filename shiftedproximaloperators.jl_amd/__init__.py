@@ -11,7 +11,8 @@ from .shifted import (ShiftedGroupNormL2, ShiftedGroupNormL2Binf, ShiftedIndBall
                       ShiftedProximableFunction, ShiftedRootNormLhalf, ShiftedRootNormLhalfBox, b2_prox_step, b2_prox_step_bang,
                       context, device_values,
                       group_prox_step, group_prox_step_bang, iprox, iprox_bang, iprox_step, iprox_step_bang,
-                      iprox_step_batch, iprox_step_batch_bang, prox,
+                      iprox_step_batch, iprox_step_batch_bang, lhalf_threshold_batch, prox,
+                      prox_step_lhalf_batch, prox_step_lhalf_batch_bang,
                       prox_bang, prox_step, prox_step_b2_batch, prox_step_b2_batch_bang, prox_step_bang, prox_step_batch, prox_step_batch_bang,
                       prox_step_group_batch, prox_step_group_batch_bang, prox_step_group_binf_batch,
                       prox_step_group_binf_batch_bang, prox_step_topr_batch, prox_step_topr_batch_bang, prox_value, prox_value_bang, set_bounds_bang, set_radius_bang, shift_bang, shifted, synchronize, value)

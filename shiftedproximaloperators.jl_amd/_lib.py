@@ -147,6 +147,14 @@ TOPR_BATCH_SIGNATURES = {
     "spx_proxstep_indball_l0_binf_batch": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p],
 }
 
+# libspx_lhalf_batch.so (include/spx_lhalf_batch.h): the batched RootNormLhalf(Box) calls, an eighth library that links against libspx.so
+LHALF_BATCH_LIB_PATH = LIB_PATH[:-3] + "_lhalf_batch.so"
+LHALF_BATCH_SIGNATURES = {
+    "spx_proxstep_lhalf_batch": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p],
+    "spx_proxstep_lhalf_box_batch": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p],
+    "spx_lhalf_threshold_batch": [_p, _p, _p, _i64, _p],
+}
+
 
 class SpxError(RuntimeError):
     """A libspx call returned a non-zero spx_status."""
@@ -294,6 +302,26 @@ def load_topr_batch():
             fn.restype = _int
         _topr_batch = L
     return _topr_batch
+
+
+_lhalf_batch = None
+
+
+def load_lhalf_batch():
+    """Load libspx_lhalf_batch.so (after libspx.so, whose contexts and error text it shares).  Raises if it is missing."""
+    global _lhalf_batch
+    if _lhalf_batch is None:
+        load()
+        if not os.path.exists(LHALF_BATCH_LIB_PATH):
+            raise ImportError("libspx_lhalf_batch.so not found at %s -- build it with shiftedproximaloperators.jl_amd/csrc/build.sh; "
+                              "there is no CPU fallback" % LHALF_BATCH_LIB_PATH)
+        L = ctypes.CDLL(LHALF_BATCH_LIB_PATH)
+        for name, args in LHALF_BATCH_SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.argtypes = args
+            fn.restype = _int
+        _lhalf_batch = L
+    return _lhalf_batch
 
 
 def check(status):

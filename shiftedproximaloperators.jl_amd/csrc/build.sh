@@ -8,7 +8,8 @@
 # batched group call, include/spx_gbatch.h) a fourth: lib/libspx_gbatch.so, X_gbatch.so; spx_gbinf_batch.hip (the batched Binf
 # group call, include/spx_gbinf_batch.h) a fifth: lib/libspx_gbinf_batch.so, X_gbinf_batch.so; spx_b2_batch.hip (the batched
 # ShiftedNormL1B2 call, include/spx_b2_batch.h) a sixth: lib/libspx_b2_batch.so, X_b2_batch.so; spx_topr_batch.hip (the batched
-# top-r calls, include/spx_topr_batch.h) a seventh: lib/libspx_topr_batch.so, X_topr_batch.so.
+# top-r calls, include/spx_topr_batch.h) a seventh: lib/libspx_topr_batch.so, X_topr_batch.so; spx_lhalf_batch.hip (the batched
+# RootNormLhalf(Box) calls, include/spx_lhalf_batch.h) an eighth: lib/libspx_lhalf_batch.so, X_lhalf_batch.so.
 set -euo pipefail
 HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 ROOT="$(cd "$HERE/../.." && pwd)"
@@ -39,6 +40,8 @@ pids+=($!)
 pids+=($!)
 "$HIPCC" "${FLAGS[@]}" -c "$HERE/spx_topr_batch.hip" -o "$OBJ/spx_topr_batch.o" &
 pids+=($!)
+"$HIPCC" "${FLAGS[@]}" -c "$HERE/spx_lhalf_batch.hip" -o "$OBJ/spx_lhalf_batch.o" &
+pids+=($!)
 fail=0
 for p in "${pids[@]}"; do wait "$p" || fail=1; done
 [ "$fail" = 0 ] || { echo "compile failed" >&2; exit 1; }
@@ -68,4 +71,8 @@ TOPRBATCH="${NAME%.so}_topr_batch.so"
 "$HIPCC" --offload-arch=gfx950 -shared -fPIC -fvisibility=hidden "$OBJ/spx_topr_batch.o" -L"$OUT" -l:"$NAME" '-Wl,-rpath,$ORIGIN' \
   -o "$OUT/$TOPRBATCH.tmp"
 mv -f "$OUT/$TOPRBATCH.tmp" "$OUT/$TOPRBATCH"
+LHALFBATCH="${NAME%.so}_lhalf_batch.so"
+"$HIPCC" --offload-arch=gfx950 -shared -fPIC -fvisibility=hidden "$OBJ/spx_lhalf_batch.o" -L"$OUT" -l:"$NAME" '-Wl,-rpath,$ORIGIN' \
+  -o "$OUT/$LHALFBATCH.tmp"
+mv -f "$OUT/$LHALFBATCH.tmp" "$OUT/$LHALFBATCH"
 echo "built $OUT/$NAME"

@@ -1130,6 +1130,96 @@ def prox_step_b2_batch(Q, XK, SJ, lam, sigma, delta, q_scale, chi_lambda=1.0, xk
                                    delta, q_scale, chi_lambda, xkn, out)
 
 
+def prox_step_lhalf_batch_bang(Y, Q, XK, SJ, lam, sigma, q_scale, l=None, u=None, selected=None, xkn=None, out=None):
+    """prox_step_bang for `batch` RootNormLhalf problems in ONE library call (spx_proxstep_lhalf[_box]_batch,
+    libspx_lhalf_batch.so), every per-problem scalar read from DEVICE memory.  Row b of the batch × n tensors Y, Q, XK, SJ (and
+    xkn) is one problem: Y[b] = prox!(ψ_b, q_scale[b] .* Q[b], sigma[b]) with ψ_b = shifted(shifted(RootNormLhalf(lam[b]), XK[b]),
+    SJ[b]) (ShiftedRootNormLhalf), in the box [l[b], u[b]] when l and u are given (ShiftedRootNormLhalfBox; a trust region of
+    radius Δ_b: l = -Δ, u = Δ), and
+
+        out[b, 0] = h  = lam[b] · Σ over the SELECTED indices of √|(XK[b] + SJ[b]) + Y[b]|
+        out[b, 1] = qy = Σ over ALL i of Q[b, i] · Y[b, i]   -- with the UNSCALED Q as passed, not q_scale[b] · Q
+        out[b, 2] = yy = Σ over ALL i of Y[b, i]²
+        xkn[b, i] = (XK[b, i] + SJ[b, i]) + Y[b, i] for every i, selected or not (None: not stored)
+
+    The 2-D tensors are float64 device tensors with unit inner stride and a common row stride (the library's ld >= n; the
+    elements between the rows are never touched).  lam, sigma, q_scale, l, u: 1-D float64 device tensors with one entry per
+    problem -- the kernel reads them, so a loop (or a captured graph) that updates them on the device needs no host round trip.
+    selected: ONE selection shared by the problems (Box form) -- a uint8 device mask of length n, used as it is, or 0-based
+    indices, from which a mask is built on every call (build the mask once for a loop or a capture).  out: a contiguous
+    batch × 3 float64 device tensor (None: allocated).  Returns (Y, out); nothing is read back and the stream is not
+    synchronised.  Y must not be Q; xkn must be none of the other tensors.
+    Box form: Y[b] and xkn[b] have the bits of prox_step_bang on row b alone with the same scalars.  Unboxed form: the same,
+    except for an element whose |q_scale · q + (xk + sj)| lies between the host's threshold and the device's (at most 4 ulps
+    apart; lhalf_threshold_batch returns the device's): such an element has the other branch of the prox's jump, 0 - (xk + sj)
+    or the stationary point (include/spx_lhalf_batch.h)."""
+    _batch_matrix(Y, "Y")
+    for t, name in ((Q, "Q"), (XK, "XK"), (SJ, "SJ")):
+        _batch_matrix(t, name, like=Y)
+    if xkn is not None:
+        _batch_matrix(xkn, "xkn", like=Y)
+    if Y is Q:
+        raise TypeError("prox_step_lhalf_batch: Y must not be Q (qy is taken with the Q that was passed)")
+    batch, n = Y.shape
+    # (one row has no row stride to share: with batch == 1 the strides are not compared and the library gets ld = n)
+    ld = Y.stride(0) if batch > 1 else max(n, 1)
+    if ld < n:
+        raise TypeError("the rows of Y overlap (row stride %d < n = %d)" % (ld, n))
+    box = l is not None or u is not None
+    if box and (l is None or u is None):
+        raise TypeError("l and u are given together (one scalar per problem each)")
+    if selected is not None and not box:
+        raise TypeError("selected needs the box form (give l and u)")
+    for t, name in ((lam, "lam"), (sigma, "sigma"), (q_scale, "q_scale")) + (((l, "l"), (u, "u")) if box else ()):
+        _batch_params(t, name, batch, Y)
+    if out is None:
+        out = torch.empty((batch, 3), dtype=torch.float64, device=Y.device)
+    elif not (type(out) is _Tensor and out.is_cuda and out.dtype == torch.float64 and tuple(out.shape) == (batch, 3)
+              and out.is_contiguous() and out.device == Y.device):
+        raise TypeError("out must be a contiguous batch x 3 float64 device tensor on Y's device")
+    L = _lib.load_lhalf_batch()
+    head = (_ctx(Y.device), _ptr(Y), _ptr(Q), _ptr(XK), _ptr(SJ), n, batch, ld, _ptr(lam), _ptr(sigma))
+    if not box:
+        _lib.check(L.spx_proxstep_lhalf_batch(*head, _ptr(q_scale), _ptr(xkn), _ptr(out)))
+        return Y, out
+    mask = None
+    if selected is not None:
+        if type(selected) is _Tensor and selected.dtype == torch.uint8:
+            if not (selected.is_cuda and selected.dim() == 1 and selected.numel() == n and (n <= 1 or selected.stride(0) == 1)
+                    and selected.device == Y.device):
+                raise TypeError("a selection mask must be a contiguous uint8 device tensor of length n on Y's device")
+            mask = selected
+        else:
+            built = _build_mask(selected, Y[0] if batch else Y.reshape(-1)[:n])
+            mask = built[0] if built is not None else None
+    _lib.check(L.spx_proxstep_lhalf_box_batch(*head, _ptr(l), _ptr(u), _ptr(mask), _ptr(q_scale), _ptr(xkn), _ptr(out)))
+    return Y, out
+
+
+def prox_step_lhalf_batch(Q, XK, SJ, lam, sigma, q_scale, l=None, u=None, selected=None, xkn=None, out=None):
+    """prox_step_lhalf_batch_bang into a new Y shaped and strided like Q: (Y, out); see prox_step_lhalf_batch_bang"""
+    return prox_step_lhalf_batch_bang(torch.empty_strided(Q.shape, Q.stride(), dtype=Q.dtype, device=Q.device), Q, XK, SJ, lam, sigma,
+                                      q_scale, l, u, selected, xkn, out)
+
+
+def lhalf_threshold_batch(lam, sigma, out=None):
+    """The thresholds prox_step_lhalf_batch_bang's unboxed kernel compares |q_scale · q + (xk + sj)| with, one per problem
+    (spx_lhalf_threshold_batch): p[b] = 54^(1/3) (2 sigma[b] lam[b])^(2/3) / 4 as the DEVICE rounds it -- the kernel's own value,
+    within 4 ulps of the host's.  lam, sigma: contiguous 1-D float64 device tensors of one length; out: one more (None:
+    allocated).  Returns out; nothing is read back and the stream is not synchronised."""
+    if not (type(lam) is _Tensor and lam.is_cuda and lam.dtype == torch.float64 and lam.dim() == 1):
+        raise TypeError("lam must be a contiguous 1-D float64 device tensor with one entry per problem")
+    batch = lam.numel()
+    _batch_params(lam, "lam", batch, lam)
+    _batch_params(sigma, "sigma", batch, lam)
+    if out is None:
+        out = torch.empty(batch, dtype=torch.float64, device=lam.device)
+    else:
+        _batch_params(out, "out", batch, lam)
+    _lib.check(_lib.load_lhalf_batch().spx_lhalf_threshold_batch(_ctx(lam.device), _ptr(lam), _ptr(sigma), batch, _ptr(out)))
+    return out
+
+
 def prox_step_topr_batch_bang(Y, Q, XK, SJ, r, q_scale, delta=None, xkn=None, out=None):
     """prox! + step statistics of the top-r operators, ShiftedIndBallL0 (delta=None) and ShiftedIndBallL0BInf (delta given), for
     `batch` problems in ONE library call (spx_proxstep_indball_l0_batch / spx_proxstep_indball_l0_binf_batch,
