@@ -14,7 +14,7 @@
 //      y = jl_min(jl_max((-xk) r, lo), hi) rinv - sj -- Julia-semantics min / max at the store only, fma-masked sums elsewhere.
 // Every lane forms the same totals (a fixed shape: wave_sum_dpp, then fold16_sum over the wavefronts' slots) and redoes the
 // scalar update for itself, so the workgroup needs no broadcast.
-// Which form: b2_batch_plan (spx_plan.hpp).
+// Which form: row_batch_plan on kB2BatchShape (spx_plan.hpp); the site shared with the other row-owner calls: spx_row_batch.hpp.
 //   row-resident (REG): the lane's units -- xk and both box ends -- are loaded once, by unconditional loads at clamped indices so
 //              that all of them are in flight, and stay in registers across the reductions.
 //   row walk   (!REG): 1024 lanes re-read the row once per reduction, kB2BatchWalkUnroll units in flight per lane.
@@ -23,8 +23,7 @@
 #include <type_traits>
 
 #include "spx_b2_batch.h"
-#include "spx_common.hpp"
-#include "spx_plan.hpp"
+#include "spx_row_batch.hpp"
 #include "spx_b2_row.hpp"
 
 namespace {
@@ -41,23 +40,6 @@ struct B2BatchArgs {
   int xkn_pairs;
   double* stats;
 };
-
-// sums of NV values over a workgroup of <= 16 wavefronts, the same bits in every lane; lds = [3][16], the slots of absent
-// wavefronts zero (b2_block_sum_n of spx_b2.hip)
-template <int NV>
-__device__ __forceinline__ void b2b_block_sum(double (&v)[3], double (*lds)[16]) {
-#pragma unroll
-  for (int k = 0; k < NV; ++k) v[k] = wave_sum_dpp(v[k]);
-  const int w = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < NV; ++k) lds[k][w] = v[k];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < NV; ++k) v[k] = fold16_sum(lds[k][threadIdx.x & 15]);
-}
 
 template <int LANES, int EPL, bool REG, bool PAIRS>
 __global__ __launch_bounds__(LANES) void k_b2_batch(B2BatchArgs k) {
@@ -78,26 +60,18 @@ __global__ __launch_bounds__(LANES) void k_b2_batch(B2BatchArgs k) {
   double* const xkn = k.xkn ? k.xkn + off : nullptr;
   const int n = k.n;
   const int ufull = n / E;                              // units of E elements; >= 1 (pairs: n >= 2)
-  const int utot = (int)b2_batch_units(n, PAIRS);       // ... and the one-element unit of an odd row in the pairs form
+  const int utot = (int)row_batch_units(n, PAIRS);      // ... and the one-element unit of an odd row in the pairs form
 
-  // unit u as the sums want it: xk and the box (sj + q_scale q) -+ lambda sigma of its elements, zeros beyond the row.  Loads at
-  // a clamped index, never past the row's last full unit; the lane that owns the odd row's last element fetches it alone.
+  // unit u as the sums want it: xk and the box (sj + q_scale q) -+ lambda sigma of its elements, zeros beyond the row
   auto load_unit = [&](int u, double (&x)[E], double (&lo)[E], double (&hi)[E]) {
-    const int uc = u < ufull ? u : ufull - 1;
-    double xv[E], sv[E], qv[E];
-    if constexpr (PAIRS) {
-      const f64x2 a = reinterpret_cast<const f64x2*>(xk)[uc], c = reinterpret_cast<const f64x2*>(sj)[uc],
-                  d = reinterpret_cast<const f64x2*>(q)[uc];
-      xv[0] = a.x; xv[1] = a.y; sv[0] = c.x; sv[1] = c.y; qv[0] = d.x; qv[1] = d.y;
-      if (2 * u == n - 1) { xv[0] = xk[n - 1]; sv[0] = sj[n - 1]; qv[0] = q[n - 1]; }
-    } else {
-      xv[0] = xk[uc]; sv[0] = sj[uc]; qv[0] = q[uc];
-    }
+    const double* const in[3] = {xk, sj, q};
+    double w[3][E];
+    row_load_unit<PAIRS>(in, u, ufull, n, w);
 #pragma unroll
     for (int e = 0; e < E; ++e) {
       const bool valid = u * E + e < n;
-      const double sq = sv[e] + qs * qv[e];  // `sj .+ q` (:56) at q_scale q: one rounded multiply in front of the sum
-      x[e] = valid ? xv[e] : 0.0;
+      const double sq = w[1][e] + qs * w[2][e];  // `sj .+ q` (:56) at q_scale q: one rounded multiply in front of the sum
+      x[e] = valid ? w[0][e] : 0.0;
       lo[e] = valid ? sq - ls : 0.0;
       hi[e] = valid ? sq + ls : 0.0;
     }
@@ -107,7 +81,7 @@ __global__ __launch_bounds__(LANES) void k_b2_batch(B2BatchArgs k) {
 #pragma unroll
     for (int kk = 0; kk < UPL; ++kk) {
       double x[E], lo[E], hi[E];
-      load_unit((int)b2_batch_unit(kk, LANES, t), x, lo, hi);
+      load_unit((int)row_batch_unit(kk, LANES, t), x, lo, hi);
 #pragma unroll
       for (int e = 0; e < E; ++e) { X[kk * E + e] = x[e]; LO[kk * E + e] = lo[e]; HI[kk * E + e] = hi[e]; }
     }
@@ -152,8 +126,8 @@ __global__ __launch_bounds__(LANES) void k_b2_batch(B2BatchArgs k) {
       }
     }
     if (bad) v[0] = __longlong_as_double(0x7ff8000000000000ll);
-    if (first) b2b_block_sum<3>(v, lds);
-    else b2b_block_sum<2>(v, lds);
+    if (first) row_block_sum<3>(v, lds);
+    else row_block_sum<2>(v, lds);
     P = v[0]; C = v[1];
     if (first) F = v[2];
   };
@@ -181,11 +155,8 @@ __global__ __launch_bounds__(LANES) void k_b2_batch(B2BatchArgs k) {
       const f64x2 s2 = reinterpret_cast<const f64x2*>(sj)[u], q2 = reinterpret_cast<const f64x2*>(q)[u];
       const f64x2 o{outv(lo[0], hi[0], x[0], s2.x), outv(lo[E - 1], hi[E - 1], x[E - 1], s2.y)};
       const f64x2 v{(x[0] + s2.x) + o.x, (x[E - 1] + s2.y) + o.y};
-      reinterpret_cast<f64x2*>(y)[u] = o;
-      if (xkn != nullptr) {
-        if (k.xkn_pairs) reinterpret_cast<f64x2*>(xkn)[u] = v;
-        else { xkn[2 * u] = v.x; xkn[2 * u + 1] = v.y; }
-      }
+      row_store_y<PAIRS>(y, u, true, o.x, o.y);
+      row_store_xkn<PAIRS>(xkn, k.xkn_pairs, u, true, v.x, v.y);
       sums(q2.x, v.x, o.x);
       sums(q2.y, v.y, o.y);
     } else {  // one element: the element-wise form, or the last element of an odd row
@@ -193,8 +164,8 @@ __global__ __launch_bounds__(LANES) void k_b2_batch(B2BatchArgs k) {
       const double s = sj[i], qr = q[i];
       const double o = outv(lo[0], hi[0], x[0], s);
       const double v = (x[0] + s) + o;
-      y[i] = o;
-      if (xkn != nullptr) xkn[i] = v;
+      row_store_y<PAIRS>(y, u, false, o, o);
+      row_store_xkn<PAIRS>(xkn, k.xkn_pairs, u, false, v, v);
       sums(qr, v, o);
     }
   };
@@ -204,7 +175,7 @@ __global__ __launch_bounds__(LANES) void k_b2_batch(B2BatchArgs k) {
       double x[E], lo[E], hi[E];
 #pragma unroll
       for (int e = 0; e < E; ++e) { x[e] = X[kk * E + e]; lo[e] = LO[kk * E + e]; hi[e] = HI[kk * E + e]; }
-      store_unit((int)b2_batch_unit(kk, LANES, t), x, lo, hi);
+      store_unit((int)row_batch_unit(kk, LANES, t), x, lo, hi);
     }
   } else {
     for (int base = 0; base < utot; base += LANES * kB2BatchWalkUnroll) {
@@ -215,7 +186,7 @@ __global__ __launch_bounds__(LANES) void k_b2_batch(B2BatchArgs k) {
       for (int j = 0; j < kB2BatchWalkUnroll; ++j) store_unit(base + j * LANES + t, x[j], lo[j], hi[j]);
     }
   }
-  b2b_block_sum<3>(h, lds);
+  row_block_sum<3>(h, lds);
   if (t == 0) {
     k.stats[3 * b] = lam * h[0];
     k.stats[3 * b + 1] = h[1];
@@ -223,59 +194,32 @@ __global__ __launch_bounds__(LANES) void k_b2_batch(B2BatchArgs k) {
   }
 }
 
-template <int LANES, int EPL, bool REG>
-void b2_batch_launch(spx_ctx* ctx, const B2BatchPlan& p, const B2BatchArgs& a) {
-  if (p.pairs) hipLaunchKernelGGL((k_b2_batch<LANES, EPL, REG, true>), dim3((unsigned)p.grid), dim3(LANES), 0, ctx->stream, a);
-  else hipLaunchKernelGGL((k_b2_batch<LANES, EPL, REG, false>), dim3((unsigned)p.grid), dim3(LANES), 0, ctx->stream, a);
-}
-template <int TILE>
-void b2_batch_launch_tile(spx_ctx* ctx, const B2BatchPlan& p, const B2BatchArgs& a) {
-  if constexpr (TILE < kB2BatchTileCount) {
-    if (p.tile == TILE) b2_batch_launch<kB2BatchTiles[TILE].lanes, kB2BatchTiles[TILE].epl, true>(ctx, p, a);
-    else b2_batch_launch_tile<TILE + 1>(ctx, p, a);
+// what differs from the other row-owner calls on the host (run_row_batch, spx_row_batch.hpp)
+struct B2BatchKind {
+  static constexpr const char* kLibName = "libspx_b2_batch.so";
+  static constexpr RowBatchShape kShape = kB2BatchShape;
+  struct Params {
+    const double *lambda, *sigma, *delta, *q_scale;
+    double chi_lambda;
+  };
+  static bool null_params(const Params& a) { return a.lambda == nullptr || a.sigma == nullptr || a.delta == nullptr || a.q_scale == nullptr; }
+  static constexpr const char* kNullParams = "a parameter array (lambda, sigma, delta, q_scale) is NULL";
+  static const char* refuse_alias(const RowBatchCall&) { return nullptr; }
+  static constexpr const char* kNTooLarge =
+      "n > 2^20: one workgroup per problem is the wrong tool (spx_proxstep_l1_b2 holds such a problem on chip across many CUs, one "
+      "problem per call)";
+  template <int LANES, int EPL, bool REG, bool PAIRS>
+  static void launch(const RowBatchCall& c, const Params& a, const RowBatchPlan& p) {
+    hipLaunchKernelGGL((k_b2_batch<LANES, EPL, REG, PAIRS>), dim3((unsigned)p.grid), dim3(LANES), 0, c.ctx->stream,
+                       B2BatchArgs{c.y, c.q, c.xk, c.sj, c.xkn, a.lambda, a.sigma, a.delta, a.q_scale, a.chi_lambda, c.ld, (int)c.n,
+                                   p.xkn_pairs ? 1 : 0, c.stats_dev});
   }
-}
+};
 
 }  // namespace
 
-// Every refusal is made before anything is enqueued.  There is no host destination: the call only enqueues.
 SPX_EXPORT int spx_proxstep_l1_b2_batch(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
                                         int64_t batch, int64_t ld, const double* lambda, const double* sigma, const double* delta,
                                         const double* q_scale, double chi_lambda, double* xkn, double* stats_dev) {
-  // the libraries share spx_ctx and four functions: refuse to touch a context of a libspx.so built from other sources
-  if (spx_shared_abi() != kSpxSharedAbi) {
-    spx_set_error("libspx_b2_batch.so and libspx.so do not match (shared layout %d, expected %d): rebuild both", spx_shared_abi(),
-                  kSpxSharedAbi);
-    return SPX_ERR_INTERNAL;
-  }
-  SPX_REQUIRE(ctx != nullptr, "ctx is NULL");
-  SPX_REQUIRE(n >= 0, "n < 0");
-  SPX_REQUIRE(batch >= 0, "batch < 0");
-  if (batch == 0) return SPX_OK;
-  SPX_REQUIRE(stats_dev != nullptr, "stats_dev is NULL");
-  SPX_REQUIRE(lambda != nullptr && sigma != nullptr && delta != nullptr && q_scale != nullptr,
-              "a parameter array (lambda, sigma, delta, q_scale) is NULL");
-  SPX_REQUIRE(ld >= n, "ld < n");
-  const void* const in[4] = {y, q, xk, sj};
-  if (n > 0) {
-    for (const void* v : in) SPX_REQUIRE(v != nullptr, "NULL vector with n > 0");
-    SPX_REQUIRE(y != q, kSpxYAliasesQ);
-    if (xkn != nullptr) {
-      for (const void* o : in) SPX_REQUIRE(xkn != o, "xkn is one of the other vectors");
-    }
-  }
-  int bits = spx_aligned16(xkn) ? 0 : 1 << 4;
-  for (int v = 0; v < 4; ++v) bits |= spx_aligned16(in[v]) ? 0 : 1 << v;
-  const B2BatchPlan p = b2_batch_plan(n, batch, ld, bits);
-  SPX_REQUIRE(p.ok || p.why != B2BatchRefusal::kNTooLarge,
-              "n > 2^20: one workgroup per problem is the wrong tool (spx_proxstep_l1_b2 holds such a problem on chip across many CUs, one "
-              "problem per call)");
-  SPX_REQUIRE(p.ok, "batch > 2^31 - 1");
-  SPX_ON_DEVICE(ctx);
-  if (n == 0) return spx_zero_async(ctx, stats_dev, (size_t)batch * 3 * sizeof(double));  // zeros for every problem, by a kernel
-  const B2BatchArgs a{y, q, xk, sj, xkn, lambda, sigma, delta, q_scale, chi_lambda, ld, (int)n, p.xkn_pairs ? 1 : 0, stats_dev};
-  if (p.form == B2BatchForm::kResident) b2_batch_launch_tile<0>(ctx, p, a);
-  else b2_batch_launch<kB2BatchWalkLanes, 0, false>(ctx, p, a);
-  SPX_LAUNCH_CHECK();
-  return SPX_OK;
+  return run_row_batch<B2BatchKind>({ctx, y, q, xk, sj, n, batch, ld, xkn, stats_dev}, {lambda, sigma, delta, q_scale, chi_lambda});
 }

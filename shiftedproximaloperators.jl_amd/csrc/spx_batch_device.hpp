@@ -264,11 +264,7 @@ int run_batch(const BatchCall& c) {
   constexpr bool kBox = Row::Op::kBox;
   constexpr int NS = Kind::kPlan.planes;
   spx_ctx* const ctx = c.ctx;
-  // the libraries share spx_ctx and four functions: refuse to touch a context of a libspx.so built from other sources
-  if (spx_shared_abi() != kSpxSharedAbi) {
-    spx_set_error("%s and libspx.so do not match (shared layout %d, expected %d): rebuild both", Kind::kLibName, spx_shared_abi(), kSpxSharedAbi);
-    return SPX_ERR_INTERNAL;
-  }
+  SPX_REQUIRE_SHARED_ABI(Kind::kLibName);
   SPX_REQUIRE(ctx != nullptr, "ctx is NULL");
   SPX_REQUIRE(c.n >= 0, "n < 0");
   SPX_REQUIRE(c.batch >= 0, "batch < 0");

@@ -120,6 +120,16 @@ constexpr int kSpxSharedVersion = 1;
 constexpr int kSpxSharedAbi = kSpxSharedVersion * 65536 + (int)sizeof(spx_ctx);
 SPX_SHARED int spx_shared_abi();
 SPX_SHARED void spx_set_error(const char* fmt, ...);
+// the first statement of every entry point of a batch library `lib` ("libspx_batch.so", ...): the libraries share spx_ctx and four
+// functions, so refuse to touch a context of a libspx.so built from other sources
+#define SPX_REQUIRE_SHARED_ABI(lib)                                                                                       \
+  do {                                                                                                                    \
+    if (spx_shared_abi() != kSpxSharedAbi) {                                                                              \
+      spx_set_error("%s and libspx.so do not match (shared layout %d, expected %d): rebuild both", lib, spx_shared_abi(), \
+                    kSpxSharedAbi);                                                                                       \
+      return SPX_ERR_INTERNAL;                                                                                            \
+    }                                                                                                                     \
+  } while (0)
 SPX_SHARED int spx_ws_reserve(spx_ctx* ctx, size_t bytes);
 #ifdef SPX_TEST_HOOKS
 // Test builds: every call site of spx_ws_reserve names itself (key 104) before it reserves; the staging allocator (spx_host.hip)

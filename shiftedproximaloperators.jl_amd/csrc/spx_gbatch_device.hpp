@@ -28,11 +28,7 @@ struct GBatchCall {
 template <class Kind>
 int run_gbatch(const GBatchCall& c) {
   spx_ctx* const ctx = c.ctx;
-  // the libraries share spx_ctx and four functions: refuse to touch a context of a libspx.so built from other sources
-  if (spx_shared_abi() != kSpxSharedAbi) {
-    spx_set_error("%s and libspx.so do not match (shared layout %d, expected %d): rebuild both", Kind::kLibName, spx_shared_abi(), kSpxSharedAbi);
-    return SPX_ERR_INTERNAL;
-  }
+  SPX_REQUIRE_SHARED_ABI(Kind::kLibName);
   SPX_REQUIRE(ctx != nullptr, "ctx is NULL");
   SPX_REQUIRE(c.group_size >= 1 && c.group_size <= kGroupRegMax, Kind::kBadGroupSize);
   SPX_REQUIRE(c.ngroups >= 0, "ngroups < 0");

@@ -102,10 +102,7 @@ SPX_EXPORT int spx_proxstep_lhalf_box_batch(spx_ctx* ctx, double* y, const doubl
                                                  nullptr, nullptr, l, u, sel_mask});
 }
 SPX_EXPORT int spx_lhalf_threshold_batch(spx_ctx* ctx, const double* lambda, const double* sigma, int64_t batch, double* p_dev) {
-  if (spx_shared_abi() != kSpxSharedAbi) {
-    spx_set_error("%s and libspx.so do not match (shared layout %d, expected %d): rebuild both", LhalfKind::kLibName, spx_shared_abi(), kSpxSharedAbi);
-    return SPX_ERR_INTERNAL;
-  }
+  SPX_REQUIRE_SHARED_ABI(LhalfKind::kLibName);
   SPX_REQUIRE(ctx != nullptr, "ctx is NULL");
   SPX_REQUIRE(batch >= 0, "batch < 0");
   if (batch == 0) return SPX_OK;

@@ -483,62 +483,63 @@ SPX_PLAN_HD inline int binf_walk_bit(unsigned long long word, int slots, int pas
 }
 
 // ---------------------------------------------------------------------------------------------
-// batched ShiftedNormL1B2 call (spx_proxstep_l1_b2_batch, spx_b2_batch.hip): `batch` problems of n elements, problem b at
-// elements [b * ld, b * ld + n) of every vector.  ONE workgroup owns a problem through its whole root iteration (spx_b2_row.hpp):
-// no workgroup waits for another, so there is no residency question and no workspace.
-//   row-resident (n <= kB2BatchRowMax): xk and the box ends of the row stay in registers across the reductions; lanes x elements
-//              per lane by n (kB2BatchTiles) -- a row of 1e3 takes 256 lanes, not a CU-wide workgroup.
-//   row walk   (kB2BatchRowMax < n <= kB2BatchNMax): kB2BatchWalkLanes lanes re-read the row once per reduction (from L2 or the
-//              Infinity Cache at these sizes).  Beyond kB2BatchNMax the call is refused: spx_proxstep_l1_b2 holds such a problem on
-//              chip across many CUs.
-// A lane owns the units u = k * lanes + t (k = 0, 1, ...); a unit is a 16-byte pair of elements (pairs) or one element
-// (element-wise).  Pairs: y, q, xk, sj all on a 16-byte boundary, ld even and n >= 2 -- every row then starts on one; a row of odd
-// n ends in a unit of one element.  Otherwise the element-wise form for the whole launch.  xkn takes no part in the choice:
-// where it sits 8 bytes off, only its stores drop to 8 bytes (xkn_pairs).
+// row-owner batched calls (spx_row_batch.hpp): `batch` problems of n elements, problem b at elements [b * ld, b * ld + n) of
+// every vector.  ONE workgroup owns a problem from its first load to its last store: no workgroup waits for another, so there is
+// no residency question and no workspace.  What a call alone decides is its shape (RowBatchShape); the plan is the same function
+// of it for every call.
+//   row-resident (n <= row_max): the row stays in registers; lanes x elements per lane by n (the shape's tiles) -- a row of 1e3
+//              takes 256 lanes, not a CU-wide workgroup.
+//   row walk   (row_max < n <= n_max): walk_lanes lanes re-read the row once per pass (from L2 or the Infinity Cache at these
+//              sizes), walk_unroll units in flight per lane.  Beyond n_max the call is refused: a single call serves such a problem.
+// A lane owns the units u = k * lanes + t (k = 0, 1, ...) in EVERY pass; a unit is a 16-byte pair of elements (pairs) or one
+// element (element-wise).  Pairs: y, q, xk, sj all on a 16-byte boundary, ld even and n >= 2 -- every row then starts on one; a
+// row of odd n ends in a unit of one element.  Otherwise the element-wise form for the whole launch.  xkn takes no part in the
+// choice: where it sits 8 bytes off, only its stores drop to 8 bytes (xkn_pairs).
 // Form, tile and pairs are functions of n and the alignment class alone: a problem's bits do not depend on batch or on its row.
 // ---------------------------------------------------------------------------------------------
-constexpr int64_t kB2BatchRowMax = kB2RegBlock;          // 8192: 512 lanes x 16 elements, the tile of k_b2_coop<REG>
-constexpr int64_t kB2BatchNMax = (int64_t)1 << 20;
-constexpr int kB2BatchWalkLanes = 1024;
-constexpr int kB2BatchWalkUnroll = 4;                    // units a lane of the row walk has in flight
-struct B2BatchTile { int lanes, epl; };
-constexpr int kB2BatchTileCount = 4;
-constexpr B2BatchTile kB2BatchTiles[kB2BatchTileCount] = {{64, 4}, {256, 4}, {256, 16}, {kB2RegThreads, kB2Epl}};  // 256, 1024, 4096, 8192 elements
-enum class B2BatchForm { kResident, kWalk };
-enum class B2BatchRefusal { kNone, kNTooLarge, kBatchTooLarge };
-struct B2BatchPlan {
-  bool ok;
-  B2BatchRefusal why;  // !ok
-  B2BatchForm form;
-  int tile;            // kResident: the row of kB2BatchTiles
-  int lanes;           // of the workgroup
-  int epl;             // kResident: elements per lane held in registers
-  bool pairs;
-  bool xkn_pairs;      // xkn is stored by 16-byte pairs too
-  int64_t grid;        // = batch
+struct RowBatchTile { int lanes, epl; };
+struct RowBatchShape {
+  const RowBatchTile* tiles;  // ascending by lanes x epl; the last one holds row_max elements
+  int tile_count;
+  int64_t row_max;            // the resident bound
+  int64_t n_max;
+  int walk_lanes;
+  int walk_unroll;            // units a lane of the row walk has in flight
 };
-SPX_PLAN_HD inline int b2_batch_unit_elems(bool pairs) { return pairs ? 2 : 1; }
+enum class RowBatchForm { kResident, kWalk };
+enum class RowBatchRefusal { kNone, kNTooLarge, kBatchTooLarge };
+struct RowBatchPlan {
+  bool ok;
+  RowBatchRefusal why;  // !ok
+  RowBatchForm form;
+  int tile;             // kResident: the row of the shape's tiles; -1 on the walk
+  int lanes;            // of the workgroup
+  int epl;              // kResident: elements per lane held in registers; 0 on the walk
+  bool pairs;
+  bool xkn_pairs;       // xkn is stored by 16-byte pairs too
+  int64_t grid;         // = batch
+};
 // units of a row: full ones and, in the pairs form with odd n, one of a single element behind them
-SPX_PLAN_HD inline int64_t b2_batch_units(int64_t n, bool pairs) { return pairs ? (n + 1) >> 1 : n; }
+SPX_PLAN_HD inline int64_t row_batch_units(int64_t n, bool pairs) { return pairs ? (n + 1) >> 1 : n; }
 // the unit that slot k of lane t owns
-SPX_PLAN_HD inline int64_t b2_batch_unit(int64_t k, int lanes, int t) { return k * lanes + t; }
+SPX_PLAN_HD inline int64_t row_batch_unit(int64_t k, int lanes, int t) { return k * lanes + t; }
 // base_alignment_bits: bit k set = vector k of y, q, xk, sj, xkn starts off a 16-byte boundary (an absent xkn: clear)
-inline B2BatchPlan b2_batch_plan(int64_t n, int64_t batch, int64_t ld, int base_alignment_bits) {
-  B2BatchPlan p{};
-  if (n > kB2BatchNMax) { p.why = B2BatchRefusal::kNTooLarge; return p; }
-  if (batch > kBatchGridMax) { p.why = B2BatchRefusal::kBatchTooLarge; return p; }
+inline RowBatchPlan row_batch_plan(const RowBatchShape& s, int64_t n, int64_t batch, int64_t ld, int base_alignment_bits) {
+  RowBatchPlan p{};
+  if (n > s.n_max) { p.why = RowBatchRefusal::kNTooLarge; return p; }
+  if (batch > kBatchGridMax) { p.why = RowBatchRefusal::kBatchTooLarge; return p; }
   p.pairs = (base_alignment_bits & 15) == 0 && (ld & 1) == 0 && n >= 2;
   p.xkn_pairs = p.pairs && (base_alignment_bits & 16) == 0;
-  if (n <= kB2BatchRowMax) {
-    p.form = B2BatchForm::kResident;
+  if (n <= s.row_max) {
+    p.form = RowBatchForm::kResident;
     p.tile = 0;
-    while ((int64_t)kB2BatchTiles[p.tile].lanes * kB2BatchTiles[p.tile].epl < n) ++p.tile;
-    p.lanes = kB2BatchTiles[p.tile].lanes;
-    p.epl = kB2BatchTiles[p.tile].epl;
+    while ((int64_t)s.tiles[p.tile].lanes * s.tiles[p.tile].epl < n) ++p.tile;
+    p.lanes = s.tiles[p.tile].lanes;
+    p.epl = s.tiles[p.tile].epl;
   } else {
-    p.form = B2BatchForm::kWalk;
+    p.form = RowBatchForm::kWalk;
     p.tile = -1;
-    p.lanes = kB2BatchWalkLanes;
+    p.lanes = s.walk_lanes;
     p.epl = 0;
   }
   p.grid = batch;
@@ -546,65 +547,28 @@ inline B2BatchPlan b2_batch_plan(int64_t n, int64_t batch, int64_t ld, int base_
   return p;
 }
 
-// ---------------------------------------------------------------------------------------------
-// batched top-r calls (spx_proxstep_indball_l0[_binf]_batch, spx_topr_batch.hip): `batch` problems of n elements, problem b at
-// elements [b * ld, b * ld + n) of every vector.  ONE workgroup owns a problem through its whole selection (spx_topr_row.hpp):
-// no workgroup waits for another, so there is no residency question and no workspace.
-//   row-resident (n <= kToprBatchRowMax): v, xk + sj and q of the row stay in registers across the digit passes; lanes x elements
-//              per lane by n (kToprBatchTiles) -- a row of 1e3 takes 256 lanes, not a CU-wide workgroup.
-//   row walk   (kToprBatchRowMax < n <= kToprBatchNMax): kToprBatchWalkLanes lanes park v in the row of y and re-read it once per
-//              digit (from L2 or the Infinity Cache at these sizes).  Beyond kToprBatchNMax the call is refused:
-//              spx_prox_indball_l0[_binf] spreads such a problem over many CUs.
-// A lane owns the units u = k * lanes + t (k = 0, 1, ...) in EVERY pass; a unit is a 16-byte pair of elements (pairs) or one
-// element (element-wise).  Pairs: y, q, xk, sj all on a 16-byte boundary, ld even and n >= 2 -- every row then starts on one; a
-// row of odd n ends in a unit of one element.  Otherwise the element-wise form for the whole launch.  xkn takes no part in the
-// choice: where it sits 8 bytes off, only its stores drop to 8 bytes (xkn_pairs).
-// Form, tile and pairs are functions of n and the alignment class alone: a problem's bits do not depend on batch or on its row.
-// ---------------------------------------------------------------------------------------------
+// batched ShiftedNormL1B2 call (spx_proxstep_l1_b2_batch, spx_b2_batch.hip): the workgroup runs the whole root iteration
+// (spx_b2_row.hpp).  Resident: xk and the box ends of the row stay in registers across the reductions; the largest tile is that
+// of k_b2_coop<REG>.  Walk: the row is re-read once per reduction.  n > kB2BatchNMax: spx_proxstep_l1_b2 holds such a problem on
+// chip across many CUs.
+constexpr int64_t kB2BatchRowMax = kB2RegBlock;          // 8192: 512 lanes x 16 elements, the tile of k_b2_coop<REG>
+constexpr int64_t kB2BatchNMax = (int64_t)1 << 20;
+constexpr int kB2BatchWalkLanes = 1024;
+constexpr int kB2BatchWalkUnroll = 4;
+constexpr int kB2BatchTileCount = 4;
+constexpr RowBatchTile kB2BatchTiles[kB2BatchTileCount] = {{64, 4}, {256, 4}, {256, 16}, {kB2RegThreads, kB2Epl}};  // 256, 1024, 4096, 8192 elements
+constexpr RowBatchShape kB2BatchShape = {kB2BatchTiles, kB2BatchTileCount, kB2BatchRowMax, kB2BatchNMax, kB2BatchWalkLanes,
+                                         kB2BatchWalkUnroll};
+
+// batched top-r calls (spx_proxstep_indball_l0[_binf]_batch, spx_topr_batch.hip): the workgroup runs the whole selection
+// (spx_topr_row.hpp).  Resident: v, xk + sj and q of the row stay in registers across the digit passes; the largest tile is what
+// the histogram in LDS and three doubles per element leave room for.  Walk: v is parked in the row of y and re-read once per
+// digit.  n > kToprBatchNMax: spx_prox_indball_l0[_binf] spreads such a problem over many CUs.
 constexpr int64_t kToprBatchRowMax = 8192;               // 512 lanes x 16 elements
 constexpr int64_t kToprBatchNMax = (int64_t)1 << 20;
 constexpr int kToprBatchWalkLanes = 1024;
-constexpr int kToprBatchWalkUnroll = 4;                  // units a lane of the row walk has in flight
-struct ToprBatchTile { int lanes, epl; };
+constexpr int kToprBatchWalkUnroll = 4;
 constexpr int kToprBatchTileCount = 4;
-constexpr ToprBatchTile kToprBatchTiles[kToprBatchTileCount] = {{64, 4}, {256, 4}, {256, 16}, {512, 16}};  // 256, 1024, 4096, 8192 elements
-enum class ToprBatchForm { kResident, kWalk };
-enum class ToprBatchRefusal { kNone, kNTooLarge, kBatchTooLarge };
-struct ToprBatchPlan {
-  bool ok;
-  ToprBatchRefusal why;  // !ok
-  ToprBatchForm form;
-  int tile;              // kResident: the row of kToprBatchTiles; -1 on the walk
-  int lanes;             // of the workgroup
-  int epl;               // kResident: elements per lane held in registers; 0 on the walk
-  bool pairs;
-  bool xkn_pairs;        // xkn is stored by 16-byte pairs too
-  int64_t grid;          // = batch
-};
-// units of a row: full ones and, in the pairs form with odd n, one of a single element behind them
-SPX_PLAN_HD inline int64_t topr_batch_units(int64_t n, bool pairs) { return pairs ? (n + 1) >> 1 : n; }
-// the unit that slot k of lane t owns
-SPX_PLAN_HD inline int64_t topr_batch_unit(int64_t k, int lanes, int t) { return k * lanes + t; }
-// base_alignment_bits: bit k set = vector k of y, q, xk, sj, xkn starts off a 16-byte boundary (an absent xkn: clear)
-inline ToprBatchPlan topr_batch_plan(int64_t n, int64_t batch, int64_t ld, int base_alignment_bits) {
-  ToprBatchPlan p{};
-  if (n > kToprBatchNMax) { p.why = ToprBatchRefusal::kNTooLarge; return p; }
-  if (batch > kBatchGridMax) { p.why = ToprBatchRefusal::kBatchTooLarge; return p; }
-  p.pairs = (base_alignment_bits & 15) == 0 && (ld & 1) == 0 && n >= 2;
-  p.xkn_pairs = p.pairs && (base_alignment_bits & 16) == 0;
-  if (n <= kToprBatchRowMax) {
-    p.form = ToprBatchForm::kResident;
-    p.tile = 0;
-    while ((int64_t)kToprBatchTiles[p.tile].lanes * kToprBatchTiles[p.tile].epl < n) ++p.tile;
-    p.lanes = kToprBatchTiles[p.tile].lanes;
-    p.epl = kToprBatchTiles[p.tile].epl;
-  } else {
-    p.form = ToprBatchForm::kWalk;
-    p.tile = -1;
-    p.lanes = kToprBatchWalkLanes;
-    p.epl = 0;
-  }
-  p.grid = batch;
-  p.ok = true;
-  return p;
-}
+constexpr RowBatchTile kToprBatchTiles[kToprBatchTileCount] = {{64, 4}, {256, 4}, {256, 16}, {512, 16}};  // 256, 1024, 4096, 8192 elements
+constexpr RowBatchShape kToprBatchShape = {kToprBatchTiles, kToprBatchTileCount, kToprBatchRowMax, kToprBatchNMax,
+                                           kToprBatchWalkLanes, kToprBatchWalkUnroll};

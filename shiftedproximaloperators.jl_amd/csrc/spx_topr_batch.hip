@@ -12,7 +12,7 @@
 //      count: tied data and index digits send whole wavefronts to one bin), located by wavefront 0 in two 64-wide scans;
 //   3. the storing pass: y = (keep ? v : 0) - (xk + sj) [clamped], xkn = (xk + sj) + y, the count of nonzeros of xkn and the two
 //      sums, by a fixed-order workgroup reduce (wave_sum_dpp, then fold16_sum over the wavefronts' slots).
-// Which form: topr_batch_plan (spx_plan.hpp).
+// Which form: row_batch_plan on kToprBatchShape (spx_plan.hpp); the site shared with the other row-owner calls: spx_row_batch.hpp.
 //   row-resident (REG): the lane's units -- v, xk + sj and q -- are loaded once, by unconditional loads at clamped indices so that
 //              all of them are in flight, and stay in registers across the digit passes: 40 B/element of traffic.
 //   row walk   (!REG): 1024 lanes park v in the row of y and re-read it once per digit, kToprBatchWalkUnroll units in flight per
@@ -21,8 +21,7 @@
 #include <type_traits>
 
 #include "spx_topr_batch.h"
-#include "spx_common.hpp"
-#include "spx_plan.hpp"
+#include "spx_row_batch.hpp"
 #include "spx_topr_row.hpp"
 
 namespace {
@@ -39,22 +38,6 @@ struct ToprBatchArgs {
   int xkn_pairs;
   double* stats;
 };
-
-// sums of three values over a workgroup of <= 16 wavefronts, the same bits in every lane; lds = [3][16], the slots of absent
-// wavefronts zero (b2b_block_sum of spx_b2_batch.hip)
-__device__ __forceinline__ void topr_block_sum(double (&v)[3], double (*lds)[16]) {
-#pragma unroll
-  for (int k = 0; k < 3; ++k) v[k] = wave_sum_dpp(v[k]);
-  const int w = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) lds[k][w] = v[k];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < 3; ++k) v[k] = fold16_sum(lds[k][threadIdx.x & 15]);
-}
 
 // Histogram add of a wavefront's digits with the heavy hitter peeled off first: the bin of the first pending lane is added ONCE
 // with its population count, the rest go lane by lane (atomics on one LDS address are serialised).  Called by whole wavefronts;
@@ -148,49 +131,29 @@ __global__ __launch_bounds__(LANES) void k_topr_batch(ToprBatchArgs k) {
   double* const xkn = k.xkn ? k.xkn + off : nullptr;
   const int n = k.n;
   const int ufull = n / E;                              // units of E elements; >= 1 (pairs: n >= 2)
-  const int utot = (int)topr_batch_units(n, PAIRS);     // ... and the one-element unit of an odd row in the pairs form
+  const int utot = (int)row_batch_units(n, PAIRS);      // ... and the one-element unit of an odd row in the pairs form
   __syncthreads();
 
   // unit u of the inputs: v = (xk + sj) + q_scale q (shiftedIndBallL0.jl:66 at q_scale q: one rounded multiply in front of the sum;
-  // from_y: the parked v instead), xs = xk + sj, q as passed.  Loads at a clamped index, never past the row's last full unit; the
-  // lane that owns the odd row's last element fetches it alone.  What a slot beyond the row holds is never used.
+  // from_y: the parked v instead), xs = xk + sj, q as passed.  What a slot beyond the row holds is never used.
   auto load_in = [&](int u, double (&v)[E], double (&xs)[E], double (&qv)[E], bool from_y) {
-    const int uc = u < ufull ? u : ufull - 1;
-    double xv[E], sv[E], pv[E];
-    if constexpr (PAIRS) {
-      const f64x2 a = reinterpret_cast<const f64x2*>(xk)[uc], c = reinterpret_cast<const f64x2*>(sj)[uc],
-                  d = reinterpret_cast<const f64x2*>(q)[uc];
-      xv[0] = a.x; xv[1] = a.y; sv[0] = c.x; sv[1] = c.y; qv[0] = d.x; qv[1] = d.y;
-      if (from_y) { const f64x2 p = reinterpret_cast<const f64x2*>(y)[uc]; pv[0] = p.x; pv[1] = p.y; }
-      if (2 * u == n - 1) {
-        xv[0] = xk[n - 1]; sv[0] = sj[n - 1]; qv[0] = q[n - 1];
-        if (from_y) pv[0] = y[n - 1];
-      }
-    } else {
-      xv[0] = xk[uc]; sv[0] = sj[uc]; qv[0] = q[uc];
-      if (from_y) pv[0] = y[uc];
-    }
+    if (from_y) {
+      const double* const in[4] = {xk, sj, q, y};
+      double w[4][E];
+      row_load_unit<PAIRS>(in, u, ufull, n, w);
 #pragma unroll
-    for (int e = 0; e < E; ++e) {
-      xs[e] = xv[e] + sv[e];
-      v[e] = from_y ? pv[e] : xs[e] + qs * qv[e];
-    }
-  };
-  // row walk: the parked v of unit u
-  auto load_y = [&](int u, double (&v)[E]) {
-    const int uc = u < ufull ? u : ufull - 1;
-    if constexpr (PAIRS) {
-      const f64x2 p = reinterpret_cast<const f64x2*>(y)[uc];
-      v[0] = p.x; v[1] = p.y;
-      if (2 * u == n - 1) v[0] = y[n - 1];
+      for (int e = 0; e < E; ++e) { xs[e] = w[0][e] + w[1][e]; qv[e] = w[2][e]; v[e] = w[3][e]; }
     } else {
-      v[0] = y[uc];
+      const double* const in[3] = {xk, sj, q};
+      double w[3][E];
+      row_load_unit<PAIRS>(in, u, ufull, n, w);
+#pragma unroll
+      for (int e = 0; e < E; ++e) { xs[e] = w[0][e] + w[1][e]; qv[e] = w[2][e]; v[e] = xs[e] + qs * qv[e]; }
     }
   };
+  // row walk: v of unit u goes to the row of y
   auto park = [&](int u, const double (&v)[E]) {
-    if (u >= utot) return;
-    if (PAIRS && u < ufull) reinterpret_cast<f64x2*>(y)[u] = f64x2{v[0], v[E - 1]};
-    else y[u * E] = v[0];
+    if (u < utot) row_store_y<PAIRS>(y, u, u < ufull, v[0], v[E - 1]);
   };
   uint64_t kmin = ~0ull, kmax = 0ull;
   auto track = [&](int u, const double (&v)[E]) {
@@ -209,7 +172,7 @@ __global__ __launch_bounds__(LANES) void k_topr_batch(ToprBatchArgs k) {
 #pragma unroll
     for (int kk = 0; kk < UPL; ++kk) {
       double v[E], xs[E], qv[E];
-      const int u = (int)topr_batch_unit(kk, LANES, t);
+      const int u = (int)row_batch_unit(kk, LANES, t);
       load_in(u, v, xs, qv, false);
       track(u, v);
 #pragma unroll
@@ -259,15 +222,16 @@ __global__ __launch_bounds__(LANES) void k_topr_batch(ToprBatchArgs k) {
         double v[E];
 #pragma unroll
         for (int e = 0; e < E; ++e) v[e] = V[kk * E + e];
-        count_unit(st, (int)topr_batch_unit(kk, LANES, t), v);
+        count_unit(st, (int)row_batch_unit(kk, LANES, t), v);
       }
     } else {
       for (int base = 0; base < utot; base += LANES * WU) {
-        double v[WU][E];
+        const double* const parked[1] = {y};  // the row walk reads v where pass 0 left it
+        double v[WU][1][E];
 #pragma unroll
-        for (int j = 0; j < WU; ++j) load_y(base + j * LANES + t, v[j]);
+        for (int j = 0; j < WU; ++j) row_load_unit<PAIRS>(parked, base + j * LANES + t, ufull, n, v[j]);
 #pragma unroll
-        for (int j = 0; j < WU; ++j) count_unit(st, base + j * LANES + t, v[j]);
+        for (int j = 0; j < WU; ++j) count_unit(st, base + j * LANES + t, v[j][0]);
       }
     }
     __syncthreads();
@@ -292,19 +256,16 @@ __global__ __launch_bounds__(LANES) void k_topr_batch(ToprBatchArgs k) {
     if (PAIRS && u < ufull) {
       const f64x2 o{outv(v[0], xs[0], 2 * u), outv(v[E - 1], xs[E - 1], 2 * u + 1)};
       const f64x2 w{xs[0] + o.x, xs[E - 1] + o.y};
-      reinterpret_cast<f64x2*>(y)[u] = o;
-      if (xkn != nullptr) {
-        if (k.xkn_pairs) reinterpret_cast<f64x2*>(xkn)[u] = w;
-        else { xkn[2 * u] = w.x; xkn[2 * u + 1] = w.y; }
-      }
+      row_store_y<PAIRS>(y, u, true, o.x, o.y);
+      row_store_xkn<PAIRS>(xkn, k.xkn_pairs, u, true, w.x, w.y);
       sums(qv[0], w.x, o.x);
       sums(qv[E - 1], w.y, o.y);
     } else {  // one element: the element-wise form, or the last element of an odd row
       const int i = u * E;
       const double o = outv(v[0], xs[0], i);
       const double w = xs[0] + o;
-      y[i] = o;
-      if (xkn != nullptr) xkn[i] = w;
+      row_store_y<PAIRS>(y, u, false, o, o);
+      row_store_xkn<PAIRS>(xkn, k.xkn_pairs, u, false, w, w);
       sums(qv[0], w, o);
     }
   };
@@ -314,7 +275,7 @@ __global__ __launch_bounds__(LANES) void k_topr_batch(ToprBatchArgs k) {
       double v[E], xs[E], qv[E];
 #pragma unroll
       for (int e = 0; e < E; ++e) { v[e] = V[kk * E + e]; xs[e] = XS[kk * E + e]; qv[e] = Q[kk * E + e]; }
-      store_unit((int)topr_batch_unit(kk, LANES, t), v, xs, qv);
+      store_unit((int)row_batch_unit(kk, LANES, t), v, xs, qv);
     }
   } else {
     for (int base = 0; base < utot; base += LANES * WU) {
@@ -325,7 +286,7 @@ __global__ __launch_bounds__(LANES) void k_topr_batch(ToprBatchArgs k) {
       for (int j = 0; j < WU; ++j) store_unit(base + j * LANES + t, v[j], xs[j], qv[j]);
     }
   }
-  topr_block_sum(h, lds);
+  row_block_sum<3>(h, lds);
   if (t == 0) {
     k.stats[3 * b] = h[0];
     k.stats[3 * b + 1] = h[1];
@@ -333,74 +294,43 @@ __global__ __launch_bounds__(LANES) void k_topr_batch(ToprBatchArgs k) {
   }
 }
 
-template <int LANES, int EPL, bool REG, bool BINF>
-void topr_batch_launch(spx_ctx* ctx, const ToprBatchPlan& p, const ToprBatchArgs& a) {
-  if (p.pairs) hipLaunchKernelGGL((k_topr_batch<LANES, EPL, REG, true, BINF>), dim3((unsigned)p.grid), dim3(LANES), 0, ctx->stream, a);
-  else hipLaunchKernelGGL((k_topr_batch<LANES, EPL, REG, false, BINF>), dim3((unsigned)p.grid), dim3(LANES), 0, ctx->stream, a);
-}
-template <int TILE, bool BINF>
-void topr_batch_launch_tile(spx_ctx* ctx, const ToprBatchPlan& p, const ToprBatchArgs& a) {
-  if constexpr (TILE < kToprBatchTileCount) {
-    if (p.tile == TILE) topr_batch_launch<kToprBatchTiles[TILE].lanes, kToprBatchTiles[TILE].epl, true, BINF>(ctx, p, a);
-    else topr_batch_launch_tile<TILE + 1, BINF>(ctx, p, a);
-  }
-}
-
-// Every refusal is made before anything is enqueued.  There is no host destination: the call only enqueues.
+// what differs from the other row-owner calls on the host (run_row_batch, spx_row_batch.hpp)
 template <bool BINF>
-int topr_batch_run(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n, int64_t batch, int64_t ld,
-                   const int64_t* r, const double* delta, const double* q_scale, double* xkn, double* stats_dev) {
-  // the libraries share spx_ctx and four functions: refuse to touch a context of a libspx.so built from other sources
-  if (spx_shared_abi() != kSpxSharedAbi) {
-    spx_set_error("libspx_topr_batch.so and libspx.so do not match (shared layout %d, expected %d): rebuild both", spx_shared_abi(),
-                  kSpxSharedAbi);
-    return SPX_ERR_INTERNAL;
+struct ToprBatchKind {
+  static constexpr const char* kLibName = "libspx_topr_batch.so";
+  static constexpr RowBatchShape kShape = kToprBatchShape;
+  struct Params {
+    const int64_t* r;
+    const double *delta, *q_scale;  // delta: NULL in the plain form
+  };
+  static bool null_params(const Params& a) { return a.r == nullptr || a.q_scale == nullptr || (BINF && a.delta == nullptr); }
+  static constexpr const char* kNullParams = BINF ? "a parameter array (r, delta, q_scale) is NULL" : "a parameter array (r, q_scale) is NULL";
+  static const char* refuse_alias(const RowBatchCall& c) {
+    return c.y != c.xk && c.y != c.sj ? nullptr : "y is xk or sj (v is parked in the row of y between the digit passes)";
   }
-  SPX_REQUIRE(ctx != nullptr, "ctx is NULL");
-  SPX_REQUIRE(n >= 0, "n < 0");
-  SPX_REQUIRE(batch >= 0, "batch < 0");
-  if (batch == 0) return SPX_OK;
-  SPX_REQUIRE(stats_dev != nullptr, "stats_dev is NULL");
-  SPX_REQUIRE(r != nullptr && q_scale != nullptr && (!BINF || delta != nullptr),
-              BINF ? "a parameter array (r, delta, q_scale) is NULL" : "a parameter array (r, q_scale) is NULL");
-  SPX_REQUIRE(ld >= n, "ld < n");
-  const void* const in[4] = {y, q, xk, sj};
-  if (n > 0) {
-    for (const void* v : in) SPX_REQUIRE(v != nullptr, "NULL vector with n > 0");
-    SPX_REQUIRE(y != q, kSpxYAliasesQ);
-    SPX_REQUIRE(y != xk && y != sj, "y is xk or sj (v is parked in the row of y between the digit passes)");
-    if (xkn != nullptr) {
-      for (const void* o : in) SPX_REQUIRE(xkn != o, "xkn is one of the other vectors");
-    }
+  static constexpr const char* kNTooLarge =
+      BINF ? "n > 2^20: one workgroup per problem is the wrong tool (spx_prox_indball_l0_binf spreads such a problem over many "
+             "CUs, one problem per call)"
+           : "n > 2^20: one workgroup per problem is the wrong tool (spx_prox_indball_l0 spreads such a problem over many CUs, "
+             "one problem per call)";
+  template <int LANES, int EPL, bool REG, bool PAIRS>
+  static void launch(const RowBatchCall& c, const Params& a, const RowBatchPlan& p) {
+    hipLaunchKernelGGL((k_topr_batch<LANES, EPL, REG, PAIRS, BINF>), dim3((unsigned)p.grid), dim3(LANES), 0, c.ctx->stream,
+                       ToprBatchArgs{c.y, c.q, c.xk, c.sj, c.xkn, a.r, a.delta, a.q_scale, c.ld, (int)c.n, p.xkn_pairs ? 1 : 0,
+                                     c.stats_dev});
   }
-  int bits = spx_aligned16(xkn) ? 0 : 1 << 4;
-  for (int v = 0; v < 4; ++v) bits |= spx_aligned16(in[v]) ? 0 : 1 << v;
-  const ToprBatchPlan p = topr_batch_plan(n, batch, ld, bits);
-  SPX_REQUIRE(p.ok || p.why != ToprBatchRefusal::kNTooLarge,
-              BINF ? "n > 2^20: one workgroup per problem is the wrong tool (spx_prox_indball_l0_binf spreads such a problem over many "
-                     "CUs, one problem per call)"
-                   : "n > 2^20: one workgroup per problem is the wrong tool (spx_prox_indball_l0 spreads such a problem over many CUs, "
-                     "one problem per call)");
-  SPX_REQUIRE(p.ok, "batch > 2^31 - 1");
-  SPX_ON_DEVICE(ctx);
-  if (n == 0) return spx_zero_async(ctx, stats_dev, (size_t)batch * 3 * sizeof(double));  // zeros for every problem, by a kernel
-  const ToprBatchArgs a{y, q, xk, sj, xkn, r, delta, q_scale, ld, (int)n, p.xkn_pairs ? 1 : 0, stats_dev};
-  if (p.form == ToprBatchForm::kResident) topr_batch_launch_tile<0, BINF>(ctx, p, a);
-  else topr_batch_launch<kToprBatchWalkLanes, 0, false, BINF>(ctx, p, a);
-  SPX_LAUNCH_CHECK();
-  return SPX_OK;
-}
+};
 
 }  // namespace
 
 SPX_EXPORT int spx_proxstep_indball_l0_batch(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj, int64_t n,
                                              int64_t batch, int64_t ld, const int64_t* r, const double* q_scale, double* xkn,
                                              double* stats_dev) {
-  return topr_batch_run<false>(ctx, y, q, xk, sj, n, batch, ld, r, nullptr, q_scale, xkn, stats_dev);
+  return run_row_batch<ToprBatchKind<false>>({ctx, y, q, xk, sj, n, batch, ld, xkn, stats_dev}, {r, nullptr, q_scale});
 }
 
 SPX_EXPORT int spx_proxstep_indball_l0_binf_batch(spx_ctx* ctx, double* y, const double* q, const double* xk, const double* sj,
                                                   int64_t n, int64_t batch, int64_t ld, const int64_t* r, const double* delta,
                                                   const double* q_scale, double* xkn, double* stats_dev) {
-  return topr_batch_run<true>(ctx, y, q, xk, sj, n, batch, ld, r, delta, q_scale, xkn, stats_dev);
+  return run_row_batch<ToprBatchKind<true>>({ctx, y, q, xk, sj, n, batch, ld, xkn, stats_dev}, {r, delta, q_scale});
 }

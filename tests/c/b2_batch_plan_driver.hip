@@ -1,10 +1,7 @@
 /* Stand-alone driver for the device-free parts of the batched ShiftedNormL1B2 call (spx_proxstep_l1_b2_batch):
- *   no argument : b2_batch_plan (csrc/spx_plan.hpp) over a grid of n, batch, ld and alignment bits --
- *     - the lane slots of the plan's workgroup, walked as k_b2_batch of csrc/spx_b2_batch.hip walks them (b2_batch_unit,
- *       b2_batch_units), visit every element of a row exactly once and nothing beyond it;
- *     - a resident tile holds the row, and the tile before it would not; the form, the tile and the lanes depend on n alone,
- *       pairs on (n >= 2, the parity of ld, the alignment bits of y, q, xk, sj) alone, xkn_pairs on xkn's bit besides;
- *     - n = kB2BatchNMax and batch = 2^31 - 1 are accepted, one more of either is refused, each with its own reason.
+ *   no argument : row_batch_plan (csrc/spx_plan.hpp) on kB2BatchShape over a grid of n, batch, ld and alignment bits: the checks
+ *     of tests/c/row_batch_plan_checks.hpp (the cover of a row by the lane slots as k_b2_batch of csrc/spx_b2_batch.hip walks
+ *     them, the tile choice, what form and pairs depend on, the refusals at kB2BatchNMax + 1 and batch = 2^31).
  *   rows IN OUT : the step rule of csrc/spx_b2_row.hpp (b2_row_begin, b2_row_step, b2_row_scales) on the rows of the binary file
  *     IN, every sum a plain sequential loop on the host with the element expressions of the kernel.  IN: int64 rows, then per
  *     row int64 n, double lambda, sigma, delta, q_scale, chi_lambda, then q[n], xk[n], sj[n].  OUT: per row int64 reductions,
@@ -30,94 +27,15 @@ static int g_fail = 0;
     if (!(cond)) { if (g_fail < 20) printf("FAILED line %d: %s\n", __LINE__, #cond); ++g_fail; } \
   } while (0)
 
-// ---- (a) the plan -------------------------------------------------------------------------------
-// every (lane, slot) of the plan's workgroup -> its unit -> the elements of the row it covers
-static void check_cover(int64_t n, const B2BatchPlan& p, std::vector<unsigned char>& seen) {
-  const int E = b2_batch_unit_elems(p.pairs);
-  const int64_t utot = b2_batch_units(n, p.pairs);
-  int64_t slots;
-  if (p.form == B2BatchForm::kResident) {
-    slots = p.epl / E;
-  } else {  // the row walk: whole rounds of kB2BatchWalkUnroll units per lane until the row is covered
-    const int64_t round = (int64_t)p.lanes * kB2BatchWalkUnroll;
-    slots = (utot + round - 1) / round * kB2BatchWalkUnroll;
-  }
-  seen.assign((size_t)n, 0);
-  long beyond = 0, twice = 0;
-  for (int t = 0; t < p.lanes; ++t)
-    for (int64_t k = 0; k < slots; ++k) {
-      const int64_t u = b2_batch_unit(k, p.lanes, t);
-      if (u >= utot) continue;  // an idle slot: zeros
-      for (int e = 0; e < E; ++e) {
-        const int64_t i = u * E + e;
-        if (i >= n) { if (!(p.pairs && e == 1 && i == n)) ++beyond; continue; }  // (the missing half of an odd row's last unit)
-        if (seen[(size_t)i]++) ++twice;
-      }
-    }
-  long missed = 0;
-  for (int64_t i = 0; i < n; ++i) missed += seen[(size_t)i] == 0;
-  CHECK(beyond == 0);
-  CHECK(twice == 0);
-  CHECK(missed == 0);
-}
+// ---- (a) the plan: the checks every row-owner call shares, on this call's shape ---------------------
+#include "row_batch_plan_checks.hpp"
 
 static int run_plan_checks() {
-  std::vector<int64_t> ns = {1, 2, 3, 7, 63, 64, 65, 1000, 5000, 10000, 12289, 100000, 1000003};
-  for (int i = 0; i < kB2BatchTileCount; ++i) {
-    const int64_t cap = (int64_t)kB2BatchTiles[i].lanes * kB2BatchTiles[i].epl;
-    for (int64_t d = -2; d <= 2; ++d) ns.push_back(cap + d);
-  }
-  for (int64_t d = -1; d <= 2; ++d) ns.push_back(kB2BatchRowMax + d);
-  ns.push_back(2 * kB2BatchRowMax + 3);
-  for (int64_t d = -2; d <= 0; ++d) ns.push_back(kB2BatchNMax + d);
-  for (int64_t m = 1; m <= 3; ++m)  // around whole rounds of the row walk
-    for (int64_t d = -1; d <= 1; ++d) ns.push_back(4 * m * kB2BatchWalkLanes * kB2BatchWalkUnroll + d);
-  const int64_t batches[] = {1, 2, 3, 7, 256, 70001, kBatchGridMax};
-  const int64_t pads[] = {0, 1, 2, 5};
-  std::vector<unsigned char> seen;
-  for (int64_t n : ns) {
-    const B2BatchPlan ref = b2_batch_plan(n, 1, n, 0);
-    CHECK(ref.ok);
-    for (int64_t batch : batches)
-      for (int64_t pad : pads)
-        for (int bits = 0; bits < 32; ++bits) {
-          const int64_t ld = n + pad;
-          const B2BatchPlan p = b2_batch_plan(n, batch, ld, bits);
-          CHECK(p.ok && p.why == B2BatchRefusal::kNone);
-          CHECK(p.grid == batch);
-          // the form is a function of n alone, pairs of the alignment class
-          CHECK(p.form == ref.form && p.tile == ref.tile && p.lanes == ref.lanes && p.epl == ref.epl);
-          CHECK(p.pairs == ((bits & 15) == 0 && (ld & 1) == 0 && n >= 2));
-          CHECK(p.xkn_pairs == (p.pairs && (bits & 16) == 0));
-          CHECK((p.form == B2BatchForm::kResident) == (n <= kB2BatchRowMax));
-          if (p.form == B2BatchForm::kResident) {
-            CHECK(p.tile >= 0 && p.tile < kB2BatchTileCount);
-            CHECK(p.lanes == kB2BatchTiles[p.tile].lanes && p.epl == kB2BatchTiles[p.tile].epl);
-            CHECK((int64_t)p.lanes * p.epl >= n);
-            if (p.tile > 0) CHECK((int64_t)kB2BatchTiles[p.tile - 1].lanes * kB2BatchTiles[p.tile - 1].epl < n);
-            CHECK(p.epl % 2 == 0 && p.lanes % 64 == 0 && p.lanes <= 1024);
-          } else {
-            CHECK(p.lanes == kB2BatchWalkLanes && p.tile == -1);
-          }
-        }
-    // the cover, once per alignment class (it does not depend on batch)
-    for (int cls = 0; cls < 2; ++cls) {
-      const B2BatchPlan p = b2_batch_plan(n, 3, n + (n & 1), cls ? 1 : 0);
-      CHECK(p.pairs == (cls == 0 && n >= 2));
-      check_cover(n, p, seen);
-    }
-  }
-  // the bounds
-  CHECK(kB2BatchNMax == ((int64_t)1 << 20) && kB2BatchRowMax == 8192);
-  CHECK(b2_batch_plan(kB2BatchNMax, kBatchGridMax, kB2BatchNMax, 0).ok);
-  {
-    const B2BatchPlan p = b2_batch_plan(kB2BatchNMax + 1, 1, kB2BatchNMax + 1, 0);
-    CHECK(!p.ok && p.why == B2BatchRefusal::kNTooLarge);
-    const B2BatchPlan g = b2_batch_plan(5, kBatchGridMax + 1, 5, 0);
-    CHECK(!g.ok && g.why == B2BatchRefusal::kBatchTooLarge);
-    const B2BatchPlan h = b2_batch_plan(INT64_MAX, INT64_MAX, INT64_MAX, 31);
-    CHECK(!h.ok);
-  }
+  run_row_batch_plan_checks(kB2BatchShape);
+  // the shape is the named constants
+  CHECK(kB2BatchShape.tiles == kB2BatchTiles && kB2BatchShape.tile_count == kB2BatchTileCount);
+  CHECK(kB2BatchShape.row_max == kB2BatchRowMax && kB2BatchShape.n_max == kB2BatchNMax);
+  CHECK(kB2BatchShape.walk_lanes == kB2BatchWalkLanes && kB2BatchShape.walk_unroll == kB2BatchWalkUnroll);
   printf("%ld checks\n", g_checked);
   if (g_fail) { printf("%d FAILED\n", g_fail); return 1; }
   printf("ok\n");

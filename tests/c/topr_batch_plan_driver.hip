@@ -1,10 +1,7 @@
 /* Stand-alone driver for the device-free parts of the batched top-r calls (spx_proxstep_indball_l0[_binf]_batch):
- *   (a) topr_batch_plan (csrc/spx_plan.hpp) over a grid of n, batch, ld and alignment bits --
- *     - the lane slots of the plan's workgroup, walked as k_topr_batch of csrc/spx_topr_batch.hip walks them (topr_batch_unit,
- *       topr_batch_units), visit every element of a row exactly once and nothing beyond it;
- *     - a resident tile holds the row, and the tile before it would not; the form, the tile and the lanes depend on n alone,
- *       pairs on (n >= 2, the parity of ld, the alignment bits of y, q, xk, sj) alone, xkn_pairs on xkn's bit besides;
- *     - n = kToprBatchNMax and batch = 2^31 - 1 are accepted, one more of either is refused, each with its own reason.
+ *   (a) row_batch_plan (csrc/spx_plan.hpp) on kToprBatchShape over a grid of n, batch, ld and alignment bits: the checks of
+ *     tests/c/row_batch_plan_checks.hpp (the cover of a row by the lane slots as k_topr_batch of csrc/spx_topr_batch.hip walks
+ *     them, the tile choice, what form and pairs depend on, the refusals at kToprBatchNMax + 1 and batch = 2^31).
  *   (b) the selection of csrc/spx_topr_row.hpp (topr_key, topr_row_begin, topr_row_digit, topr_row_step, topr_row_keep) on host
  *     arrays, every histogram a plain loop: the kept set against a STABLE descending sort by |v| (NaN above Inf, all NaNs equal),
  *     for every r in {-1, 0, 1, ..., n, n + 1}, on random values, a constant with alternating sign, a 2^-8 lattice, values over
@@ -32,98 +29,15 @@ static int g_fail = 0;
     if (!(cond)) { if (g_fail < 20) printf("FAILED line %d: %s\n", __LINE__, #cond); ++g_fail; } \
   } while (0)
 
-// ---- (a) the plan -------------------------------------------------------------------------------
-// every (lane, slot) of the plan's workgroup -> its unit -> the elements of the row it covers
-static void check_cover(int64_t n, const ToprBatchPlan& p, std::vector<unsigned char>& seen) {
-  const int E = p.pairs ? 2 : 1;
-  const int64_t utot = topr_batch_units(n, p.pairs);
-  int64_t slots;
-  if (p.form == ToprBatchForm::kResident) {
-    slots = p.epl / E;
-  } else {  // the row walk: whole rounds of kToprBatchWalkUnroll units per lane until the row is covered
-    const int64_t round = (int64_t)p.lanes * kToprBatchWalkUnroll;
-    slots = (utot + round - 1) / round * kToprBatchWalkUnroll;
-  }
-  seen.assign((size_t)n, 0);
-  long beyond = 0, twice = 0;
-  for (int t = 0; t < p.lanes; ++t)
-    for (int64_t k = 0; k < slots; ++k) {
-      const int64_t u = topr_batch_unit(k, p.lanes, t);
-      if (u >= utot) continue;  // an idle slot
-      for (int e = 0; e < E; ++e) {
-        const int64_t i = u * E + e;
-        if (i >= n) { if (!(p.pairs && e == 1 && i == n)) ++beyond; continue; }  // (the missing half of an odd row's last unit)
-        if (seen[(size_t)i]++) ++twice;
-      }
-    }
-  long missed = 0;
-  for (int64_t i = 0; i < n; ++i) missed += seen[(size_t)i] == 0;
-  CHECK(beyond == 0);
-  CHECK(twice == 0);
-  CHECK(missed == 0);
-}
+// ---- (a) the plan: the checks every row-owner call shares, on this call's shape ---------------------
+#include "row_batch_plan_checks.hpp"
 
 static void run_plan_checks() {
-  std::vector<int64_t> ns = {0, 1, 2, 3, 7, 63, 64, 65, 1000, 5000, 10000, 100000, 1000003};
-  for (int i = 0; i < kToprBatchTileCount; ++i) {
-    const int64_t cap = (int64_t)kToprBatchTiles[i].lanes * kToprBatchTiles[i].epl;
-    for (int64_t d = -1; d <= 1; ++d) ns.push_back(cap + d);
-  }
-  for (int64_t d = -1; d <= 2; ++d) ns.push_back(kToprBatchRowMax + d);
-  ns.push_back(2 * kToprBatchRowMax + 3);
-  for (int64_t d = -2; d <= 0; ++d) ns.push_back(kToprBatchNMax + d);
-  for (int64_t m = 1; m <= 3; ++m)  // around whole rounds of the row walk
-    for (int64_t d = -1; d <= 1; ++d) ns.push_back(4 * m * kToprBatchWalkLanes * kToprBatchWalkUnroll + d);
-  const int64_t batches[] = {1, 2, 3, 7, 256, 70001, kBatchGridMax};
-  const int64_t pads[] = {0, 1, 2, 5};
-  std::vector<unsigned char> seen;
-  for (int64_t n : ns) {
-    const ToprBatchPlan ref = topr_batch_plan(n, 1, n, 0);
-    CHECK(ref.ok);
-    for (int64_t batch : batches)
-      for (int64_t pad : pads)
-        for (int bits = 0; bits < 32; ++bits) {  // all 32 alignment classes; pads 1 and 5 give odd ld for even n and the reverse
-          const int64_t ld = n + pad;
-          const ToprBatchPlan p = topr_batch_plan(n, batch, ld, bits);
-          CHECK(p.ok && p.why == ToprBatchRefusal::kNone);
-          CHECK(p.grid == batch);
-          // the form is a function of n alone (not of batch, ld or the alignment), pairs of the alignment class
-          CHECK(p.form == ref.form && p.tile == ref.tile && p.lanes == ref.lanes && p.epl == ref.epl);
-          CHECK(p.pairs == ((bits & 15) == 0 && (ld & 1) == 0 && n >= 2));
-          CHECK(p.xkn_pairs == (p.pairs && (bits & 16) == 0));
-          CHECK((p.form == ToprBatchForm::kResident) == (n <= kToprBatchRowMax));
-          if (p.form == ToprBatchForm::kResident) {
-            CHECK(p.tile >= 0 && p.tile < kToprBatchTileCount);
-            CHECK(p.lanes == kToprBatchTiles[p.tile].lanes && p.epl == kToprBatchTiles[p.tile].epl);
-            CHECK((int64_t)p.lanes * p.epl >= n);
-            if (p.tile > 0) CHECK((int64_t)kToprBatchTiles[p.tile - 1].lanes * kToprBatchTiles[p.tile - 1].epl < n);
-            CHECK(p.epl % 2 == 0 && p.lanes % 64 == 0 && p.lanes <= 1024);
-          } else {
-            CHECK(p.lanes == kToprBatchWalkLanes && p.tile == -1 && p.epl == 0);
-          }
-        }
-    // the cover, once per alignment class (it does not depend on batch)
-    for (int cls = 0; cls < 2; ++cls) {
-      const ToprBatchPlan p = topr_batch_plan(n, 3, n + (n & 1), cls ? 1 : 0);
-      CHECK(p.pairs == (cls == 0 && n >= 2));
-      check_cover(n, p, seen);
-    }
-  }
-  // the tiles: a row of 1e3 does not take a CU-wide workgroup, the largest tile is the resident bound
-  CHECK(topr_batch_plan(1000, 1, 1000, 0).lanes == 256 && topr_batch_plan(256, 1, 256, 0).lanes == 64);
-  CHECK((int64_t)kToprBatchTiles[kToprBatchTileCount - 1].lanes * kToprBatchTiles[kToprBatchTileCount - 1].epl == kToprBatchRowMax);
-  CHECK(topr_batch_plan(8192, 9, 8192, 0).form == ToprBatchForm::kResident && topr_batch_plan(8193, 9, 8194, 0).form == ToprBatchForm::kWalk);
-  // the bounds
-  CHECK(kToprBatchNMax == ((int64_t)1 << 20) && kToprBatchRowMax == 8192);
-  CHECK(topr_batch_plan(kToprBatchNMax, kBatchGridMax, kToprBatchNMax, 0).ok);
-  {
-    const ToprBatchPlan p = topr_batch_plan(kToprBatchNMax + 1, 1, kToprBatchNMax + 1, 0);
-    CHECK(!p.ok && p.why == ToprBatchRefusal::kNTooLarge);
-    const ToprBatchPlan g = topr_batch_plan(5, kBatchGridMax + 1, 5, 0);
-    CHECK(!g.ok && g.why == ToprBatchRefusal::kBatchTooLarge);
-    const ToprBatchPlan h = topr_batch_plan(INT64_MAX, INT64_MAX, INT64_MAX, 31);
-    CHECK(!h.ok);
-  }
+  run_row_batch_plan_checks(kToprBatchShape);
+  // the shape is the named constants
+  CHECK(kToprBatchShape.tiles == kToprBatchTiles && kToprBatchShape.tile_count == kToprBatchTileCount);
+  CHECK(kToprBatchShape.row_max == kToprBatchRowMax && kToprBatchShape.n_max == kToprBatchNMax);
+  CHECK(kToprBatchShape.walk_lanes == kToprBatchWalkLanes && kToprBatchShape.walk_unroll == kToprBatchWalkUnroll);
 }
 
 // ---- (b) the selection -------------------------------------------------------------------------------

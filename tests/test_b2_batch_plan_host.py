@@ -2,7 +2,7 @@
 (tests/c/b2_batch_plan_driver.hip, its own main) built with AddressSanitizer + UBSan on the host side and run as a child.
 Nothing is put into LD_PRELOAD and the library is not loaded.
 
-(a) b2_batch_plan (csrc/spx_plan.hpp) over a grid of n, batch, ld and alignment bits: every element of every row is visited by
+(a) row_batch_plan on kB2BatchShape (csrc/spx_plan.hpp; tests/c/row_batch_plan_checks.hpp) over a grid of n, batch, ld and alignment bits: every element of every row is visited by
     exactly one lane slot, the form is a function of n and the alignment class alone, refusals come at the grid and n bounds.
 (b) the step rule of csrc/spx_b2_row.hpp -- the one k_b2_batch runs -- on the host with plain sequential sums, on Gaussian,
     integer-lattice and sparse rows with the trust region active, barely active (Delta = 0.9 ||xk||) and inactive: y against

@@ -106,8 +106,9 @@ def test_library_links_against_libspx_and_reserves_no_workspace(built):
                                text=True).stdout
     assert "spx_set_error" in undefined and "spx_zero_async" in undefined   # what it takes from libspx.so ...
     assert "spx_ws_reserve" not in undefined                                # ... and what it does not: workspace NONE
-    src = open(os.path.join(ROOT, "shiftedproximaloperators.jl_amd", "csrc", "spx_topr_batch.hip")).read()
-    assert "spx_ws_reserve(" not in src and "hipMemsetAsync" not in src and "ctx->sync" not in src
+    for name in ("spx_topr_batch.hip", "spx_row_batch.hpp"):     # the call's own file and the row-owner site it shares
+        src = open(os.path.join(ROOT, "shiftedproximaloperators.jl_amd", "csrc", name)).read()
+        assert "spx_ws_reserve(" not in src and "hipMemsetAsync" not in src and "ctx->sync" not in src, name
 
 
 def test_ctypes_table_binds_the_calls(built):

@@ -2,7 +2,7 @@
 (tests/c/topr_batch_plan_driver.hip, its own main) built with AddressSanitizer + UBSan on the host side and run as a child.
 Nothing is put into LD_PRELOAD and the library is not loaded.
 
-(a) topr_batch_plan (csrc/spx_plan.hpp) at n = 0, 1, 2, every tile edge +-1, 8192, 8193, 2^20 and 2^20 + 1, over all 32 alignment
+(a) row_batch_plan on kToprBatchShape (csrc/spx_plan.hpp; tests/c/row_batch_plan_checks.hpp) at n = 0, 1, 2, every tile edge +-1, 8192, 8193, 2^20 and 2^20 + 1, over all 32 alignment
     classes, even and odd ld and seven batch sizes: every element of every row is visited by exactly one lane slot, form and
     tile are functions of n alone, refusals come at the grid and n bounds.
 (b) the selection of csrc/spx_topr_row.hpp -- the one k_topr_batch runs -- on host arrays with histograms built by a plain loop:

@@ -18,7 +18,7 @@ driven through ctypes like every caller of the C ABI from Python: where its laun
 (b) measures that overhead -- which is what such a caller pays.  Before a shape is timed the rows of (a) are compared with the
 rows of (b): to 1e-12 max(||y||, ||xk||) per row where the trust region is active, bit for bit where it is not.
 
-    timeout -k 10 1100 python tools/b2_proxstep_batch_timing.py [--out profiles/b2_proxstep_batch_timing.txt] [--quick]
+    timeout -k 10 1100 python tools/b2_proxstep_batch_timing.py [--out profiles/b2_proxstep_batch_timing.txt] [--quick] [--only-a]
 
 One process, every status checked, no retry: a failing call ends the run with its message."""
 import argparse
@@ -34,6 +34,7 @@ import __graft_entry__ as ge
 ap = argparse.ArgumentParser()
 ap.add_argument("--out", default=None, help="also write the table to this file")
 ap.add_argument("--quick", action="store_true", help="small shapes and few rounds (a rehearsal of the tool, not a measurement)")
+ap.add_argument("--only-a", action="store_true", help="time leg (a) alone (A/B runs of two builds); the comparison with leg (b) before it stays")
 args = ap.parse_args()
 
 s = ge.build()
@@ -111,9 +112,11 @@ for n, batch in SHAPES:
         inner_a = max(5, min(200, 2_000_000_000 // (40 * n * batch)))
         inner_b = max(1, 2048 // batch)
         rounds = 3 if args.quick else 9
-        legs = [(leg_a, inner_a, []), (leg_b, inner_b, [])]
+        legs = [(leg_a, inner_a, []), (leg_b, 0 if args.only_a else inner_b, [0.0] if args.only_a else [])]
         for _ in range(rounds):                # the legs alternate: drift of the machine hits all alike
             for leg, inner, ts in legs:
+                if inner == 0:                 # --only-a: leg (b) is not timed, its columns read 0
+                    continue
                 ms = ctypes.c_float()
                 check_rc(L.spx_timer_start(ctx))
                 for _ in range(inner):
@@ -121,7 +124,7 @@ for n, batch in SHAPES:
                 check_rc(L.spx_timer_stop(ctx, ctypes.byref(ms)))
                 ts.append(1e3 * ms.value / inner)
         med = lambda ts: sorted(ts)[len(ts) // 2]
-        sprd = lambda ts: 100.0 * (max(ts) - min(ts)) / med(ts)
+        sprd = lambda ts: 100.0 * (max(ts) - min(ts)) / med(ts) if med(ts) else 0.0
         ta, tb = legs[0][2], legs[1][2]
         a, b = med(ta), med(tb)
         line = "%8d %6d %-8s %-9s %11.2f %7.1f%% %11.2f %7.1f%% %8.2f %11.0f" % (n, batch, tr, "resident" if n <= 8192 else "walk", a, sprd(ta),
