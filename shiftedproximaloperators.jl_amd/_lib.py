@@ -1,6 +1,7 @@
 """ctypes binding of libspx.so (include/spx.h).  There is NO fallback: if the HIP library is missing
 or no GPU is visible, the product path raises -- it never computes on the CPU."""
 import ctypes
+import functools
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -104,8 +105,7 @@ SIGNATURES = {
 SIGNATURES.update({"spx_host_" + k[4:]: list(v) for k, v in list(SIGNATURES.items())
                    if k.startswith(("spx_prox_", "spx_iprox_", "spx_obj_")) and not k.endswith("_f32")})
 
-# libspx_batch.so (include/spx_batch.h): the batched separable call, a library of its own that links against libspx.so
-BATCH_LIB_PATH = LIB_PATH[:-3] + "_batch.so"
+# include/spx_batch.h: the batched separable call
 BATCH_SIGNATURES = {
     "spx_proxstep_l1_batch": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p],
     "spx_proxstep_l0_batch": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p],
@@ -113,8 +113,7 @@ BATCH_SIGNATURES = {
     "spx_proxstep_l0_box_batch": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p],
 }
 
-# libspx_ibatch.so (include/spx_ibatch.h): the batched iprox! call, a third library that links against libspx.so
-IBATCH_LIB_PATH = LIB_PATH[:-3] + "_ibatch.so"
+# include/spx_ibatch.h: the batched iprox! call
 IBATCH_SIGNATURES = {
     "spx_iproxstep_l1_batch": [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p],
     "spx_iproxstep_l0_batch": [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p],
@@ -122,33 +121,28 @@ IBATCH_SIGNATURES = {
     "spx_iproxstep_l0_box_batch": [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _p],
 }
 
-# libspx_gbatch.so (include/spx_gbatch.h): the batched group call, a fourth library that links against libspx.so
-GBATCH_LIB_PATH = LIB_PATH[:-3] + "_gbatch.so"
+# include/spx_gbatch.h: the batched group call
 GBATCH_SIGNATURES = {
     "spx_proxstep_group_l2_batch": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _i64, _p, _p, _p, _p, _p],
 }
 
-# libspx_gbinf_batch.so (include/spx_gbinf_batch.h): the batched Binf group call, a fifth library that links against libspx.so
-GBINF_BATCH_LIB_PATH = LIB_PATH[:-3] + "_gbinf_batch.so"
+# include/spx_gbinf_batch.h: the batched Binf group call
 GBINF_BATCH_SIGNATURES = {
     "spx_proxstep_group_l2_binf_batch": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _i64, _p, _p, _p, _p, _p, _p],
 }
 
-# libspx_b2_batch.so (include/spx_b2_batch.h): the batched ShiftedNormL1B2 call, a sixth library that links against libspx.so
-B2_BATCH_LIB_PATH = LIB_PATH[:-3] + "_b2_batch.so"
+# include/spx_b2_batch.h: the batched ShiftedNormL1B2 call
 B2_BATCH_SIGNATURES = {
     "spx_proxstep_l1_b2_batch": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _d, _p, _p],
 }
 
-# libspx_topr_batch.so (include/spx_topr_batch.h): the batched top-r calls, a seventh library that links against libspx.so
-TOPR_BATCH_LIB_PATH = LIB_PATH[:-3] + "_topr_batch.so"
+# include/spx_topr_batch.h: the batched top-r calls
 TOPR_BATCH_SIGNATURES = {
     "spx_proxstep_indball_l0_batch": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p],
     "spx_proxstep_indball_l0_binf_batch": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p],
 }
 
-# libspx_lhalf_batch.so (include/spx_lhalf_batch.h): the batched RootNormLhalf(Box) calls, an eighth library that links against libspx.so
-LHALF_BATCH_LIB_PATH = LIB_PATH[:-3] + "_lhalf_batch.so"
+# include/spx_lhalf_batch.h: the batched RootNormLhalf(Box) calls
 LHALF_BATCH_SIGNATURES = {
     "spx_proxstep_lhalf_batch": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p],
     "spx_proxstep_lhalf_box_batch": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p],
@@ -184,144 +178,62 @@ def load():
     return _lib
 
 
-_batch = None
+# The batched libraries, in build order: file-name suffix -> ctypes table.  Each is a library of its own that links against
+# libspx.so ("A library of its own, and why"); everything else about one follows from its key: include/spx_<key>.h,
+# csrc/spx_<key>.hip, lib/libspx_<key>.so.  csrc/build.sh's BATCH_LIBS array names the same keys (tests/test_batch_libraries.py).
+BATCH_LIBRARIES = {
+    "batch": BATCH_SIGNATURES,
+    "ibatch": IBATCH_SIGNATURES,
+    "gbatch": GBATCH_SIGNATURES,
+    "gbinf_batch": GBINF_BATCH_SIGNATURES,
+    "b2_batch": B2_BATCH_SIGNATURES,
+    "topr_batch": TOPR_BATCH_SIGNATURES,
+    "lhalf_batch": LHALF_BATCH_SIGNATURES,
+}
 
 
-def load_batch():
-    """Load libspx_batch.so (after libspx.so, whose contexts and error text it shares).  Raises if it is missing."""
-    global _batch
-    if _batch is None:
+def batch_lib_path(key):
+    """lib/libspx_<key>.so -- for SPX_LIB_NAME=X.so: X_<key>.so"""
+    return LIB_PATH[:-3] + "_" + key + ".so"
+
+
+_batch_libs = {}
+
+
+def load_batch_library(key):
+    """Load libspx_<key>.so (after libspx.so, whose contexts and error text it shares).  Raises if it is missing."""
+    if key not in _batch_libs:
+        signatures, path = BATCH_LIBRARIES[key], batch_lib_path(key)  # KeyError for a library the table does not know
         load()
-        if not os.path.exists(BATCH_LIB_PATH):
-            raise ImportError("libspx_batch.so not found at %s -- build it with shiftedproximaloperators.jl_amd/csrc/build.sh; "
-                              "there is no CPU fallback" % BATCH_LIB_PATH)
-        L = ctypes.CDLL(BATCH_LIB_PATH)
-        for name, args in BATCH_SIGNATURES.items():
-            fn = getattr(L, name)
+        if not os.path.exists(path):
+            raise ImportError("libspx_%s.so not found at %s -- build it with shiftedproximaloperators.jl_amd/csrc/build.sh; "
+                              "there is no CPU fallback" % (key, path))
+        L = ctypes.CDLL(path)
+        for name, args in signatures.items():
+            fn = getattr(L, name)  # AttributeError if the .so lacks a declared symbol
             fn.argtypes = args
             fn.restype = _int
-        _batch = L
-    return _batch
+        _batch_libs[key] = L
+    return _batch_libs[key]
 
 
-_ibatch = None
+# the names shifted.py, tests/ and tools/ use: one line each, defined from the table
+BATCH_LIB_PATH = batch_lib_path("batch")
+IBATCH_LIB_PATH = batch_lib_path("ibatch")
+GBATCH_LIB_PATH = batch_lib_path("gbatch")
+GBINF_BATCH_LIB_PATH = batch_lib_path("gbinf_batch")
+B2_BATCH_LIB_PATH = batch_lib_path("b2_batch")
+TOPR_BATCH_LIB_PATH = batch_lib_path("topr_batch")
+LHALF_BATCH_LIB_PATH = batch_lib_path("lhalf_batch")
 
 
-def load_ibatch():
-    """Load libspx_ibatch.so (after libspx.so, whose contexts and error text it shares).  Raises if it is missing."""
-    global _ibatch
-    if _ibatch is None:
-        load()
-        if not os.path.exists(IBATCH_LIB_PATH):
-            raise ImportError("libspx_ibatch.so not found at %s -- build it with shiftedproximaloperators.jl_amd/csrc/build.sh; "
-                              "there is no CPU fallback" % IBATCH_LIB_PATH)
-        L = ctypes.CDLL(IBATCH_LIB_PATH)
-        for name, args in IBATCH_SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.argtypes = args
-            fn.restype = _int
-        _ibatch = L
-    return _ibatch
-
-
-_gbatch = None
-
-
-def load_gbatch():
-    """Load libspx_gbatch.so (after libspx.so, whose contexts and error text it shares).  Raises if it is missing."""
-    global _gbatch
-    if _gbatch is None:
-        load()
-        if not os.path.exists(GBATCH_LIB_PATH):
-            raise ImportError("libspx_gbatch.so not found at %s -- build it with shiftedproximaloperators.jl_amd/csrc/build.sh; "
-                              "there is no CPU fallback" % GBATCH_LIB_PATH)
-        L = ctypes.CDLL(GBATCH_LIB_PATH)
-        for name, args in GBATCH_SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.argtypes = args
-            fn.restype = _int
-        _gbatch = L
-    return _gbatch
-
-
-_gbinf_batch = None
-
-
-def load_gbinf_batch():
-    """Load libspx_gbinf_batch.so (after libspx.so, whose contexts and error text it shares).  Raises if it is missing."""
-    global _gbinf_batch
-    if _gbinf_batch is None:
-        load()
-        if not os.path.exists(GBINF_BATCH_LIB_PATH):
-            raise ImportError("libspx_gbinf_batch.so not found at %s -- build it with shiftedproximaloperators.jl_amd/csrc/build.sh; "
-                              "there is no CPU fallback" % GBINF_BATCH_LIB_PATH)
-        L = ctypes.CDLL(GBINF_BATCH_LIB_PATH)
-        for name, args in GBINF_BATCH_SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.argtypes = args
-            fn.restype = _int
-        _gbinf_batch = L
-    return _gbinf_batch
-
-
-_b2_batch = None
-
-
-def load_b2_batch():
-    """Load libspx_b2_batch.so (after libspx.so, whose contexts and error text it shares).  Raises if it is missing."""
-    global _b2_batch
-    if _b2_batch is None:
-        load()
-        if not os.path.exists(B2_BATCH_LIB_PATH):
-            raise ImportError("libspx_b2_batch.so not found at %s -- build it with shiftedproximaloperators.jl_amd/csrc/build.sh; "
-                              "there is no CPU fallback" % B2_BATCH_LIB_PATH)
-        L = ctypes.CDLL(B2_BATCH_LIB_PATH)
-        for name, args in B2_BATCH_SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.argtypes = args
-            fn.restype = _int
-        _b2_batch = L
-    return _b2_batch
-
-
-_topr_batch = None
-
-
-def load_topr_batch():
-    """Load libspx_topr_batch.so (after libspx.so, whose contexts and error text it shares).  Raises if it is missing."""
-    global _topr_batch
-    if _topr_batch is None:
-        load()
-        if not os.path.exists(TOPR_BATCH_LIB_PATH):
-            raise ImportError("libspx_topr_batch.so not found at %s -- build it with shiftedproximaloperators.jl_amd/csrc/build.sh; "
-                              "there is no CPU fallback" % TOPR_BATCH_LIB_PATH)
-        L = ctypes.CDLL(TOPR_BATCH_LIB_PATH)
-        for name, args in TOPR_BATCH_SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.argtypes = args
-            fn.restype = _int
-        _topr_batch = L
-    return _topr_batch
-
-
-_lhalf_batch = None
-
-
-def load_lhalf_batch():
-    """Load libspx_lhalf_batch.so (after libspx.so, whose contexts and error text it shares).  Raises if it is missing."""
-    global _lhalf_batch
-    if _lhalf_batch is None:
-        load()
-        if not os.path.exists(LHALF_BATCH_LIB_PATH):
-            raise ImportError("libspx_lhalf_batch.so not found at %s -- build it with shiftedproximaloperators.jl_amd/csrc/build.sh; "
-                              "there is no CPU fallback" % LHALF_BATCH_LIB_PATH)
-        L = ctypes.CDLL(LHALF_BATCH_LIB_PATH)
-        for name, args in LHALF_BATCH_SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.argtypes = args
-            fn.restype = _int
-        _lhalf_batch = L
-    return _lhalf_batch
+load_batch = functools.partial(load_batch_library, "batch")
+load_ibatch = functools.partial(load_batch_library, "ibatch")
+load_gbatch = functools.partial(load_batch_library, "gbatch")
+load_gbinf_batch = functools.partial(load_batch_library, "gbinf_batch")
+load_b2_batch = functools.partial(load_batch_library, "b2_batch")
+load_topr_batch = functools.partial(load_batch_library, "topr_batch")
+load_lhalf_batch = functools.partial(load_batch_library, "lhalf_batch")
 
 
 def check(status):

@@ -5,25 +5,22 @@ pytest id `file::function[case]`.  The ids are the measurement's evidence (profi
 file); this test checks that the ledger and the library agree and that each id names an existing test function.
 
 A pull request that adds (or removes) an instantiation of k_sep_batch or k_batch_reduce fails here until it says which test
-launches the new one.  libspx.so itself must not gain a kernel from the batched call: its ledger is unchanged."""
+launches the new one.  No other library may gain a kernel from the batched call, and libspx.so holds no batched kernel at all:
+its ledger is unchanged."""
 import json
 import os
-import re
-import subprocess
-import sys
 
 import pytest
 
+import batch_libs
+from batch_libs import normalised
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TOOL = os.path.join(ROOT, "tools", "kernel_census.py")
 
 
 @pytest.fixture(scope="module")
 def libs():
-    import __graft_entry__ as ge
-    ge.build()
-    import spx_amd
-    return spx_amd._lib.LIB_PATH, spx_amd._lib.BATCH_LIB_PATH
+    return batch_libs.library_paths()
 
 
 @pytest.fixture(scope="module")
@@ -32,21 +29,8 @@ def census():
         return json.load(f)
 
 
-def _normalised(lib):
-    sys.path.insert(0, os.path.dirname(TOOL))
-    try:
-        import kernel_census as kc
-    finally:
-        sys.path.pop(0)
-    out = subprocess.run([sys.executable, TOOL, "symbols", lib], check=True, capture_output=True, text=True).stdout
-    names = [l for l in out.splitlines() if l.strip()]
-    norm = [kc.normalise(n)[0] for n in names]
-    assert len(set(norm)) == len(names)                  # the normalised spelling keeps the instantiations apart
-    return set(norm)
-
-
 def test_every_batch_instantiation_is_in_the_census(libs, census):
-    built = _normalised(libs[1])
+    built = normalised(libs["batch"])
     # {row, tiled} x {L1, L0, L1Box, L1Box + mask, L0Box, L0Box + mask} x {pairs, element-wise} + the per-problem reduce
     assert len(built) == 25 and all(n.startswith(("k_sep_batch<", "k_batch_reduce")) for n in built), sorted(built)[:5]
     listed = set(census)
@@ -54,17 +38,11 @@ def test_every_batch_instantiation_is_in_the_census(libs, census):
     assert not missing and not stale, (
         "tests/kernel_census_batch.json is out of step with libspx_batch.so: %d instantiations without an entry %s; %d entries "
         "for instantiations that no longer exist %s" % (len(missing), missing[:5], len(stale), stale[:5]))
-    # the batched kernels live in the second library only
-    assert not [n for n in _normalised(libs[0]) if "batch" in n]
+    # the batched kernels live in this library only, and libspx.so holds no batched kernel at all
+    for key, lib in batch_libs.others("batch").items():
+        assert not [n for n in normalised(lib) if n.startswith(("k_sep_batch<", "k_batch_reduce"))], key
+    assert not [n for n in normalised(libs[batch_libs.CORE]) if "batch" in n]
 
 
 def test_batch_census_entries_name_existing_tests(census):
-    funcs = {}
-    for norm, e in census.items():
-        assert isinstance(e, dict) and set(e) == {"test"}, (norm, e)     # none is unreachable
-        path, _, rest = e["test"].partition("::")
-        assert re.fullmatch(r"tests/test_\w+\.py", path) and os.path.isfile(os.path.join(ROOT, path)) and rest, (norm, e)
-        if path not in funcs:
-            with open(os.path.join(ROOT, path)) as f:
-                funcs[path] = set(re.findall(r"^def (test_\w+)\(", f.read(), flags=re.M))
-        assert rest.split("[", 1)[0] in funcs[path], (norm, e)
+    batch_libs.census_entries_name_existing_tests(census)

@@ -6,29 +6,23 @@ profiler run per test file); this test checks that the ledger and the library ag
 function.
 
 A pull request that adds (or removes) an instantiation of k_binf_batch or k_binf_batch_reduce fails here until it says which test
-launches the new one.  libspx.so, libspx_batch.so, libspx_ibatch.so and libspx_gbatch.so must not gain a kernel from the batched
-Binf call: their ledgers are unchanged."""
+launches the new one.  No other library may gain a kernel from the batched Binf call: their ledgers are unchanged."""
 import json
 import os
-import re
-import subprocess
-import sys
 
 import pytest
 
+import batch_libs
+from batch_libs import normalised
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TOOL = os.path.join(ROOT, "tools", "kernel_census.py")
 # GroupTilesBinf (csrc/spx_group_common.hpp): lanes per group x elements per lane of the nine rows
 TILES = [(1, 2), (1, 4), (1, 8), (2, 8), (4, 8), (8, 8), (8, 16), (16, 16), (32, 16)]
 
 
 @pytest.fixture(scope="module")
 def libs():
-    import __graft_entry__ as ge
-    ge.build()
-    import spx_amd
-    L = spx_amd._lib
-    return L.LIB_PATH, L.BATCH_LIB_PATH, L.IBATCH_LIB_PATH, L.GBATCH_LIB_PATH, L.GBINF_BATCH_LIB_PATH
+    return batch_libs.library_paths()
 
 
 @pytest.fixture(scope="module")
@@ -37,21 +31,8 @@ def census():
         return json.load(f)
 
 
-def _normalised(lib):
-    sys.path.insert(0, os.path.dirname(TOOL))
-    try:
-        import kernel_census as kc
-    finally:
-        sys.path.pop(0)
-    out = subprocess.run([sys.executable, TOOL, "symbols", lib], check=True, capture_output=True, text=True).stdout
-    names = [l for l in out.splitlines() if l.strip()]
-    norm = [kc.normalise(n)[0] for n in names]
-    assert len(set(norm)) == len(names)                  # the normalised spelling keeps the instantiations apart
-    return set(norm)
-
-
 def test_every_gbinf_batch_instantiation_is_in_the_census(libs, census):
-    built = _normalised(libs[4])
+    built = normalised(libs["gbinf_batch"])
     assert built and all(n.startswith(("k_binf_batch<", "k_binf_batch_reduce")) for n in built), sorted(built)[:5]
     listed = set(census)
     missing, stale = sorted(built - listed), sorted(listed - built)
@@ -65,22 +46,14 @@ def test_every_gbinf_batch_instantiation_is_in_the_census(libs, census):
 
 
 def test_the_other_libraries_gained_no_kernel_of_the_new_names(libs):
-    for lib in libs[:4]:
-        assert not [n for n in _normalised(lib) if "k_binf_batch" in n], lib
+    for key, lib in batch_libs.others("gbinf_batch").items():
+        assert not [n for n in normalised(lib) if "k_binf_batch" in n], key
     # the new names stay clear of the strings the other ledgers search for
-    assert not [n for n in _normalised(libs[4]) if "k_group_batch" in n or "k_gbatch" in n]
+    assert not [n for n in normalised(libs["gbinf_batch"]) if "k_group_batch" in n or "k_gbatch" in n]
     # the first library holds no batched kernel at all; the others still hold their own
-    assert not [n for n in _normalised(libs[0]) if "batch" in n]
-    assert [len(_normalised(lib)) for lib in libs[1:4]] == [25, 25, 37]
+    assert not [n for n in normalised(libs[batch_libs.CORE]) if "batch" in n]
+    assert [len(normalised(libs[key])) for key in ("batch", "ibatch", "gbatch")] == [25, 25, 37]
 
 
 def test_gbinf_batch_census_entries_name_existing_tests(census):
-    funcs = {}
-    for norm, e in census.items():
-        assert isinstance(e, dict) and set(e) == {"test"}, (norm, e)     # none is unreachable
-        path, _, rest = e["test"].partition("::")
-        assert re.fullmatch(r"tests/test_\w+\.py", path) and os.path.isfile(os.path.join(ROOT, path)) and rest, (norm, e)
-        if path not in funcs:
-            with open(os.path.join(ROOT, path)) as f:
-                funcs[path] = set(re.findall(r"^def (test_\w+)\(", f.read(), flags=re.M))
-        assert rest.split("[", 1)[0] in funcs[path], (norm, e)
+    batch_libs.census_entries_name_existing_tests(census)

@@ -5,17 +5,17 @@ launches it, a full pytest id `file::function[case]`.  This test checks kernel n
 and that each id names an existing test function and a size the test file generates.
 
 A pull request that adds (or removes) an instantiation of k_topr_batch fails here until it says which test launches the new
-one.  The other six libraries must not gain a kernel from the batched top-r calls."""
+one.  The other seven libraries must not gain a kernel from the batched top-r calls."""
 import json
 import os
 import re
-import subprocess
-import sys
 
 import pytest
 
+import batch_libs
+from batch_libs import normalised
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TOOL = os.path.join(ROOT, "tools", "kernel_census.py")
 # kToprBatchTiles (csrc/spx_plan.hpp): lanes x elements per lane of the row-resident form; the row walk: kToprBatchWalkLanes x 0
 TILES = [(64, 4), (256, 4), (256, 16), (512, 16)]
 WALK = (1024, 0)
@@ -24,12 +24,7 @@ BOOL = ("false", "true")
 
 @pytest.fixture(scope="module")
 def libs():
-    import __graft_entry__ as ge
-    ge.build()
-    import spx_amd
-    L = spx_amd._lib
-    return (L.LIB_PATH, L.BATCH_LIB_PATH, L.IBATCH_LIB_PATH, L.GBATCH_LIB_PATH, L.GBINF_BATCH_LIB_PATH, L.B2_BATCH_LIB_PATH,
-            L.TOPR_BATCH_LIB_PATH)
+    return batch_libs.library_paths()
 
 
 @pytest.fixture(scope="module")
@@ -38,21 +33,8 @@ def census():
         return json.load(f)
 
 
-def _normalised(lib):
-    sys.path.insert(0, os.path.dirname(TOOL))
-    try:
-        import kernel_census as kc
-    finally:
-        sys.path.pop(0)
-    out = subprocess.run([sys.executable, TOOL, "symbols", lib], check=True, capture_output=True, text=True).stdout
-    names = [l for l in out.splitlines() if l.strip()]
-    norm = [kc.normalise(n)[0] for n in names]
-    assert len(set(norm)) == len(names)                  # the normalised spelling keeps the instantiations apart
-    return set(norm)
-
-
 def test_every_topr_batch_instantiation_is_in_the_census(libs, census):
-    built = _normalised(libs[6])
+    built = normalised(libs["topr_batch"])
     assert built and all(n.startswith("k_topr_batch<") for n in built), sorted(built)[:5]
     listed = set(census)
     missing, stale = sorted(built - listed), sorted(listed - built)
@@ -67,10 +49,10 @@ def test_every_topr_batch_instantiation_is_in_the_census(libs, census):
 
 
 def test_the_other_libraries_gained_no_kernel_of_the_new_name(libs):
-    for lib in libs[:6]:
-        assert not [n for n in _normalised(lib) if "topr" in n], lib
+    for key, lib in batch_libs.others("topr_batch").items():
+        assert not [n for n in normalised(lib) if "topr" in n], key
     # the new names stay clear of the strings the other ledgers search for
-    assert not [n for n in _normalised(libs[6]) if "k_b2_batch" in n or "k_binf_batch" in n or "k_group_batch" in n or "k_gbatch" in n]
+    assert not [n for n in normalised(libs["topr_batch"]) if "k_b2_batch" in n or "k_binf_batch" in n or "k_group_batch" in n or "k_gbatch" in n]
 
 
 def test_topr_batch_census_entries_name_existing_tests(census):

@@ -1,18 +1,21 @@
-"""CPU: the batched ShiftedNormL1B2 prox! + step statistics entry point (spx_proxstep_l1_b2_batch) exists at every layer that can
-be looked at without a GPU -- include/spx_b2_batch.h (a header of its own: the call lives in libspx_b2_batch.so, the sixth
-library next to libspx.so) compiles as C99 and as C++11 on its own, declares the call and states its contract,
-libspx_b2_batch.so exports it (and no other library does), the ctypes table (B2_BATCH_SIGNATURES) binds exactly the declared set
-with the three integers and chi_lambda by value and pointers elsewhere, the ABI version is unchanged, and the mirror takes
-lambda, sigma, delta and q_scale as per-problem device tensors: anything else is refused."""
+"""CPU: what is specific to the batched ShiftedNormL1B2 prox! + step statistics entry point (spx_proxstep_l1_b2_batch,
+include/spx_b2_batch.h, libspx_b2_batch.so): the header declares the call as the single one's with the per-problem scalars as
+device arrays and states its contract, the ctypes table (B2_BATCH_SIGNATURES) binds it with the three integers and chi_lambda by
+value and pointers elsewhere, and the mirror takes lambda, sigma, delta and q_scale as per-problem device tensors: anything else
+is refused.
+
+What holds for every batched library alike -- the header compiles alone as C99 and C++11, includes spx.h and declares exactly
+the ctypes table's names; the library exports them and no other library does; no host-pointer twin; NEEDED libspx.so found by
+$ORIGIN; the loader's argtypes; the ABI version; the build -- is in tests/test_batch_libraries.py, for all seven."""
 import ctypes
 import inspect
 import os
 import re
-import shutil
-import subprocess
 import sys
 
 import pytest
+
+from batch_libs import header_declarations
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAME = "spx_proxstep_l1_b2_batch"
@@ -36,32 +39,15 @@ def _header_text():
     return open(HEADER).read()
 
 
-def _header_declarations(path=HEADER):
-    txt = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return {m.group(1): m.group(2) for m in re.finditer(r"\bint\s+(spx_[a-z0-9_]+)\s*\(([^;]*?)\)\s*;", txt, flags=re.S)}
-
-
-def test_header_is_plain_c_and_cxx():
-    if shutil.which("gcc"):
-        subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-fsyntax-only", "-x", "c", HEADER])
-    if shutil.which("g++"):
-        subprocess.check_call(["g++", "-std=c++11", "-Wall", "-Werror", "-fsyntax-only", "-x", "c++", HEADER])
-
-
-def test_header_is_additive_and_includes_spx_h():
-    assert '#include "spx.h"' in _header_text()
-    assert sorted(_header_declarations()) == [NAME]
-
-
 def test_header_declares_the_call():
-    args = [" ".join(a.split()) for a in _header_declarations()[NAME].split(",")]
+    args = [" ".join(a.split()) for a in header_declarations(HEADER)[NAME].split(",")]
     assert args == ARGS, args
     # the single call's vectors and scalars under their names (the per-problem ones as device arrays), plus batch and ld; no
     # host destination
-    single = _header_declarations(os.path.join(ROOT, "include", "spx.h"))["spx_proxstep_l1_b2"]
+    single = header_declarations(os.path.join(ROOT, "include", "spx.h"))["spx_proxstep_l1_b2"]
     names = lambda decl: [a.split()[-1].lstrip("*") for a in decl.split(",")]
-    assert sorted(names(_header_declarations()[NAME])) == sorted([a for a in names(single) if a != "stats"] + ["batch", "ld"])
-    assert names(_header_declarations()[NAME])[:6] == names(single)[:6]
+    assert sorted(names(header_declarations(HEADER)[NAME])) == sorted([a for a in names(single) if a != "stats"] + ["batch", "ld"])
+    assert names(header_declarations(HEADER)[NAME])[:6] == names(single)[:6]
 
 
 def test_header_states_the_contract():
@@ -74,32 +60,8 @@ def test_header_states_the_contract():
         assert word in txt, word
 
 
-def test_library_exports_the_call(built):
-    lib = built._lib.load_b2_batch()
-    assert os.path.basename(built._lib.B2_BATCH_LIB_PATH) == "libspx_b2_batch.so"
-    assert hasattr(lib, NAME)
-    # built and found as the other batch libraries are: next to libspx.so, named after it
-    assert built._lib.B2_BATCH_LIB_PATH == built._lib.LIB_PATH[:-3] + "_b2_batch.so"
-    for other in (ctypes.CDLL(built._lib.LIB_PATH), built._lib.load_batch(), built._lib.load_ibatch(), built._lib.load_gbatch(),
-                  built._lib.load_gbinf_batch()):
-        assert not hasattr(other, NAME)                      # the new entry point lives in the sixth library only
-    assert not hasattr(lib, "spx_host_" + NAME[4:])          # no host-pointer twin
-    core = ctypes.CDLL(built._lib.LIB_PATH)
-    core.spx_abi_version.restype = ctypes.c_int
-    assert core.spx_abi_version() == 1                       # the change is additive
-
-
-def test_library_links_against_libspx_by_rpath_origin(built):
-    if not shutil.which("readelf"):
-        pytest.skip("no readelf")
-    dyn = subprocess.run(["readelf", "-d", built._lib.B2_BATCH_LIB_PATH], check=True, capture_output=True, text=True).stdout
-    assert re.search(r"NEEDED.*\[%s\]" % re.escape(os.path.basename(built._lib.LIB_PATH)), dyn), dyn
-    assert re.search(r"R(UN)?PATH.*\$ORIGIN", dyn), dyn
-
-
 def test_ctypes_table_binds_the_call(built):
     sig = built._lib.B2_BATCH_SIGNATURES
-    assert sorted(sig) == sorted(_header_declarations())      # the table binds exactly the declared set
     assert len(sig[NAME]) == len(ARGS), sig[NAME]
     for k, t in enumerate(sig[NAME]):
         want = ctypes.c_int64 if k in I64_BY_VALUE else ctypes.c_double if k in F64_BY_VALUE else ctypes.c_void_p
@@ -108,13 +70,6 @@ def test_ctypes_table_binds_the_call(built):
     assert [k for k, a in enumerate(ARGS) if a.startswith("double ")] == F64_BY_VALUE
     fn = getattr(built._lib.load_b2_batch(), NAME)
     assert list(fn.argtypes) == sig[NAME] and fn.restype is ctypes.c_int
-
-
-def test_build_knows_the_sixth_library():
-    src = open(os.path.join(ROOT, "__graft_entry__.py")).read()
-    assert "spx_b2_batch.h" in src and "_b2_batch.so" in src and "load_b2_batch()" in src
-    sh = open(os.path.join(ROOT, "shiftedproximaloperators.jl_amd", "csrc", "build.sh")).read()
-    assert sh.count("spx_b2_batch") >= 3 and "_b2_batch.so" in sh
 
 
 def test_mirror_takes_the_scalars_per_problem_on_the_device(built):

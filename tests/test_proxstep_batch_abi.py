@@ -1,14 +1,20 @@
-"""CPU: the batched prox! + step statistics entry points (spx_proxstep_{l1,l0}[_box]_batch) exist at every layer that can be
-looked at without a GPU -- include/spx_batch.h (a header of its own: the call lives in libspx_batch.so, next to libspx.so) declares the four with `int64_t n, int64_t batch, int64_t ld` followed by the device
-parameter arrays and `double* xkn, double* stats_dev`, libspx_batch.so exports them, the ctypes table (BATCH_SIGNATURES) binds them with the header's
-argument count, there is no host-pointer twin, the ABI version is unchanged, and the mirror's docstring names the three sums."""
+"""CPU: what is specific to the batched prox! + step statistics entry points (spx_proxstep_{l1,l0}[_box]_batch, include/spx_batch.h,
+libspx_batch.so): the header declares the four with `int64_t n, int64_t batch, int64_t ld` followed by the device parameter arrays
+and `double* xkn, double* stats_dev`, the library has them, the ctypes table (BATCH_SIGNATURES) binds them with the header's
+argument count, n, batch and ld by value and pointers elsewhere, and the mirror's docstring names the three sums.
+
+What holds for every batched library alike -- the header compiles alone as C99 and C++11, includes spx.h and declares exactly
+the ctypes table's names; the library exports them and no other library does; no host-pointer twin; NEEDED libspx.so found by
+$ORIGIN; the loader's argtypes; the ABI version; the build -- is in tests/test_batch_libraries.py, for all seven."""
 import ctypes
 import os
-import re
 
 import pytest
 
+from batch_libs import header_declarations
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "include", "spx_batch.h")
 OPS = {"l1": 13, "l0": 13, "l1_box": 16, "l0_box": 16}   # operator -> argument count
 HEAD = ["spx_ctx* ctx", "double* y", "const double* q", "const double* xk", "const double* sj", "int64_t n", "int64_t batch",
         "int64_t ld", "const double* lambda", "const double* sigma"]
@@ -24,15 +30,9 @@ def built():
     return spx_amd
 
 
-def _header_declarations():
-    txt = open(os.path.join(ROOT, "include", "spx_batch.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return {m.group(1): m.group(2) for m in re.finditer(r"\bint\s+(spx_[a-z0-9_]+)\s*\(([^;]*?)\)\s*;", txt, flags=re.S)}
-
-
 @pytest.mark.parametrize("op", sorted(OPS))
 def test_header_declares_proxstep_batch(op):
-    decl = _header_declarations()
+    decl = header_declarations(HEADER)
     name = "spx_proxstep_%s_batch" % op
     assert name in decl
     args = [" ".join(a.split()) for a in decl[name].split(",")]
@@ -49,7 +49,6 @@ def test_library_exports_proxstep_batch(built, op):
 @pytest.mark.parametrize("op", sorted(OPS))
 def test_ctypes_table_binds_proxstep_batch(built, op):
     sig = built._lib.BATCH_SIGNATURES
-    assert sorted(sig) == sorted(_header_declarations())      # the table binds exactly the declared set
     name = "spx_proxstep_%s_batch" % op
     assert name in sig
     assert len(sig[name]) == OPS[op], sig[name]
@@ -57,16 +56,6 @@ def test_ctypes_table_binds_proxstep_batch(built, op):
     assert sig[name][5:8] == [ctypes.c_int64] * 3
     assert all(t is ctypes.c_void_p for t in sig[name][:5] + sig[name][8:]), sig[name]
     assert "spx_host_proxstep_%s_batch" % op not in sig      # device pointers only: no host-pointer twin
-
-
-def test_no_host_twin_and_the_abi_version_stays(built):
-    for table in (built._lib.SIGNATURES, built._lib.BATCH_SIGNATURES, _header_declarations()):
-        assert not [k for k in table if k.startswith("spx_host_") and k.endswith("_batch")]
-    lib, blib = ctypes.CDLL(built._lib.LIB_PATH), built._lib.load_batch()
-    for op in OPS:
-        assert not hasattr(lib, "spx_host_proxstep_%s_batch" % op) and not hasattr(blib, "spx_host_proxstep_%s_batch" % op)
-    lib.spx_abi_version.restype = ctypes.c_int
-    assert lib.spx_abi_version() == 1                        # the change is additive
 
 
 def test_mirror_documents_the_three_sums(built):

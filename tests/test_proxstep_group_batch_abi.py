@@ -1,17 +1,22 @@
-"""CPU: the batched group prox! + step statistics entry point (spx_proxstep_group_l2_batch) exists at every layer that can be
-looked at without a GPU -- include/spx_gbatch.h (a header of its own: the call lives in libspx_gbatch.so, next to libspx.so,
-libspx_batch.so and libspx_ibatch.so) declares it with `int64_t group_size, int64_t ngroups, int64_t batch, int64_t ld`, the
-weights as `lambda_vec, ldl, lambda_scale` and the device parameter arrays, libspx_gbatch.so exports it, the ctypes table
-(GBATCH_SIGNATURES) binds exactly the declared set with the five integers by value and pointers elsewhere, there is no
-host-pointer twin, the ABI version is unchanged, the header states the alignment classes, and the mirror's docstring names the
-three sums and the weights' layout."""
+"""CPU: what is specific to the batched group prox! + step statistics entry point (spx_proxstep_group_l2_batch,
+include/spx_gbatch.h, libspx_gbatch.so): the header declares it with `int64_t group_size, int64_t ngroups, int64_t batch,
+int64_t ld`, the weights as `lambda_vec, ldl, lambda_scale` and the device parameter arrays, the ctypes table (GBATCH_SIGNATURES)
+binds it with the five integers by value and pointers elsewhere, the header states the alignment classes, and the mirror's
+docstring names the three sums and the weights' layout.
+
+What holds for every batched library alike -- the header compiles alone as C99 and C++11, includes spx.h and declares exactly
+the ctypes table's names; the library exports them and no other library does; no host-pointer twin; NEEDED libspx.so found by
+$ORIGIN; the loader's argtypes; the ABI version; the build -- is in tests/test_batch_libraries.py, for all seven."""
 import ctypes
 import os
 import re
 
 import pytest
 
+from batch_libs import header_declarations
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "include", "spx_gbatch.h")
 NAME = "spx_proxstep_group_l2_batch"
 ARGS = ["spx_ctx* ctx", "double* y", "const double* q", "const double* xk", "const double* sj", "int64_t group_size",
         "int64_t ngroups", "int64_t batch", "int64_t ld", "const double* lambda_vec", "int64_t ldl", "const double* lambda_scale",
@@ -31,18 +36,8 @@ def _header_text():
     return open(os.path.join(ROOT, "include", "spx_gbatch.h")).read()
 
 
-def _header_declarations():
-    txt = re.sub(r"/\*.*?\*/", "", _header_text(), flags=re.S)
-    return {m.group(1): m.group(2) for m in re.finditer(r"\bint\s+(spx_[a-z0-9_]+)\s*\(([^;]*?)\)\s*;", txt, flags=re.S)}
-
-
-def test_header_is_additive_and_includes_spx_h():
-    assert '#include "spx.h"' in _header_text()
-    assert sorted(_header_declarations()) == [NAME]
-
-
 def test_header_declares_the_call():
-    args = [" ".join(a.split()) for a in _header_declarations()[NAME].split(",")]
+    args = [" ".join(a.split()) for a in header_declarations(HEADER)[NAME].split(",")]
     assert args == ARGS, args
 
 
@@ -54,34 +49,12 @@ def test_header_states_the_alignment_classes_and_the_refusals():
         assert word in txt, word
 
 
-def test_library_exports_the_call(built):
-    lib = built._lib.load_gbatch()
-    assert os.path.basename(built._lib.GBATCH_LIB_PATH) == "libspx_gbatch.so"
-    assert hasattr(lib, NAME)
-    # built and found as the two other batch libraries are: next to libspx.so, named after it
-    assert os.path.dirname(built._lib.GBATCH_LIB_PATH) == os.path.dirname(built._lib.LIB_PATH)
-    assert built._lib.GBATCH_LIB_PATH == built._lib.LIB_PATH[:-3] + "_gbatch.so"
-
-
 def test_ctypes_table_binds_the_call(built):
     sig = built._lib.GBATCH_SIGNATURES
-    assert sorted(sig) == sorted(_header_declarations())      # the table binds exactly the declared set
     assert len(sig[NAME]) == len(ARGS), sig[NAME]
     for k, t in enumerate(sig[NAME]):
         assert t is (ctypes.c_int64 if k in BY_VALUE else ctypes.c_void_p), (k, t)
     assert [k for k, a in enumerate(ARGS) if a.startswith("int64_t")] == BY_VALUE
-
-
-def test_no_host_twin_and_the_abi_version_stays(built):
-    for table in (built._lib.SIGNATURES, built._lib.BATCH_SIGNATURES, built._lib.IBATCH_SIGNATURES, built._lib.GBATCH_SIGNATURES,
-                  _header_declarations()):
-        assert not [k for k in table if k.startswith("spx_host_") and k.endswith("_batch")]
-    lib, glib = ctypes.CDLL(built._lib.LIB_PATH), built._lib.load_gbatch()
-    assert not hasattr(lib, "spx_host_" + NAME[4:]) and not hasattr(glib, "spx_host_" + NAME[4:])
-    for other in (lib, built._lib.load_batch(), built._lib.load_ibatch()):
-        assert not hasattr(other, NAME)                      # the new entry point lives in the fourth library only
-    lib.spx_abi_version.restype = ctypes.c_int
-    assert lib.spx_abi_version() == 1                        # the change is additive
 
 
 def test_mirror_documents_the_sums_and_the_weights(built):

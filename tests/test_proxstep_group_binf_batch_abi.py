@@ -1,18 +1,21 @@
-"""CPU: the batched Binf group prox! + step statistics entry point (spx_proxstep_group_l2_binf_batch) exists at every layer that
-can be looked at without a GPU -- include/spx_gbinf_batch.h (a header of its own: the call lives in libspx_gbinf_batch.so, the
-fifth library next to libspx.so) compiles as C99 and as C++11 on its own and declares the call as spx_proxstep_group_l2_batch's
-with `const double* delta` between sigma and q_scale, libspx_gbinf_batch.so exports it (and no other library does), the ctypes
-table (GBINF_BATCH_SIGNATURES) binds exactly the declared set with the five integers by value and pointers elsewhere, the ABI
-version is unchanged, and the mirror takes delta as a per-problem device tensor: anything else is refused."""
+"""CPU: what is specific to the batched Binf group prox! + step statistics entry point (spx_proxstep_group_l2_binf_batch,
+include/spx_gbinf_batch.h, libspx_gbinf_batch.so): the header declares the call as spx_proxstep_group_l2_batch's with
+`const double* delta` between sigma and q_scale and states its contract, the ctypes table (GBINF_BATCH_SIGNATURES) binds it with
+the five integers by value and pointers elsewhere, and the mirror takes delta as a per-problem device tensor: anything else is
+refused.
+
+What holds for every batched library alike -- the header compiles alone as C99 and C++11, includes spx.h and declares exactly
+the ctypes table's names; the library exports them and no other library does; no host-pointer twin; NEEDED libspx.so found by
+$ORIGIN; the loader's argtypes; the ABI version; the build -- is in tests/test_batch_libraries.py, for all seven."""
 import ctypes
 import inspect
 import os
 import re
-import shutil
-import subprocess
 import sys
 
 import pytest
+
+from batch_libs import header_declarations
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAME = "spx_proxstep_group_l2_binf_batch"
@@ -35,27 +38,10 @@ def _header_text():
     return open(HEADER).read()
 
 
-def _header_declarations(path=HEADER):
-    txt = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return {m.group(1): m.group(2) for m in re.finditer(r"\bint\s+(spx_[a-z0-9_]+)\s*\(([^;]*?)\)\s*;", txt, flags=re.S)}
-
-
-def test_header_is_plain_c_and_cxx():
-    if shutil.which("gcc"):
-        subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-fsyntax-only", "-x", "c", HEADER])
-    if shutil.which("g++"):
-        subprocess.check_call(["g++", "-std=c++11", "-Wall", "-Werror", "-fsyntax-only", "-x", "c++", HEADER])
-
-
-def test_header_is_additive_and_includes_spx_h():
-    assert '#include "spx.h"' in _header_text()
-    assert sorted(_header_declarations()) == [NAME]
-
-
 def test_header_declares_the_call_as_the_plain_one_plus_delta():
-    args = [" ".join(a.split()) for a in _header_declarations()[NAME].split(",")]
+    args = [" ".join(a.split()) for a in header_declarations(HEADER)[NAME].split(",")]
     assert args == ARGS, args
-    plain = _header_declarations(os.path.join(ROOT, "include", "spx_gbatch.h"))["spx_proxstep_group_l2_batch"]
+    plain = header_declarations(os.path.join(ROOT, "include", "spx_gbatch.h"))["spx_proxstep_group_l2_batch"]
     assert [a for a in args if a != "const double* delta"] == [" ".join(a.split()) for a in plain.split(",")]
 
 
@@ -68,23 +54,8 @@ def test_header_states_the_contract():
         assert word in txt, word
 
 
-def test_library_exports_the_call(built):
-    lib = built._lib.load_gbinf_batch()
-    assert os.path.basename(built._lib.GBINF_BATCH_LIB_PATH) == "libspx_gbinf_batch.so"
-    assert hasattr(lib, NAME)
-    # built and found as the other batch libraries are: next to libspx.so, named after it
-    assert built._lib.GBINF_BATCH_LIB_PATH == built._lib.LIB_PATH[:-3] + "_gbinf_batch.so"
-    for other in (ctypes.CDLL(built._lib.LIB_PATH), built._lib.load_batch(), built._lib.load_ibatch(), built._lib.load_gbatch()):
-        assert not hasattr(other, NAME)                      # the new entry point lives in the fifth library only
-    assert not hasattr(lib, "spx_host_" + NAME[4:])          # no host-pointer twin
-    core = ctypes.CDLL(built._lib.LIB_PATH)
-    core.spx_abi_version.restype = ctypes.c_int
-    assert core.spx_abi_version() == 1                       # the change is additive
-
-
 def test_ctypes_table_binds_the_call(built):
     sig = built._lib.GBINF_BATCH_SIGNATURES
-    assert sorted(sig) == sorted(_header_declarations())      # the table binds exactly the declared set
     assert len(sig[NAME]) == len(ARGS), sig[NAME]
     for k, t in enumerate(sig[NAME]):
         assert t is (ctypes.c_int64 if k in BY_VALUE else ctypes.c_void_p), (k, t)

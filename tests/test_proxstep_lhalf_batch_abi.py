@@ -1,10 +1,12 @@
-"""CPU: the batched RootNormLhalf(Box) prox! + step statistics entry points (spx_proxstep_lhalf_batch,
-spx_proxstep_lhalf_box_batch) and the threshold call (spx_lhalf_threshold_batch) exist at every layer that can be looked at without
-a GPU -- include/spx_lhalf_batch.h (a header of its own: the calls live in libspx_lhalf_batch.so, the eighth library next to
-libspx.so) compiles as C99 and as C++11 on its own, declares exactly the three calls and states their contract,
-libspx_lhalf_batch.so exports them (and no other library does) and links against libspx.so, the ctypes table
-(LHALF_BATCH_SIGNATURES) binds exactly the declared set with the integers by value and pointers elsewhere, the ABI version is
-unchanged, build.sh and build() name the library, and the mirror has the new names (prox_step_batch_bang keeps refusing "lhalf").
+"""CPU: what is specific to the batched RootNormLhalf(Box) prox! + step statistics entry points (spx_proxstep_lhalf_batch,
+spx_proxstep_lhalf_box_batch) and the threshold call (spx_lhalf_threshold_batch), include/spx_lhalf_batch.h,
+libspx_lhalf_batch.so: the header declares exactly the three calls, word for word the NormL1 calls' argument lists, and states
+their contract, the ctypes table (LHALF_BATCH_SIGNATURES) binds them with the integers by value and pointers elsewhere, and the
+mirror has the new names (prox_step_batch_bang keeps refusing "lhalf").
+
+What holds for every batched library alike -- the header compiles alone as C99 and C++11, includes spx.h and declares exactly
+the ctypes table's names; the library exports them and no other library does; no host-pointer twin; NEEDED libspx.so found by
+$ORIGIN; the loader's argtypes; the ABI version; the build -- is in tests/test_batch_libraries.py, for all seven.
 
 The host side of the device threshold (csrc/spx_lhalf_threshold.hpp is __host__ __device__) is held to glibc's pow here too:
 tests/c/lhalf_threshold_driver.cpp runs the header's statements on the host."""
@@ -18,6 +20,8 @@ import sys
 
 import numpy as np
 import pytest
+
+from batch_libs import header_declarations
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "spx_lhalf_batch.h")
@@ -40,27 +44,15 @@ def _header_text():
     return open(HEADER).read()
 
 
-def _header_declarations(path=HEADER):
-    txt = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return {m.group(1): m.group(2) for m in re.finditer(r"\bint\s+(spx_[a-z0-9_]+)\s*\(([^;]*?)\)\s*;", txt, flags=re.S)}
-
-
-def test_header_is_plain_c_and_cxx():
-    if shutil.which("gcc"):
-        subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-fsyntax-only", "-x", "c", HEADER])
-    if shutil.which("g++"):
-        subprocess.check_call(["g++", "-std=c++11", "-Wall", "-Werror", "-fsyntax-only", "-x", "c++", HEADER])
-
-
 def test_header_declares_exactly_the_three_calls():
     assert '#include "spx.h"' in _header_text()
-    decl = _header_declarations()
+    decl = header_declarations(HEADER)
     assert sorted(decl) == sorted(DECLS)
     for name, want in DECLS.items():
         args = [" ".join(a.split()) for a in decl[name].split(",")]
         assert args == want, (name, args)
     # word for word the argument lists of the NormL1 calls of spx_batch.h
-    l1 = _header_declarations(os.path.join(ROOT, "include", "spx_batch.h"))
+    l1 = header_declarations(os.path.join(ROOT, "include", "spx_batch.h"))
     flat = lambda d: [" ".join(a.split()) for a in d.split(",")]
     assert flat(decl["spx_proxstep_lhalf_batch"]) == flat(l1["spx_proxstep_l1_batch"])
     assert flat(decl["spx_proxstep_lhalf_box_batch"]) == flat(l1["spx_proxstep_l1_box_batch"])
@@ -78,38 +70,8 @@ def test_header_states_the_contract():
         assert word in txt, word
 
 
-def test_library_exports_the_calls_and_no_other_does(built):
-    L = built._lib
-    lib = L.load_lhalf_batch()
-    assert os.path.basename(L.LHALF_BATCH_LIB_PATH) == "libspx_lhalf_batch.so"
-    assert L.LHALF_BATCH_LIB_PATH == L.LIB_PATH[:-3] + "_lhalf_batch.so"
-    others = (ctypes.CDLL(L.LIB_PATH), L.load_batch(), L.load_ibatch(), L.load_gbatch(), L.load_gbinf_batch(), L.load_b2_batch(),
-              L.load_topr_batch())
-    for name in DECLS:
-        assert hasattr(lib, name), name
-        assert not hasattr(lib, "spx_host_" + name[4:])          # no host-pointer twin
-        for other in others:
-            assert not hasattr(other, name), name
-    if shutil.which("nm"):                                        # nothing else is exported
-        out = subprocess.run(["nm", "-D", "--defined-only", L.LHALF_BATCH_LIB_PATH], check=True, capture_output=True, text=True).stdout
-        exported = {l.split()[-1] for l in out.splitlines() if " T " in l and l.split()[-1].startswith("spx_")}
-        assert exported == set(DECLS), exported
-    core = ctypes.CDLL(L.LIB_PATH)
-    core.spx_abi_version.restype = ctypes.c_int
-    assert core.spx_abi_version() == 1                            # the change is additive
-
-
-def test_library_links_against_libspx_by_rpath_origin(built):
-    if not shutil.which("readelf"):
-        pytest.skip("no readelf")
-    dyn = subprocess.run(["readelf", "-d", built._lib.LHALF_BATCH_LIB_PATH], check=True, capture_output=True, text=True).stdout
-    assert re.search(r"NEEDED.*\[%s\]" % re.escape(os.path.basename(built._lib.LIB_PATH)), dyn), dyn
-    assert re.search(r"R(UN)?PATH.*\$ORIGIN", dyn), dyn
-
-
 def test_ctypes_table_binds_the_calls(built):
     sig = built._lib.LHALF_BATCH_SIGNATURES
-    assert sorted(sig) == sorted(_header_declarations())      # the table binds exactly the declared set
     for name, args in DECLS.items():
         assert len(sig[name]) == len(args), name
         for k, (t, a) in enumerate(zip(sig[name], args)):
@@ -118,13 +80,6 @@ def test_ctypes_table_binds_the_calls(built):
         assert list(fn.argtypes) == sig[name] and fn.restype is ctypes.c_int
     assert sig["spx_proxstep_lhalf_batch"] == built._lib.BATCH_SIGNATURES["spx_proxstep_l1_batch"]
     assert sig["spx_proxstep_lhalf_box_batch"] == built._lib.BATCH_SIGNATURES["spx_proxstep_l1_box_batch"]
-
-
-def test_build_knows_the_eighth_library():
-    src = open(os.path.join(ROOT, "__graft_entry__.py")).read()
-    assert "spx_lhalf_batch.h" in src and "_lhalf_batch.so" in src and "load_lhalf_batch()" in src
-    sh = open(os.path.join(ROOT, "shiftedproximaloperators.jl_amd", "csrc", "build.sh")).read()
-    assert sh.count("spx_lhalf_batch") >= 3 and "_lhalf_batch.so" in sh
 
 
 def test_mirror_has_the_new_names(built):
