@@ -20,7 +20,8 @@ The bars are the project's own, none is new:
       `scales-ulps ...`); for Binf only on the groups the oracle zeroes neither at k nor at 0.
   (c) the fused calls: y the bits of the plain call, xkn the bits of (xk + sj) + y, [0] the oracle's objective of that y (exactly
       for NormL0, 1e-12 otherwise), the other sums within 1e-12 of sum |term| of math.fsum; a batched call: every row the bits of
-      the single call on that row, its sums to the bars of the batch files, the k = 0 row the bits of a batch of one.
+      the single call on that row, its sums to the bars of the batch files, the k = 0 row the bits of a batch of one; the
+      batched ShiftedNormL1B2 call, whose root iteration is its own, to (a) and (b) at the B2 bar, its inactive rows to bits.
   (d) psi(y) at the feasibility edges: the B2 ball with its absolute eps, the box slack, the 1.1 Delta edge of the Binf forms.
 
 The LDS and streaming forms of ShiftedNormL1B2 are reached with tuning key 8 = 4 at n = 50 001 and 70 001, as
@@ -668,34 +669,42 @@ def _check_batch_sums(got, single, terms, what):
         _check_sum(float(g), t, "%s %s" % (what, nm))
 
 
+BATCHED_SEP = ["prox_l1_box", "iprox_l1_box", "prox_l0", "prox_l0_box", "iprox_l0_box"]
+
+
 @pytest.mark.parametrize("n", [1000, 12_289 + 3072])
-@pytest.mark.parametrize("iprox", [False, True], ids=["prox", "iprox"])
-def test_batched_l1_box(s, orc, ctx, iprox, n):
+@pytest.mark.parametrize("op", BATCHED_SEP, ids=["prox", "iprox", "l0-prox", "l0_box-prox", "l0_box-iprox"])
+def test_batched_l1_box(s, orc, ctx, op, n):
     """spx_proxstep_l1_box_batch / spx_iproxstep_l1_box_batch, one call, seven rows at seven scales with lambda, l and u on the
     device scaled per row: every row the bits of the single call on that row (and of the oracle), the k = 0 row those of a batch
-    of one"""
+    of one.  The same for spx_proxstep_l0_batch, spx_proxstep_l0_box_batch and spx_iproxstep_l0_box_batch, lambda scaled by
+    c^2: the single call takes NormL0's threshold sqrt(2 lambda sigma) from the host, the batched kernel forms it on the
+    device, here at arguments from 2^-1000 to 2^1000; [0] is exactly lambda_b times the count of nonzeros."""
     import torch
-    op = "iprox_l1_box" if iprox else "prox_l1_box"
+    iprox, box = op.startswith("iprox"), op.endswith("_box")
     L = s._lib.load()
     B = s._lib.load_ibatch() if iprox else s._lib.load_batch()
-    fn = B.spx_iproxstep_l1_box_batch if iprox else B.spx_proxstep_l1_box_batch
+    fn = getattr(B, "spx_%s_%s_batch" % ("iproxstep" if iprox else "proxstep", op.split("_", 1)[1]))
     P0 = scales.separable(op, n, masked=True)
     rows = _rows(P0)
-    mask = _dev(P0.mask)
+    mask = _dev(P0.mask) if box else None
+    assert (P0.mask is not None) == box
 
     def call(rs):
         nb = len(rs)
         Q, X, S = (_stack(rs, nm) for nm in ("q", "xk", "sj"))
         Y, K = torch.full_like(Q, POISON), torch.full_like(Q, POISON)
-        lam, lo, up = (_scalars(rs, nm) for nm in ("lam", "l", "u"))
+        lam = _scalars(rs, "lam")
+        lo, up = (_scalars(rs, "l"), _scalars(rs, "u")) if box else (None, None)
+        bounds = (_p(lo), _p(up), _p(mask)) if box else ()
         out = torch.full((nb, 4 if iprox else 3), POISON, dtype=torch.float64, device="cuda:0")
         torch.cuda.synchronize()
         if iprox:
             Dm = _stack(rs, "d")
-            rc = fn(ctx, _p(Y), _p(Q), _p(Dm), _p(X), _p(S), n, nb, n, _p(lam), None, _p(lo), _p(up), _p(mask), _p(K), _p(out))
+            rc = fn(ctx, _p(Y), _p(Q), _p(Dm), _p(X), _p(S), n, nb, n, _p(lam), None, *bounds, _p(K), _p(out))
         else:
             sig, qs = _scalars(rs, "sigma"), _dev(np.ones(nb))
-            rc = fn(ctx, _p(Y), _p(Q), _p(X), _p(S), n, nb, n, _p(lam), _p(sig), _p(lo), _p(up), _p(mask), _p(qs), _p(K), _p(out))
+            rc = fn(ctx, _p(Y), _p(Q), _p(X), _p(S), n, nb, n, _p(lam), _p(sig), *bounds, _p(qs), _p(K), _p(out))
         _ok(L, rc, op + " batch")
         _ok(L, L.spx_sync(ctx), op + " batch")
         return _host(Y).copy(), _host(K).copy(), _host(out).copy()
@@ -710,8 +719,12 @@ def test_batched_l1_box(s, orc, ctx, iprox, n):
         assert scales.same_bits(Y[b], scales.oracle_y(orc, P)), (what, "against the oracle")
         assert scales.same_bits(scales.unscale(Y[b], P.k), Y[ROW_K.index(0)]), (what, "against the k = 0 row")
         _check_batch_sums(out[b], st, _sep_terms(P, Y[b]), what)
-        _check_h("l1", float(out[b][0]), scales.oracle_h(orc, P, Y[b]), what + " [0]")      # h over the selected indices
-        _check_h("l1", st[0], scales.oracle_h(orc, P, Y[b]), what + " single [0]")
+        _check_h(P0.h, float(out[b][0]), scales.oracle_h(orc, P, Y[b]), what + " [0]")      # h over the selected indices
+        _check_h(P0.h, st[0], scales.oracle_h(orc, P, Y[b]), what + " single [0]")
+        if P0.h == "l0":                                   # lambda_b * count, one rounded product, over the selected indices
+            v = (P.xk + P.sj) + Y[b]
+            count = int(np.count_nonzero(v if mask is None else v[P0.mask != 0]))
+            assert count > 0 and float(out[b][0]) == float(P.lam) * count, (what, float(out[b][0]), float(P.lam), count)
     z = ROW_K.index(0)
     Y1, K1, out1 = call([rows[z]])
     assert scales.same_bits(Y1[0], Y[z]) and scales.same_bits(K1[0], K[z]), "the k = 0 row against a batch of one"
@@ -772,3 +785,78 @@ def test_batched_groups(s, orc, ctx, binf, shape):
     Y1, K1, out1 = call([rows[z]])
     assert scales.same_bits(Y1[0], Y[z]) and scales.same_bits(K1[0], K[z]), "the k = 0 row against a batch of one"
     _check_batch_sums(out1[0], out[z], [("qy", rows[z].q * Y[z]), ("yy", Y[z] * Y[z])], "batch of one")
+
+
+B2_BATCH_FORMS = [("resident", 1000), ("registers", 8192), ("walk", 10_000)]
+_B2_BATCH_WORST = {}
+
+
+@pytest.mark.parametrize("active", [True, False], ids=["active", "inactive"])
+@pytest.mark.parametrize("form,n", B2_BATCH_FORMS, ids=[f[0] for f in B2_BATCH_FORMS])
+def test_batched_l1_b2(s, orc, ctx, form, n, active):
+    """spx_proxstep_l1_b2_batch -- its own root iteration (csrc/spx_b2_row.hpp: delta * delta, r * r * P + C, C / den, the squares
+    of the box ends sq -+ ls), not the single call's kernel -- at n = 1000 (a row-resident tile), 8192 (the last n whose row stays
+    in registers, 512 lanes) and 10 000 (the row walk): ONE call, seven rows at seven scales, ld = n, lambda, sigma and Delta per
+    row on the device.  The bars of _b2_at and of tests/test_gpu_proxstep_b2_batch.py: every row within 1e-12 of
+    max(||ref||, ||xk||) of the oracle ON THE SCALED PROBLEM and, unscaled, of the k = 0 row of the same call; xkn the bits of
+    (xk + sj) + y; [0] the oracle's objective of that y, [1] and [2] within 1e-12 of sum |term| of math.fsum.  Active rows end
+    on the sphere, | ||sj + y|| - Delta | <= 1e-9 Delta; they are NOT held to bits across scales (the kernel squares sq -+ ls,
+    which the range condition does not bound from below).  Inactive rows need no sum: the bits of spx_proxstep_l1_b2 on the
+    row and of the oracle.  The k = 0 row has the bits of a batch of one in y, xkn and all three sums.
+    On the CPU the oracle alone is scale-equivariant bit for bit on all six problems at all seven k, with
+    ||sj + y_0|| = 1.0000000000000002, 0.9999999999999978, 1.0000000000000009 (active, Delta = 1) and 24.9, 72.0, 79.3
+    (inactive, Delta = 512): it meets every bar here with room to spare."""
+    import torch
+    L, B = s._lib.load(), s._lib.load_b2_batch()
+    P0 = scales.b2(n, active)
+    rows = _rows(P0)
+    tag = "active" if active else "inactive"
+
+    def call(rs):
+        nb = len(rs)
+        Q, X, S = (_stack(rs, nm) for nm in ("q", "xk", "sj"))
+        Y, K = torch.full_like(Q, POISON), torch.full_like(Q, POISON)
+        lam, sig, dl, qs = _scalars(rs, "lam"), _scalars(rs, "sigma"), _scalars(rs, "delta"), _dev(np.ones(nb))
+        out = torch.full((nb, 3), POISON, dtype=torch.float64, device="cuda:0")
+        torch.cuda.synchronize()
+        rc = B.spx_proxstep_l1_b2_batch(ctx, _p(Y), _p(Q), _p(X), _p(S), n, nb, n, _p(lam), _p(sig), _p(dl), _p(qs), 1.0, _p(K), _p(out))
+        _ok(L, rc, "b2 batch")
+        _ok(L, L.spx_sync(ctx), "b2 batch")
+        return _host(Y).copy(), _host(K).copy(), _host(out).copy()
+
+    Y, K, out = call(rows)
+    z = ROW_K.index(0)
+    y0 = Y[z]
+    bar0 = TOL * max(np.linalg.norm(y0), np.linalg.norm(P0.xk))
+    for b, P in enumerate(rows):
+        what = "b2 batch %s %s row %d k=%d" % (form, tag, b, P.k)
+        y = Y[b]
+        ref = scales.oracle_y(orc, P)
+        err, bar = float(np.max(np.abs(y - ref))), TOL * max(np.linalg.norm(ref), np.linalg.norm(P.xk))
+        _B2_BATCH_WORST[P.k] = max(_B2_BATCH_WORST.get(P.k, 0.0), err / bar)
+        print("%s: max |y - oracle| %.3e (bar %.3e, ratio %.3g; worst ratio at this k so far %.3g)" % (what, err, bar, err / bar,
+                                                                                                     _B2_BATCH_WORST[P.k]))
+        assert np.isfinite(y).all() and err <= bar, (what, err, bar)
+        if b != z:
+            _note_ulps("l1_b2_batch_%s_%s" % (form, tag), P.k, y, y0)
+            dev0 = float(np.max(np.abs(scales.unscale(y, P.k) - y0)))
+            assert dev0 <= bar0, (what, "against the k = 0 row", dev0, bar0)
+        assert scales.same_bits(K[b], (P.xk + P.sj) + y), (what, "xkn")
+        _check_h("l1", float(out[b][0]), orc.obj_plain("l1", y, P.xk, P.sj, P.lam), what + " [0]")
+        _check_sum(float(out[b][1]), P.q * y, what + " qy")
+        _check_sum(float(out[b][2]), y * y, what + " yy")
+        nrm = float(np.linalg.norm(P.sj + y))
+        print("%s: ||sj + y|| / Delta %.17g" % (what, nrm / P.delta))
+        if active:
+            assert abs(nrm - P.delta) <= 1e-9 * P.delta, (what, nrm, P.delta)
+        else:
+            assert nrm < 0.9 * P.delta, (what, nrm, P.delta)
+            q, x, sj = _dev(P.q), _dev(P.xk), _dev(P.sj)
+            ys, ks_, st = _fresh(n), _fresh(n), (_D * 3)()
+            _ok(L, L.spx_proxstep_l1_b2(ctx, _p(ys), _p(q), _p(x), _p(sj), n, float(P.lam), float(P.sigma), float(P.delta), float(P.chi),
+                                        1.0, _p(ks_), st, None), what)
+            assert scales.same_bits(y, _host(ys)) and scales.same_bits(K[b], _host(ks_)), (what, "the single call's bits")
+            assert scales.same_bits(y, ref), (what, "the oracle's bits")
+    Y1, K1, out1 = call([rows[z]])
+    assert scales.same_bits(Y1[0], Y[z]) and scales.same_bits(K1[0], K[z]) and scales.same_bits(out1[0], out[z]), \
+        "the k = 0 row against a batch of one"

@@ -21,6 +21,13 @@ held to (a) instead of (b) under patterns 2 and 3.
 
 It prints the trace lines of key 104 and ends with one line "RESULT ok <calls>" or "RESULT FAIL <what>".
 
+`python tests/ws_poison.py row_batch` is the case of the calls that promise to reserve NOTHING (spx_proxstep_l1_b2_batch,
+spx_proxstep_indball_l0[_binf]_batch).  A tiled spx_proxstep_l1_batch call first grows the context's workspace (its trace line
+shows that key 104 is live), so that there is a block to fill; then, between the lines "NO_WS_BEGIN" and "NO_WS_END", every
+call runs under patterns 1, 2, 3 as above -- (a), (b), (c) -- and no trace line may appear between the two markers (the caller,
+tests/test_gpu_ws_poison.py, reads them; the library flushes every trace line, the markers are flushed here).  There is no
+growth step: nothing grows.
+
 Two shapes differ from what the issue's list names, because of what the plan functions (csrc/spx_plan.hpp) do:
   * top-r at n = 3e5 under key 8 = 4 is the one-launch exact select (the front kernel of the sample-predicted pipeline needs 64
     resident workgroups): it runs, and reserves nothing.  The pipeline -- the only top-r form that reserves -- runs at
@@ -41,7 +48,9 @@ YFILL = -777.0
 TOL = 1e-12
 # every key a case touches, at its default
 DEFAULT_KEYS = {0: 0, 1: 1, 2: 1, 3: 1, 5: 0, 8: 0, 9: 0, 10: 0, 11: 1, 13: 1, 14: 1, 17: 1, 18: 0}
-CASES = ("separable", "topr", "group", "b2", "host", "batch", "ibatch", "gbatch", "gbinf_batch")
+CASES = ("separable", "topr", "group", "b2", "host", "batch", "ibatch", "gbatch", "gbinf_batch", "lhalf_batch")
+# the cases whose calls promise "workspace: NONE" (include/spx_b2_batch.h, include/spx_topr_batch.h): run_no_ws
+NO_WS_CASES = ("row_batch",)
 
 
 class Env:
@@ -918,7 +927,7 @@ def _dev2(env, a, pad=1):
     return v
 
 
-def build_batch(env):
+def build_batch(env, long_reduce=True):
     orc, nf = env.orc, env.nf
     torch = env.torch
     LB = env.s._lib.load_batch()
@@ -973,7 +982,8 @@ def build_batch(env):
     for kind, box, msk in (("l1", False, False), ("l0", True, True), ("l1", True, False), ("l0", False, False)):
         calls.append(call(kind, box, msk, R + 1, 3, True, 7100 + R + 1))
         calls.append(call(kind, box, msk, R + 1, 3, False, 7100 + R + 1))
-    calls.append(call("l1", True, False, 2048 * TILE + 1, 2, True, 7400))     # 2049 tiles: the long reduce loop
+    if long_reduce:
+        calls.append(call("l1", True, False, 2048 * TILE + 1, 2, True, 7400))     # 2049 tiles: the long reduce loop
     return calls, (0, len(calls) - 1)
 
 
@@ -1106,15 +1116,273 @@ def _build_gbatch(env, binf):
     return calls, (0, len(calls) - 1)
 
 
+def build_lhalf_batch(env):
+    """spx_proxstep_lhalf[_box]_batch through the same run_batch (csrc/spx_batch_device.hpp) and the same partials as the NormL1 /
+    NormL0 calls, tiled form only (n > 12288).  The bar of tests/test_gpu_proxstep_lhalf_batch.py: every row the bits of the
+    single call on that row (made on a context of its own, whose scratch is not the one under test), with the band rule of
+    include/spx_lhalf_batch.h for the unboxed threshold, and the oracle through arbiter.check_lhalf; the sums within 1e-12 of
+    sum |term| of math.fsum.  spx_lhalf_threshold_batch reserves nothing (one small kernel): it is used here, on the other
+    context, to read the device's thresholds, and is not a call of the case."""
+    orc, nf, arbiter, L = env.orc, env.nf, env.arbiter, env.L
+    torch = env.torch
+    LB = env.s._lib.load_lhalf_batch()
+    calls = []
+    refctx = env.new_ctx()
+
+    def p_host(lam, sig):
+        return 54.0 ** (1 / 3) * (2 * (float(sig) * float(lam))) ** (2 / 3) / 4
+
+    def stationary(a, lam, sig):
+        """the oracle's formula for the stationary point at sol = a (oracle/spx_oracle.c)"""
+        phi = np.arccos(sig * lam / 4 * (np.abs(a) / 3) ** -1.5)
+        return 2.0 / 3.0 * a * (1 + np.cos(2 * np.pi / 3 - 2.0 / 3.0 * phi))
+
+    def call(box, msk, n, rows, xkn, seed):
+        H, rng = _rows(env, n, rows, seed)
+        mask = np.zeros(n, dtype=np.uint8)
+        mask[rng.choice(n, size=max(1, n // 3), replace=False)] = 1
+        Xd, Sd, Qd = (_dev2(env, H[k]) for k in ("X", "SJ", "Q"))
+        P1 = {k: env.dev(H[k]) for k in ("lam", "sig", "qs", "dl")}
+        md, lo = env.dev(mask), env.dev(-H["dl"])
+        name = "spx_proxstep_lhalf%s_batch mask=%d n=%d rows=%d xkn=%d" % ("_box" if box else "", msk, n, rows, xkn)
+        single = {}
+
+        def run(env):
+            Y, K = _dev2(env, np.full((rows, n), YFILL)), (_dev2(env, np.full((rows, n), POISON)) if xkn else None)
+            out = torch.full((rows, 3), POISON, dtype=torch.float64, device="cuda:0")
+            head = (env.ctx, P(Y), P(Qd), P(Xd), P(Sd), n, rows, n + 1, P(P1["lam"]), P(P1["sig"]))
+            if box:
+                rc = LB.spx_proxstep_lhalf_box_batch(*head, P(lo), P(P1["dl"]), P(md) if msk else None, P(P1["qs"]), P(K), P(out))
+            else:
+                rc = LB.spx_proxstep_lhalf_batch(*head, P(P1["qs"]), P(K), P(out))
+            assert rc == 0, (name, rc, L.spx_last_error())
+            res = {"y": host(Y), "stats": host(out)}
+            if xkn:
+                res["xkn"] = host(K)
+            return res
+
+        def single_call(b):
+            """spx_proxstep_lhalf[_box] on row b with host copies of its scalars, on the other context: (y, xkn)"""
+            if b not in single:
+                q, x, sj = (env.dev(H[k][b]) for k in ("Q", "X", "SJ"))
+                y, k = env.fill(n), env.fill(n, value=POISON)
+                st = (_D * 3)()
+                lam, sig, qs, dl = (float(H[k][b]) for k in ("lam", "sig", "qs", "dl"))
+                if box:
+                    rc = L.spx_proxstep_lhalf_box(refctx, P(y), P(q), P(x), P(sj), n, lam, sig, None, None, -dl, dl, P(md) if msk else None,
+                                                  qs, P(k), st, None)
+                else:
+                    rc = L.spx_proxstep_lhalf(refctx, P(y), P(q), P(x), P(sj), n, lam, sig, qs, P(k), st, None)
+                assert rc == 0, (name, "single call", rc, L.spx_last_error())
+                single[b] = (host(y), host(k))
+            return single[b]
+
+        def thresholds():
+            pd = env.fill(rows, value=POISON)
+            rc = LB.spx_lhalf_threshold_batch(refctx, P(P1["lam"]), P(P1["sig"]), rows, P(pd))
+            assert rc == 0, (name, "threshold", rc, L.spx_last_error())
+            assert L.spx_sync(refctx) == 0
+            return host(pd)
+
+        def check(env, out):
+            pd = None if box else thresholds()
+            for b in range(rows):
+                what = "%s row %d" % (name, b)
+                lam, sig, qs, dl = (float(H[k][b]) for k in ("lam", "sig", "qs", "dl"))
+                q, x, sj = H["Q"][b], H["X"][b], H["SJ"][b]
+                qb = qs * q                                       # one rounded multiply per element
+                y = out["y"][b]
+                ys, ks = single_call(b)
+                xs = x + sj
+                band = np.zeros(n, dtype=bool)
+                if not box:                                       # the band rule: between the host's threshold and the device's
+                    ph = p_host(lam, sig)
+                    assert abs(pd[b] - ph) <= 4 * np.spacing(ph), (what, pd[b], ph)
+                    a = np.abs(qb + xs)
+                    band = (a <= ph) != (a <= pd[b])
+                    for i in np.flatnonzero(band):
+                        if a[i] <= pd[b]:
+                            assert y[i] == 0.0 - xs[i], (what, i)
+                        else:
+                            st = stationary(np.array([qb[i] + xs[i]]), lam, sig)[0] - xs[i]
+                            assert abs(y[i] - st) <= TOL * max(abs(y[i]), abs(xs[i]), abs(q[i])), (what, i)
+                assert same_bits(y[~band], ys[~band]), (what, "the single call's bits")
+                if xkn:
+                    assert same_bits(out["xkn"][b], xs + y), (what, "xkn")
+                    assert same_bits(out["xkn"][b][~band], ks[~band]), (what, "the single call's xkn")
+                m = mask if msk else None
+                with np.errstate(all="ignore"):
+                    if box:
+                        ref = orc.prox_lhalf_box(qb, x, sj, lam, sig, -dl, dl, mask=m)
+                    else:
+                        ref = orc.prox_lhalf(qb, x, sj, lam, sig)
+                    yo = np.where(band, ref, y)                   # (the band's elements were held to their branch above)
+                    arbiter.check_lhalf(orc, yo, ref, qb, x, sj, lam, sig, box=(-dl, dl) if box else None, mask=m, what=what)
+                v = xs + y
+                sel = mask.astype(bool) if msk else np.ones(n, dtype=bool)
+                sum_bar(out["stats"][b, 0], nf.h_terms("lhalf", v[sel]), what + " [0]", lam)
+                sum_bar(out["stats"][b, 1], q * y, what + " [1]")
+                sum_bar(out["stats"][b, 2], y * y, what + " [2]")
+
+        return Call(name, run, check)
+
+    n = R + TILE + 1                                                  # 15 361: five tiles and one element
+    for box, msk in ((False, False), (True, False), (True, True)):
+        calls.append(call(box, msk, n, 3, True, 7800 + n))
+        calls.append(call(box, msk, n, 3, False, 7800 + n))
+    calls.append(call(True, True, R + 6 * TILE + 1, 3, True, 7900))   # 30 721: the growth step's larger block
+    return calls, (0, len(calls) - 1)
+
+
+def _b2_chi0(q, xk, sj, ls):
+    """chi(ProjB(-xk)) = ||min(max(-xk, (sj + q) - ls), (sj + q) + ls)||: the radius below which the trust region is active"""
+    sq = sj + q
+    return math.sqrt(fsum(np.minimum(np.maximum(-xk, sq - ls), sq + ls) ** 2))
+
+
+def build_row_batch(env):
+    """The one-workgroup-per-row batched calls, spx_proxstep_l1_b2_batch and spx_proxstep_indball_l0[_binf]_batch, at n = 1000
+    (the row in registers) and n = 8200 (the row walk), rows = 3, ld = n (the pairs form) and ld = n + 1 (element-wise),
+    against the oracle at the bars of tests/test_gpu_proxstep_b2_batch.py and tests/test_gpu_proxstep_topr_batch.py.
+    -> (the warm-up call that grows the workspace, the calls)"""
+    orc, L = env.orc, env.L
+    torch = env.torch
+    LB2, LT = env.s._lib.load_b2_batch(), env.s._lib.load_topr_batch()
+    calls = []
+    rows = 3
+
+    def data(n, pad, seed):
+        H, rng = _rows(env, n, rows, seed)
+        D = {k: _dev2(env, H[k], pad) for k in ("X", "SJ", "Q")}
+        return H, rng, D
+
+    def outputs(n, pad):
+        Y, K = _dev2(env, np.full((rows, n), YFILL), pad), _dev2(env, np.full((rows, n), POISON), pad)
+        return Y, K, torch.full((rows, 3), POISON, dtype=torch.float64, device="cuda:0")
+
+    def b2_call(n, pad):
+        H, rng, D = data(n, pad, 8300 + n)
+        H["lam"] = rng.uniform(0.05, 0.6, size=rows)
+        dl = np.empty(rows)
+        kinds = ["active", "inactive", "active"]
+        for b in range(rows):
+            c = _b2_chi0(H["qs"][b] * H["Q"][b], H["X"][b], H["SJ"][b], H["lam"][b] * H["sig"][b])
+            dl[b] = 0.3 * c if kinds[b] == "active" else 2.0 * c + 1.0
+        P1 = {k: env.dev(a) for k, a in (("lam", H["lam"]), ("sig", H["sig"]), ("qs", H["qs"]), ("dl", dl))}
+        name = "spx_proxstep_l1_b2_batch n=%d rows=%d ld=n+%d" % (n, rows, pad)
+
+        def run(env):
+            Y, K, out = outputs(n, pad)
+            rc = LB2.spx_proxstep_l1_b2_batch(env.ctx, P(Y), P(D["Q"]), P(D["X"]), P(D["SJ"]), n, rows, n + pad, P(P1["lam"]), P(P1["sig"]),
+                                              P(P1["dl"]), P(P1["qs"]), _D(1.0), P(K), P(out))
+            assert rc == 0, (name, rc, L.spx_last_error())
+            return {"y": host(Y), "xkn": host(K), "stats": host(out)}
+
+        def check(env, out):
+            for b in range(rows):
+                what = "%s row %d (%s)" % (name, b, kinds[b])
+                q, x, sj, lam = H["Q"][b], H["X"][b], H["SJ"][b], float(H["lam"][b])
+                ref = orc.prox_l1_b2(H["qs"][b] * q, x, sj, lam, float(H["sig"][b]), float(dl[b]))
+                y = out["y"][b]
+                scale = max(float(np.linalg.norm(ref)), float(np.linalg.norm(x)))
+                err = float(np.max(np.abs(y - ref)))
+                assert np.isfinite(y).all() and err <= TOL * scale, (what, err, scale)
+                v = (x + sj) + y
+                assert same_bits(out["xkn"][b], v), (what, "xkn")
+                sum_bar(out["stats"][b, 0], np.abs(v), what + " [0]", lam)
+                sum_bar(out["stats"][b, 1], q * y, what + " [1]")
+                sum_bar(out["stats"][b, 2], y * y, what + " [2]")
+                if kinds[b] == "inactive":
+                    assert same_bits(y, ref), (what, "an inactive row equals the oracle")
+                else:
+                    nrm = math.sqrt(fsum((sj + y) ** 2))
+                    assert abs(nrm - dl[b]) <= TOL * dl[b], (what, nrm, dl[b])
+
+        return Call(name, run, check)
+
+    def topr_call(binf, n, pad):
+        H, rng, D = data(n, pad, 8400 + n)
+        r = np.array([n // 100, n // 2, n - 1], dtype=np.int64)
+        rd = env.dev(r)
+        P1 = {k: env.dev(H[k]) for k in ("qs", "dl")}
+        name = "spx_proxstep_indball_l0%s_batch n=%d rows=%d ld=n+%d" % ("_binf" if binf else "", n, rows, pad)
+
+        def run(env):
+            Y, K, out = outputs(n, pad)
+            head = (env.ctx, P(Y), P(D["Q"]), P(D["X"]), P(D["SJ"]), n, rows, n + pad, P(rd))
+            if binf:
+                rc = LT.spx_proxstep_indball_l0_binf_batch(*head, P(P1["dl"]), P(P1["qs"]), P(K), P(out))
+            else:
+                rc = LT.spx_proxstep_indball_l0_batch(*head, P(P1["qs"]), P(K), P(out))
+            assert rc == 0, (name, rc, L.spx_last_error())
+            return {"y": host(Y), "xkn": host(K), "stats": host(out)}
+
+        def check(env, out):
+            for b in range(rows):
+                what = "%s row %d" % (name, b)
+                q, x, sj = H["Q"][b], H["X"][b], H["SJ"][b]
+                top = orc.TopR(H["qs"][b] * q, x, sj)
+                ref = top.prox(int(r[b]), float(H["dl"][b])) if binf else top.prox(int(r[b]))
+                y = out["y"][b]
+                assert same_bits(y, ref), (what, "against the oracle")
+                v = (x + sj) + y
+                assert same_bits(out["xkn"][b], v), (what, "xkn")
+                assert float(out["stats"][b, 0]) == float(np.count_nonzero(v != 0.0)), (what, "[0]", out["stats"][b, 0])
+                sum_bar(out["stats"][b, 1], q * y, what + " [1]")
+                sum_bar(out["stats"][b, 2], y * y, what + " [2]")
+
+        return Call(name, run, check)
+
+    for n in (1000, 8192 + 8):
+        for pad in (0, 1):
+            calls.append(b2_call(n, pad))
+            calls.append(topr_call(False, n, pad))
+            calls.append(topr_call(True, n, pad))
+    warm = build_batch(env, long_reduce=False)[0][0]                  # spx_proxstep_l1_batch, tiled: n = 12 289, rows = 3
+    assert warm.name.startswith("spx_proxstep_l1_batch mask=0 n=%d" % (R + 1)), warm.name
+    return warm, calls
+
+
+def run_no_ws(name):
+    """the calls that reserve nothing, on a context whose workspace an earlier tiled call has grown (see the module's text)"""
+    env = Env()
+    L = env.L
+    warm, calls = NO_WS_BUILDERS[name](env)
+    env.key(104, 1)
+    warm.check(env, make(env, warm, 1))
+    assert L.spx_sync(env.ctx) == 0
+    sys.stdout.flush()
+    print("NO_WS_BEGIN", flush=True)
+    base = {}
+    done = 0
+    for pattern in (1, 2, 3):
+        for i, call in enumerate(calls):
+            what = "%s pattern %d call %d (%s)" % (name, pattern, i, call.name)
+            out = make(env, call, pattern)
+            if pattern == 1:
+                call.check(env, out)
+                base[i] = out
+            else:
+                compare(base[i], out, what)
+            done += 1
+        rc = L.spx_sync(env.ctx)
+        assert rc == 0, ("%s pattern %d: spx_sync" % (name, pattern), rc, L.spx_last_error())
+    print("NO_WS_END", flush=True)
+    env.key(103, 0)
+    env.key(104, 0)
+    return done
+
+
 BUILDERS = {"separable": build_separable, "topr": build_topr, "group": build_group, "b2": build_b2, "host": build_host,
             "batch": build_batch, "ibatch": build_ibatch, "gbatch": lambda env: _build_gbatch(env, False),
-            "gbinf_batch": lambda env: _build_gbatch(env, True)}
+            "gbinf_batch": lambda env: _build_gbatch(env, True), "lhalf_batch": build_lhalf_batch}
+NO_WS_BUILDERS = {"row_batch": build_row_batch}
 
 
 def main(argv):
     name = argv[1]
     try:
-        done = run_case(name)
+        done = run_no_ws(name) if name in NO_WS_CASES else run_case(name)
     except BaseException as e:           # (the first mismatch ends the case)
         traceback.print_exc()
         sys.stdout.flush()
